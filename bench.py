@@ -2,7 +2,7 @@
 """
 bench.py -- Mvoxel/s of Nellie's segmentation hot path (5-scale Frangi Filter + Label) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--shape Z Y X] [--no-cpu-baseline] [--no-io]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--shape Z Y X] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-io]]
 
 One "step" = one pass of the whole hot path (float32 conversion, 5-scale Gaussian cascade, Hessian, eigenvalues, Frangi,
 scale-max, masks, percentile mask + opening, Label thresholds, hole filling, two 26-connected labellings, area filter,
@@ -22,8 +22,14 @@ N > 1: ONE volume cut into Z slabs over the N GPUs (nellie_amd/sharded.py): ever
        frame-replica figure (one 1024^3 frame per GPU, no data-path collective) is a different workload and is only
        ever reported as `replicas`.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and `cpu_baseline`.
-The oracle is used here only for the `cpu_baseline` leg and the accuracy check that rides with it.
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run does only what that line's headline needs: set up, warm
+up, time the steps, print.  `--full` adds everything else to the same line: `roofline` (per-group timers, queue fractions, a
+rocprofv3 --pmc pass), the host-to-host and streamed `io` figures, `cpu_baseline` (+ all cores) and `accuracy`; those keys are
+null in a plain run.  The oracle is used here only for the `cpu_baseline` leg and the accuracy check that rides with it.
+
+--dump-outputs DIR (N = 1): after the timed steps, what the last step computed -- DIR/frangi.npy (float32), DIR/labels.npy (the
+labels as float64) and DIR/n_labels.npy -- whole when the frame has at most DUMP_SAMPLE voxels, else at the same DUMP_SAMPLE
+voxels (seeded, sorted flat indices) of every run: with the same arguments two builds can be compared output for output.
 """
 import argparse
 import json
@@ -82,6 +88,8 @@ GROUPS = ("load",) + GAUSS_ZYX + ("gauss_z", "gauss_yx", "gauss_y", "gauss_x", "
           "finish", "mask_volume", "label", "halo", "halo_wait")
 SLAB_PLANES = 128              # owned planes per GPU of the Z-slab run: BASELINE config 4 / 8
 SLAB_YX = (2048, 2048)
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: voxels per output (float32 Frangi + float64 labels: 48 MB)
+DUMP_SEED = 20240521
 
 
 def pmc_profile_file():
@@ -287,6 +295,10 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--shape", type=int, nargs=3, default=None, help="frame Z Y X (default 1024^3)")
     ap.add_argument("--seed", type=int, default=2345)
+    ap.add_argument("--full", action="store_true",
+                    help="also roofline, io, CPU-baseline and accuracy figures (a plain run: set up, warm up, timed steps, the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write the last timed step's outputs to DIR/<name>.npy (a fixed sample of a large frame)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-shape", type=int, nargs=3, default=[256, 512, 512], help="CPU baseline sample (default: BASELINE config 2)")
     ap.add_argument("--no-io", action="store_true", help="skip the host-to-host and streamed figures")
@@ -620,6 +632,22 @@ def roofline_of(groups, shape, steps, ms_per_step, pmc=None, facts=None):
     return out
 
 
+def dump_outputs(pipe, out_dir, n_labels):
+    """--dump-outputs: the outputs of the last timed step, still in HBM, as float32 / float64 .npy files (see the header)."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    n = int(np.prod(pipe.shape))
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    fr = pipe.download_frangi()
+    np.save(os.path.join(out_dir, "frangi.npy"), (fr if idx is None else fr.reshape(-1)[idx]).astype(np.float32))
+    del fr
+    lab = pipe.download_labels()
+    np.save(os.path.join(out_dir, "labels.npy"), (lab if idx is None else lab.reshape(-1)[idx]).astype(np.float64))
+    del lab
+    np.save(os.path.join(out_dir, "n_labels.npy"), np.array([n_labels], np.float64))
+
+
 def main():
     args = parse_args()
     if args.cpu_all_cores_child:
@@ -637,6 +665,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and max(world, args.gpus) > 1:
+        raise SystemExit("--dump-outputs: only with --gpus 1")
     if world == 1 and args.gpus > 1:
         # started by hand as `python bench.py --gpus N`: become the launcher the contract describes (one rank per GPU)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -698,36 +728,41 @@ def main():
         dist.barrier("step")
         elapsed = dist.max("elapsed", elapsed)     # ... and the figure is the maximum over the ranks (see Control)
     pipe.ctx.prof_enable(False)
-
-    groups = {}
-    for name in GROUPS:
-        ms, k = pipe.ctx.prof_get(name)
-        if k:
-            groups[name] = {"ms_total": ms, "launches": k, "ms_avg": ms / k}
     n_local = float(np.prod(shape))
     ms_per_step = elapsed / args.steps * 1e3
     tr = pipe.trace
-    # what the fused-design byte model needs from the run (outside the timed region): queue entries per scale, mask / survival fractions
-    sig = p.resolved_sigmas()
-    d0 = pl.cascade_deltas(sig, pl.z_ratio_of(ISO_01))[0] if len(sig) else (0.0, 0.0, 0.0)
-    facts = {"queue_fraction_per_scale": queue_fractions(pl, pipe, p),
-             "mask_fraction_per_scale": [round(sc.mask_count / n_local, 4) for sc in tr.scales],
-             "mask_fraction_min": round(min([sc.mask_count / n_local for sc in tr.scales if not sc.skipped] or [0.0]), 4),
-             "survival": round(tr.n_positive / n_local, 5),
-             "zeroing_group": "gauss_zyx<%d,%d>" % (int(3.0 * d0[0] + 0.5), int(3.0 * d0[1] + 0.5))}
-    pmc = None
-    if rank == 0 and world == 1 and not args.no_pmc:
-        t_pmc = time.perf_counter()
-        pmc = pmc_this_run(shape, args.seed, vol)
-        facts["pmc_this_run_s"] = round(time.perf_counter() - t_pmc, 1)
-    roofline = roofline_of(groups, shape, args.steps, ms_per_step, pmc=pmc, facts=facts)
-    # Since round 5 the chain runs the resolve kernel of scale s on the side stream beside the threshold kernels ("sample") of scale s+1
-    # on volumes of 2^26 voxels and more (nl_chain_scale).  Each group's HIP-event timer then counts the time it shared: the groups sum
-    # to more than the step.  Say so in the line instead of leaving a sum that exceeds `ms_per_step` unexplained.
-    if os.environ.get("NELLIE_RESOLVE_DEFER", "1") != "0" and float(np.prod(shape)) >= float(1 << 26) and pipe._chain_usable(p, True):
-        roofline["pipeline"]["overlapped_groups"] = ["sample", "vesselness_resolve"]
-        roofline["pipeline"]["kernel_ms_per_step_note"] = ("sample and vesselness_resolve run side by side on two streams; their timers each count "
-                                                          "the shared time, so kernel_ms_per_step (the sum of the groups) exceeds ms_per_step")
+    if args.dump_outputs:
+        dump_outputs(pipe, args.dump_outputs, n_labels)
+
+    # ---- --full: the roofline object (per-group timers of the timed steps, one more frame for the queue fractions, the PMC pass)
+    roofline = None
+    if args.full:
+        groups = {}
+        for name in GROUPS:
+            ms, k = pipe.ctx.prof_get(name)
+            if k:
+                groups[name] = {"ms_total": ms, "launches": k, "ms_avg": ms / k}
+        # what the fused-design byte model needs from the run (outside the timed region): queue entries per scale, mask / survival fractions
+        sig = p.resolved_sigmas()
+        d0 = pl.cascade_deltas(sig, pl.z_ratio_of(ISO_01))[0] if len(sig) else (0.0, 0.0, 0.0)
+        facts = {"queue_fraction_per_scale": queue_fractions(pl, pipe, p),
+                 "mask_fraction_per_scale": [round(sc.mask_count / n_local, 4) for sc in tr.scales],
+                 "mask_fraction_min": round(min([sc.mask_count / n_local for sc in tr.scales if not sc.skipped] or [0.0]), 4),
+                 "survival": round(tr.n_positive / n_local, 5),
+                 "zeroing_group": "gauss_zyx<%d,%d>" % (int(3.0 * d0[0] + 0.5), int(3.0 * d0[1] + 0.5))}
+        pmc = None
+        if rank == 0 and world == 1 and not args.no_pmc:
+            t_pmc = time.perf_counter()
+            pmc = pmc_this_run(shape, args.seed, vol)
+            facts["pmc_this_run_s"] = round(time.perf_counter() - t_pmc, 1)
+        roofline = roofline_of(groups, shape, args.steps, ms_per_step, pmc=pmc, facts=facts)
+        # Since round 5 the chain runs the resolve kernel of scale s on the side stream beside the threshold kernels ("sample") of scale s+1
+        # on volumes of 2^26 voxels and more (nl_chain_scale).  Each group's HIP-event timer then counts the time it shared: the groups sum
+        # to more than the step.  Say so in the line instead of leaving a sum that exceeds `ms_per_step` unexplained.
+        if os.environ.get("NELLIE_RESOLVE_DEFER", "1") != "0" and float(np.prod(shape)) >= float(1 << 26) and pipe._chain_usable(p, True):
+            roofline["pipeline"]["overlapped_groups"] = ["sample", "vesselness_resolve"]
+            roofline["pipeline"]["kernel_ms_per_step_note"] = ("sample and vesselness_resolve run side by side on two streams; their timers each count "
+                                                              "the shared time, so kernel_ms_per_step (the sum of the groups) exceeds ms_per_step")
     chain_info = {"enabled": bool(pipe._chain_usable(p, True)), "frames_redone_synchronously": int(pipe.chain_fallbacks),
                   "last_flags": getattr(pipe, "last_chain_flags", None)}
     fast_div = int(pipe.ctx.info("fast_div"))
@@ -735,7 +770,7 @@ def main():
     pipe.close()
 
     io = None
-    if not args.no_io and world == 1:
+    if args.full and not args.no_io and world == 1:
         io = io_figures(pl, hipnative, shape, p, min_area, vol)
     del vol
 
@@ -744,7 +779,7 @@ def main():
         cpu = None
         acc = None
         cpu_all = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu, (cvol, crun, cfr, cthr, clab) = cpu_baseline(tuple(args.cpu_shape), 1234)
             acc = accuracy_check(pl, cvol, crun, cfr, cthr, clab)
             del cvol, crun, cfr, clab

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Produces the files committed under profiles/ (run on the GPU box through gpurun; results land in gpurun_out/):
-#   ${PFX}_bench_n1_1024cube.json       the default bench line
+#   ${PFX}_bench_n1_1024cube.json       the full bench line (bench.py --full), written to $BENCH_OUT
 #   ${PFX}_kernel_stats_1024cube.csv    rocprofv3 --kernel-trace --stats summary of the same bench command
 #   ${PFX}_pmc_hbm_bytes_1024cube.json  HBM bytes per kernel launch: FETCH_SIZE and WRITE_SIZE in SEPARATE --pmc passes
 #                                    (KB units; FETCH_SIZE is doubled on gfx950, see MI355X_MICROARCH.md)
@@ -8,9 +8,10 @@
 #                                    world 1 over a real one-rank RCCL communicator): what a rank costs before any neighbour exists
 R=${GRAFT_REPO_ROOT:-/root/repo}
 PFX=${PFX:-r05}
+BENCH_OUT=${BENCH_OUT:-$R/profiles}      # the full bench line (--full) lands in the folder it is committed in
 cd /tmp && export TMPDIR=/tmp
-if [ "$1" != "nobench" ]; then python $R/bench.py --steps 10 --warmup 2 > /tmp/bench.out 2>/tmp/bench.err; tail -1 /tmp/bench.out > $R/gpurun_out/${PFX}_bench_n1_1024cube.json; fi
-rm -rf /tmp/ks && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-io > /tmp/ks.log 2>&1
+if [ "$1" != "nobench" ]; then python $R/bench.py --full --steps 10 --warmup 2 > /tmp/bench.out 2>/tmp/bench.err; tail -1 /tmp/bench.out > "$BENCH_OUT/${PFX}_bench_n1_1024cube.json"; fi
+rm -rf /tmp/ks && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-io > /tmp/ks.log 2>&1
 cp $(find /tmp/ks -name '*kernel_stats.csv' | head -1) $R/gpurun_out/${PFX}_kernel_stats_1024cube.csv
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$C && rocprofv3 --pmc $C --output-format csv -d /tmp/pmc_$C -- python $R/tools/prof_filter.py 1024 1024 1024 1 > /tmp/pmc_$C.log 2>&1
@@ -35,7 +36,7 @@ for k in sorted(f, key=lambda k: -f[k]):
 json.dump(out, sys.stdout, indent=1)
 PY
 OMP_NUM_THREADS=1 OPENBLAS_NUM_THREADS=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 python $R/bench.py --zslab-child --gpus 1 --steps 10 --warmup 2 2>/tmp/zs.err | tail -1 > $R/gpurun_out/${PFX}_zslab_world1_128x2048x2048.json
-tail -2 /tmp/ks.log; tail -c 600 $R/gpurun_out/${PFX}_bench_n1_1024cube.json
+tail -2 /tmp/ks.log; tail -c 600 "$BENCH_OUT/${PFX}_bench_n1_1024cube.json"
 # r03 additions: the SAME 8-slab volume (BASELINE config 4) as 8 slab contexts on this one GPU over the loopback transport,
 # kernel stats of the slab step at world 1, GPU idle time of a config-5 frame with and without the device-resident chain
 cd $R
