@@ -531,6 +531,29 @@ int nl_outputs_unpack(const void *blob, int64_t nbytes, float *frangi, int32_t *
    then only scatters the non-zero items. */
 int nl_host_zero(void *dst, int64_t bytes, int threads, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ Hu-moment tracking -------- */
+/* nellie/tracking/hu_tracking.py on the device (DESIGN.md "Tracking").  A tracker has its own stream and buffers (marker-sized ones
+   grow with the marker count, never shrink); it keeps the features of the last two frames resident.
+   nl_track_create   : frame shape (nz = 1 for ndim 2) and spacing ((Z,) Y, X in um) of the T stack.
+   nl_track_frame    : uploads intensity (uint8 / uint16 / float32), frangi, distance (float32) and marker (uint8) of one frame
+                       and computes its markers (np.argwhere order), radii, stats and log-Hu features; the frame before stays
+                       resident as the "pre" frame.  n_markers = the frame's marker count.
+   nl_track_features : which = 0 the last frame, 1 the one before: coords (n, ndim) int64, stats (n, 4) float32, log-Hu
+                       (n, 6 | 18) float64; NULL pointers are skipped.
+   nl_track_match    : last frame (rows) against the one before (columns); mode 0 dense, 1 sparse; row_* has n_post entries,
+                       col_* n_pre; index -1 = no candidate (sparse); full (dense, may be NULL) = the float16 cost matrix.
+   nl_host_half_round / nl_host_half_nansum : the float64 -> float16 cast and np.nansum of float16 rows the dense matcher uses. */
+typedef struct nl_track nl_track;
+int nl_track_create(nl_track **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, const double *spacing, char *err, size_t errlen);
+int nl_track_destroy(nl_track *tracker);
+int nl_track_frame(nl_track *tracker, const void *intensity, int dtype, const float *frangi, const float *distance, const uint8_t *marker,
+                   int64_t *n_markers, char *err, size_t errlen);
+int nl_track_features(nl_track *tracker, int which, int64_t *coords, float *stats, double *hu, char *err, size_t errlen);
+int nl_track_match(nl_track *tracker, int mode, double max_distance, int32_t *row_idx, float *row_cost, int32_t *col_idx,
+                   float *col_cost, uint16_t *full, char *err, size_t errlen);
+int nl_host_half_round(const double *in, uint16_t *out, int64_t n, char *err, size_t errlen);
+int nl_host_half_nansum(const uint16_t *in, int64_t rows, int k, uint16_t *out, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit
    Hessians h6[n][6] = (hxx,hxy,hxz,hyy,hyz,hzz) writes out4[n][4] = (l1,l2,l3 sorted by |.|, Frangi

@@ -142,6 +142,12 @@ _PROTOS = {
     "nl_debug_eig_frangi": [_p, _p, _i64, _int, _f32, _f32, _f32, _p],
     "nl_timer_begin": [_p],
     "nl_timer_end_ms": [_p, C.POINTER(_f32)],
+    "nl_track_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p],
+    "nl_track_frame": [_p, _p, _int, _p, _p, _p, C.POINTER(_i64)],
+    "nl_track_features": [_p, _int, _p, _p, _p],
+    "nl_track_match": [_p, _int, _f64, _p, _p, _p, _p, _p],
+    "nl_host_half_round": [_p, _p, _i64],
+    "nl_host_half_nansum": [_p, _i64, _int, _p],
 }
 # functions without the (err, errlen) tail
 _PLAIN = {
@@ -154,6 +160,7 @@ _PLAIN = {
     "nl_pinned_free": (_int, [_p]),
     "nl_host_unregister": (_int, [_p]),
     "nl_ctx_info": (_int, [_p, C.c_char_p, C.POINTER(_f64)]),
+    "nl_track_destroy": (_int, [_p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
 
@@ -309,6 +316,22 @@ def host_zero(array, threads=8):
     Python thread beside the GPU calls of the frame whose outputs the array will receive)."""
     assert array.flags.c_contiguous and array.flags.writeable
     load().call("nl_host_zero", _ptr(array), int(array.nbytes), int(threads))
+
+
+def host_half_round(x):
+    """numpy's float64 -> float16 cast as the dense tracking matcher does it (include/nellie_amd.h nl_host_half_round)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty(x.shape, np.float16)
+    load().call("nl_host_half_round", _ptr(x), _ptr(out), x.size)
+    return out
+
+
+def host_half_nansum(h):
+    """np.nansum(h, axis=-1) of float16 rows (row length <= 23) as the dense tracking matcher does it"""
+    h = np.ascontiguousarray(h, dtype=np.float16)
+    out = np.empty(h.shape[:-1], np.float16)
+    load().call("nl_host_half_nansum", _ptr(h), int(np.prod(h.shape[:-1])), int(h.shape[-1]), _ptr(out))
+    return out
 
 
 def comm_unique_id(loopback: bool = False) -> bytes:
@@ -1029,3 +1052,77 @@ class Context:
         ms, k = _f64(0), _i64(0)
         self.lib.cdll.nl_prof_get(self._h, name.encode(), C.byref(ms), C.byref(k))
         return float(ms.value), int(k.value)
+
+
+class Tracker:
+    """Device state of Hu-moment tracking for one T stack (include/nellie_amd.h nl_track_*): the features of the last two
+    frames stay on the device, so matching a frame against the one before uploads nothing."""
+
+    def __init__(self, shape, spacing, device=0):
+        self.lib = load()
+        self.ndim = len(shape)
+        if self.ndim not in (2, 3):
+            raise ValueError(f"tracking frames are 2-D or 3-D, got shape {tuple(shape)}")
+        self.shape = tuple(int(s) for s in shape)
+        self.nh = 6 if self.ndim == 2 else 18
+        nz, ny, nx = (1,) + self.shape if self.ndim == 2 else self.shape
+        sp = np.ascontiguousarray(spacing, dtype=np.float64)
+        if sp.size != self.ndim:
+            raise ValueError(f"spacing needs {self.ndim} values")
+        h = _p()
+        self.lib.call("nl_track_create", C.byref(h), int(device), self.ndim, nz, ny, nx, _ptr(sp))
+        self._h = h
+        self.n = [0, 0]                                   # markers of the last frame, of the one before
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.cdll.nl_track_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _call(self, name, *args):
+        if not self._h:
+            raise NellieHipError(NL_ESTATE, "tracker is closed")
+        self.lib.call(name, self._h, *args)
+
+    def frame(self, intensity, frangi, distance, marker) -> int:
+        arrs = []
+        for a, dt in ((intensity, None), (frangi, np.float32), (distance, np.float32), (marker, np.uint8)):
+            a = np.asarray(a)
+            if a.shape != self.shape:
+                raise ValueError(f"frame shape {a.shape} does not match the tracker's {self.shape}")
+            if dt is not None and a.dtype != dt:
+                a = (a > 0).astype(np.uint8) if dt == np.uint8 else a.astype(dt)
+            arrs.append(np.ascontiguousarray(a))
+        code = DTYPE_CODES.get(arrs[0].dtype)
+        if code is None:
+            raise ValueError(f"unsupported intensity dtype {arrs[0].dtype}")
+        n = _i64(0)
+        self._call("nl_track_frame", _ptr(arrs[0]), code, _ptr(arrs[1]), _ptr(arrs[2]), _ptr(arrs[3]), C.byref(n))
+        self.n = [int(n.value), self.n[0]]
+        return self.n[0]
+
+    def features(self, which=0):
+        n = self.n[which]
+        coords = np.zeros((n, self.ndim), np.int64)
+        stats = np.zeros((n, 4), np.float32)
+        hu = np.zeros((n, self.nh), np.float64)
+        self._call("nl_track_features", int(which), _ptr(coords), _ptr(stats), _ptr(hu))
+        return coords, stats, hu
+
+    def match(self, mode, max_distance, full=False):
+        """(row_idx, row_cost, col_idx, col_cost[, float16 cost matrix]) of the last frame against the one before"""
+        n_post, n_pre = self.n
+        ri, rc = np.full(n_post, -1, np.int32), np.full(n_post, np.inf, np.float32)
+        ci, cc = np.full(n_pre, -1, np.int32), np.full(n_pre, np.inf, np.float32)
+        m = np.full((n_post, n_pre), np.inf, np.float16) if full else None
+        self._call("nl_track_match", 0 if mode == "dense" else 1, float(max_distance), _ptr(ri), _ptr(rc), _ptr(ci), _ptr(cc),
+                   None if m is None else _ptr(m))
+        return (ri, rc, ci, cc, m) if full else (ri, rc, ci, cc)

@@ -3,7 +3,8 @@
 MI355X engine, same keyword names, same `timeit` prints.  The later stages (Network, Markers, tracking,
 Hierarchy) are Nellie's own and consume the two files this writes; `markers=True` also runs this package's
 Markers stage (reference run.py:88-89; it does not depend on Network) and writes im_marker / im_distance /
-im_border.
+im_border; `tracking=True` then runs this package's HuMomentTracking on them (run.py:91-92) and writes
+flow_vector_array.
 """
 from __future__ import annotations
 
@@ -127,18 +128,23 @@ def run_streamed(im_info, viewer=None, device_index=0, devices=None, shard=None)
 
 
 def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=None, timeit=False, device="auto",
-        low_memory=False, markers=False, devices=None, shard=None):
+        low_memory=False, markers=False, devices=None, shard=None, tracking=False):
     """nellie.run.run's signature (run.py:18-26): `file_info` is a FileInfo (this package's or any object with the same
     fields) from which the ImInfo is built as run.py:49 does; an ImInfo (anything with `pipeline_paths`) or a path / array
     is accepted too.  Returns the ImInfo.
     devices=[...]: every 3-D frame runs as Z slabs over these GPUs; shard="env": this process is one rank (WORLD_SIZE / RANK /
     LOCAL_RANK) of a multi-process Z-slab job over RCCL -- see nellie_amd/engine.py.  Frames beyond one context's size are
-    cut into slabs without being asked."""
-    from nellie_amd.im_info.verifier import ImInfo
+    cut into slabs without being asked.
+    tracking=True: Hu-moment tracking after Markers; without markers=True it needs Markers' files (im_marker, im_distance)
+    and raises before anything runs if they do not exist."""
     if hasattr(file_info, "pipeline_paths"):
         im_info = file_info
     else:
         im_info = _build_im_info(file_info, shard)
+    if tracking and not markers:
+        missing = [k for k in ("im_marker", "im_distance") if not os.path.exists(im_info.pipeline_paths[k])]
+        if missing:
+            raise FileNotFoundError(f"run(tracking=True) needs Markers' outputs {missing}: run with markers=True, or run Markers first")
     t0 = time.perf_counter() if timeit else None
     preprocessing = Filter(im_info, remove_edges=remove_edges, device=device, low_memory=low_memory, devices=devices, shard=shard)
     preprocessing.run()
@@ -156,6 +162,12 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
         Markers(im_info, device=device, low_memory=low_memory, devices=devices, shard=shard).run()
         if timeit:
             print(f"[timeit] Markers: {time.perf_counter() - t2:.3f}s")
+    if tracking and not im_info.no_t:
+        from nellie_amd.tracking.hu_tracking import HuMomentTracking
+        t3 = time.perf_counter()
+        HuMomentTracking(im_info, device=device, low_memory=low_memory).run()
+        if timeit:
+            print(f"[timeit] Tracking: {time.perf_counter() - t3:.3f}s")
     if timeit:
         print(f"[timeit] Total: {time.perf_counter() - t0:.3f}s")
     return im_info
