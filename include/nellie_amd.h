@@ -542,7 +542,8 @@ int nl_host_zero(void *dst, int64_t bytes, int threads, char *err, size_t errlen
                        (n, 6 | 18) float64; NULL pointers are skipped.
    nl_track_match    : last frame (rows) against the one before (columns); mode 0 dense, 1 sparse; row_* has n_post entries,
                        col_* n_pre; index -1 = no candidate (sparse); full (dense, may be NULL) = the float16 cost matrix.
-   nl_host_half_round / nl_host_half_nansum : the float64 -> float16 cast and np.nansum of float16 rows the dense matcher uses. */
+   nl_host_half_round / nl_host_half_nansum : the float64 -> float16 cast and np.nansum of float16 rows the dense matcher uses.
+   nl_host_np_sum_f32 : numpy's float32 np.sum of n floats (8192-item blocks, pairwise inside), the order of the float stats. */
 typedef struct nl_track nl_track;
 int nl_track_create(nl_track **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, const double *spacing, char *err, size_t errlen);
 int nl_track_destroy(nl_track *tracker);
@@ -553,6 +554,7 @@ int nl_track_match(nl_track *tracker, int mode, double max_distance, int32_t *ro
                    float *col_cost, uint16_t *full, char *err, size_t errlen);
 int nl_host_half_round(const double *in, uint16_t *out, int64_t n, char *err, size_t errlen);
 int nl_host_half_nansum(const uint16_t *in, int64_t rows, int k, uint16_t *out, char *err, size_t errlen);
+int nl_host_np_sum_f32(const float *in, int64_t n, float *out, char *err, size_t errlen);
 
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit

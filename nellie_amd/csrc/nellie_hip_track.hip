@@ -268,3 +268,10 @@ extern "C" int nl_host_half_nansum(const uint16_t *in, int64_t rows, int k, uint
     for (int64_t r = 0; r < rows; ++r) out[r] = trk_half_nansum(in + r * k, k);
     return NL_OK;
 }
+
+// Host copy of numpy's float32 np.sum of a flat array, the order of the feature kernel's float stats.
+extern "C" int nl_host_np_sum_f32(const float *in, int64_t n, float *out, char *err, size_t errlen) {
+    if (!out || (!in && n > 0) || n < 0) return nl_fail(err, errlen, NL_EINVAL, "NULL buffer or negative length");
+    *out = trk_np_sum_f32(in, n);
+    return NL_OK;
+}

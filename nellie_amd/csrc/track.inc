@@ -70,6 +70,72 @@ __host__ __device__ inline uint16_t trk_half_nansum(const uint16_t *h, int k) {
     return trk_f32_to_f16(res);
 }
 
+// ---- numpy's float32 np.sum of a flat array (the float stats, DESIGN.md "Tracking"): the array is cut into 8192-item blocks
+// (the ufunc buffer), whose sums are added in order into a float32 accumulator starting at 0.  A block is numpy's
+// pairwise_sum: below 8 items in sequence, up to 128 items 8 strided accumulators, above that split at n/2 - (n/2) % 8.
+// The split tree of a block has at most 65 leaves (64..128 items each, or one leaf when the block has <= 128 items) and
+// depth <= 7; a leaf is packed as offset | length << 13 | depth << 21.
+#define TRK_PW_BLOCK 8192
+#define TRK_PW_MAXLEAF 72
+
+__host__ __device__ inline int trk_pw_leaves(int L, unsigned int *leaf) {
+    int so[16], sl[16], sd[16], sp = 0, nl = 0;
+    so[0] = 0; sl[0] = L; sd[0] = 0; sp = 1;
+    while (sp > 0) {
+        --sp;
+        const int o = so[sp], l = sl[sp], d = sd[sp];
+        if (l <= 128) { leaf[nl++] = (unsigned int)o | ((unsigned int)l << 13) | ((unsigned int)d << 21); continue; }
+        int n2 = l / 2;
+        n2 -= n2 % 8;
+        so[sp] = o + n2; sl[sp] = l - n2; sd[sp] = d + 1; ++sp;   // right pushed first: leaves come out left to right
+        so[sp] = o; sl[sp] = n2; sd[sp] = d + 1; ++sp;
+    }
+    return nl;
+}
+
+// one leaf of pairwise_sum (n <= 128 items)
+__host__ __device__ inline float trk_pw_leaf(const float *a, int n) {
+    if (n < 8) {
+        float res = 0.0f;
+        for (int i = 0; i < n; ++i) res = res + a[i];
+        return res;
+    }
+    float r[8];
+    for (int j = 0; j < 8; ++j) r[j] = a[j];
+    for (int i = 8; i < n - n % 8; i += 8)
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + a[i + j];
+    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (int i = n - n % 8; i < n; ++i) res = res + a[i];
+    return res;
+}
+
+// the block's sum from its leaf sums (left to right): a completed subtree is added to the stack's top while both have one depth
+__host__ __device__ inline float trk_pw_combine(const float *ls, const unsigned int *leaf, int nl) {
+    float v[16];
+    int d[16], sp = 0;
+    for (int k = 0; k < nl; ++k) {
+        float x = ls[k];
+        int e = (int)(leaf[k] >> 21);
+        while (sp > 0 && d[sp - 1] == e) { x = v[--sp] + x; --e; }
+        v[sp] = x; d[sp] = e; ++sp;
+    }
+    return v[0];
+}
+
+__host__ __device__ inline float trk_np_sum_f32(const float *a, i64 n) {
+    unsigned int leaf[TRK_PW_MAXLEAF];
+    float ls[TRK_PW_MAXLEAF];
+    float acc = 0.0f;
+    int nl = 0, Lp = -1;
+    for (i64 b = 0; b < n; b += TRK_PW_BLOCK) {
+        const int L = (int)(n - b < TRK_PW_BLOCK ? n - b : TRK_PW_BLOCK);
+        if (L != Lp) { nl = trk_pw_leaves(L, leaf); Lp = L; }
+        for (int k = 0; k < nl; ++k) ls[k] = trk_pw_leaf(a + b + (leaf[k] & 0x1fffu), (int)((leaf[k] >> 13) & 0xffu));
+        acc = acc + trk_pw_combine(ls, leaf, nl);
+    }
+    return acc;
+}
+
 // np.mean(row) of a float64 row of k <= 18 items: the same pairwise order in float64, then / k
 __device__ inline double trk_mean_f64(const double *a, int k) {
     double res;
@@ -232,29 +298,76 @@ __device__ inline void trk_block_sum(S (&v)[NV], S *lds /* 4 * NV */) {
     __syncthreads();
 }
 
-// [mean, variance] with the reference's dtypes: integer inputs wrap their squares in the input dtype, sum in uint64 and
-// square the sum in uint64 (modular: exact in any order); float32 sums are rounded to float32 where numpy holds them in float32
-template <typename T>
-__device__ inline void trk_stats_store(unsigned long long cnt, typename TrkAcc<T>::S s, typename TrkAcc<T>::S sq, float *out) {
+// [mean, variance] with the reference's dtypes.  Integer inputs wrap their squares in the input dtype, sum in uint64 and square
+// the sum in uint64 (modular: exact in any order).  Float32 inputs take the float32 sums of trk_np_sums_roi and square the
+// sum in float32, as numpy does.
+__device__ inline void trk_stats_store_int(unsigned long long cnt, unsigned long long s, unsigned long long sq, float *out) {
     if (cnt == 0) { out[0] = 0.0f; out[1] = 0.0f; return; }
     const double c = (double)cnt;
-    double mean, var;
-    if constexpr (std::is_same<typename TrkAcc<T>::S, unsigned long long>::value) {
-        const unsigned long long s2 = s * s;
-        mean = (double)s / c;
-        var = ((double)sq - (double)s2 / c) / c;
-    } else {
-        const float s32 = (float)s, sq32 = (float)sq;
-        mean = (double)s32 / c;
-        var = ((double)sq32 - (double)(s32 * s32) / c) / c;
-    }
-    out[0] = (float)mean;
-    out[1] = (float)var;
+    const unsigned long long s2 = s * s;
+    out[0] = (float)((double)s / c);
+    out[1] = (float)(((double)sq - (double)s2 / c) / c);
 }
 
-template <typename T> __device__ inline typename TrkAcc<T>::S trk_sq(T v) {
-    if constexpr (std::is_same<T, float>::value) return (double)(v * v);
-    else return (unsigned long long)(T)(v * v);                   // wraps in the input dtype like numpy's ** 2
+__device__ inline void trk_stats_store_f32(unsigned long long cnt, float s, float sq, float *out) {
+    if (cnt == 0) { out[0] = 0.0f; out[1] = 0.0f; return; }
+    const double c = (double)cnt;
+    out[0] = (float)((double)s / c);
+    out[1] = (float)(((double)sq - (double)(s * s) / c) / c);
+}
+
+struct TrkPwLds {
+    unsigned int leaf[TRK_PW_MAXLEAF];
+    float ls[2][TRK_PW_MAXLEAF];
+    int nl;
+};
+
+// trk_np_sum_f32 of get(e) and of get(e) * get(e) over e < n, by the whole workgroup (uniform n); the sums land in thread 0.
+// A leaf is summed by a group of 8 lanes, lane j holding accumulator j, and the lanes' butterfly is numpy's
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) (float addition commutes; only the grouping matters).
+template <typename G>
+__device__ inline void trk_np_sums_roi(i64 n, G get, TrkPwLds &P, float &s, float &sq) {
+    const int j = threadIdx.x & 7, g = threadIdx.x >> 3, ng = blockDim.x >> 3;
+    float acc0 = 0.0f, acc1 = 0.0f;
+    int Lp = -1;
+    for (i64 b = 0; b < n; b += TRK_PW_BLOCK) {
+        const int L = (int)(n - b < TRK_PW_BLOCK ? n - b : TRK_PW_BLOCK);
+        if (L != Lp) {
+            if (threadIdx.x == 0) P.nl = trk_pw_leaves(L, P.leaf);
+            __syncthreads();
+            Lp = L;
+        }
+        const int nl = P.nl;
+        for (int k = g; k < nl; k += ng) {
+            const unsigned int lf = P.leaf[k];
+            const i64 o = b + (lf & 0x1fffu);
+            const int l = (int)((lf >> 13) & 0xffu), e8 = l - l % 8;
+            float r0 = 0.0f, r1 = 0.0f;
+            if (l >= 8) {
+                r0 = get(o + j);
+                r1 = r0 * r0;
+                for (int i = 8 + j; i < e8; i += 8) { const float v = get(o + i); r0 = r0 + v; r1 = r1 + v * v; }
+                for (int m = 1; m < 8; m <<= 1) { r0 = r0 + __shfl_xor(r0, m); r1 = r1 + __shfl_xor(r1, m); }
+            }
+            if (j == 0) {
+                for (int i = e8; i < l; ++i) { const float v = get(o + i); r0 = r0 + v; r1 = r1 + v * v; }
+                P.ls[0][k] = r0;
+                P.ls[1][k] = r1;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            acc0 = acc0 + trk_pw_combine(P.ls[0], P.leaf, nl);
+            acc1 = acc1 + trk_pw_combine(P.ls[1], P.leaf, nl);
+        }
+        __syncthreads();                                          // leaf sums (and leaves) are rewritten by the next block
+    }
+    s = acc0;
+    sq = acc1;
+}
+
+template <typename T> __device__ inline unsigned long long trk_sq(T v) {
+    return (unsigned long long)(T)(v * v);                        // wraps in the input dtype like numpy's ** 2
 }
 
 __device__ inline void trk_hu(const double (&eta)[4][4], double *lh) {
@@ -336,6 +449,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void trk_features_kernel(const T *__restrict__ im, TrkFrame F) {
     extern __shared__ float tile[];                              // R * R floats
     __shared__ double lds[4 * 16];
+    __shared__ TrkPwLds pw;
     const int k = blockIdx.x;
     const int r = F.rad[k];
     const int c[3] = {F.coord[3 * k], F.coord[3 * k + 1], F.coord[3 * k + 2]};
@@ -347,13 +461,10 @@ __global__ __launch_bounds__(256) void trk_features_kernel(const T *__restrict__
         hi[a] = min(c[a] + r + 1, dims[a]);
     }
     const int ez = hi[0] - lo[0], ey = hi[1] - lo[1], ex = hi[2] - lo[2];
-    typedef typename TrkAcc<T>::S S;
     auto at = [&](int z, int y, int x) -> i64 { return ((i64)(lo[0] + z) * F.ny + (lo[1] + y)) * F.nx + (lo[2] + x); };
 
-    // stats + Z projection (or the 2-D ROI itself): lane owns a (y, x) column
-    S si = 0, sqi = 0;
-    double sf = 0, sqf = 0;
-    unsigned long long ci = 0, cf = 0;
+    // integer stats, non-zero counts and the Z projection (or the 2-D ROI itself): lane owns a (y, x) column
+    unsigned long long si = 0, sqi = 0, ci = 0, cf = 0;
     const bool padz = ez < F.R;
     for (int i = threadIdx.x; i < F.R * F.R; i += blockDim.x) {
         const int y = i / F.R, x = i % F.R;
@@ -363,9 +474,11 @@ __global__ __launch_bounds__(256) void trk_features_kernel(const T *__restrict__
             for (int z = 0; z < ez; ++z) {
                 const i64 o = at(z, y, x);
                 const T v = im[o];
-                if (v != (T)0) { ++ci; si += (S)v; sqi += trk_sq<T>(v); }
-                const float f = F.fr[o];
-                if (f != 0.0f) { ++cf; sf += (double)f; sqf += (double)(f * f); }
+                if (v != (T)0) {
+                    ++ci;
+                    if constexpr (!std::is_same<T, float>::value) { si += (unsigned long long)v; sqi += trk_sq<T>(v); }
+                }
+                if (F.fr[o] != 0.0f) ++cf;
                 mx = fmaxf(mx, (float)v);
             }
             pm = (padz && !F.two_d) ? fmaxf(mx, 0.0f) : mx;       // the dense path's zero padding joins the maximum
@@ -373,12 +486,29 @@ __global__ __launch_bounds__(256) void trk_features_kernel(const T *__restrict__
         tile[i] = pm;
     }
     {
-        S v[3] = {si, sqi, (S)ci};
-        trk_block_sum<S, 3>(v, (S *)lds);
-        if (threadIdx.x == 0) trk_stats_store<T>((unsigned long long)v[2], v[0], v[1], F.stats + 4 * (i64)k);
-        double u[3] = {sf, sqf, (double)cf};
-        trk_block_sum<double, 3>(u, lds);
-        if (threadIdx.x == 0) trk_stats_store<float>((unsigned long long)u[2], u[0], u[1], F.stats + 4 * (i64)k + 2);
+        unsigned long long v[4] = {si, sqi, ci, cf};
+        trk_block_sum<unsigned long long, 4>(v, (unsigned long long *)lds);
+        ci = v[2];
+        cf = v[3];
+        if (threadIdx.x == 0 && !std::is_same<T, float>::value) trk_stats_store_int(ci, v[0], v[1], F.stats + 4 * (i64)k);
+    }
+    // float32 stats: numpy's float32 sums over the ROI zero-padded to R^d and flattened (e = (z * R + y) * R + x)
+    {
+        const int R = F.R;
+        const i64 nroi = F.two_d ? (i64)R * R : (i64)R * R * R;
+        auto roi = [&](const auto *src, i64 e) -> float {
+            const int z = (int)(e / ((i64)R * R)), yx = (int)(e - (i64)z * R * R), y = yx / R, x = yx - y * R;
+            if (z >= ez || y >= ey || x >= ex) return 0.0f;
+            const float v = (float)src[at(z, y, x)];
+            return v != 0.0f ? v : 0.0f;
+        };
+        float s, sq;
+        if constexpr (std::is_same<T, float>::value) {
+            trk_np_sums_roi(nroi, [&](i64 e) { return roi(im, e); }, pw, s, sq);
+            if (threadIdx.x == 0) trk_stats_store_f32(ci, s, sq, F.stats + 4 * (i64)k);
+        }
+        trk_np_sums_roi(nroi, [&](i64 e) { return roi(F.fr, e); }, pw, s, sq);
+        if (threadIdx.x == 0) trk_stats_store_f32(cf, s, sq, F.stats + 4 * (i64)k + 2);
     }
     __syncthreads();
     const int nh = F.two_d ? 6 : 18;

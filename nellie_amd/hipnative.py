@@ -148,6 +148,7 @@ _PROTOS = {
     "nl_track_match": [_p, _int, _f64, _p, _p, _p, _p, _p],
     "nl_host_half_round": [_p, _p, _i64],
     "nl_host_half_nansum": [_p, _i64, _int, _p],
+    "nl_host_np_sum_f32": [_p, _i64, _p],
 }
 # functions without the (err, errlen) tail
 _PLAIN = {
@@ -332,6 +333,14 @@ def host_half_nansum(h):
     out = np.empty(h.shape[:-1], np.float16)
     load().call("nl_host_half_nansum", _ptr(h), int(np.prod(h.shape[:-1])), int(h.shape[-1]), _ptr(out))
     return out
+
+
+def host_np_sum_f32(a):
+    """np.sum of a flat float32 array in numpy's order, as the tracking feature kernel sums the float stats"""
+    a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+    out = np.zeros(1, np.float32)
+    load().call("nl_host_np_sum_f32", _ptr(a), a.size, _ptr(out))
+    return out[0]
 
 
 def comm_unique_id(loopback: bool = False) -> bytes:

@@ -32,14 +32,25 @@ CASES = {
     "tracking_2d_u16_dense": ((60, 64), 3, np.uint16, (0.1, 0.1), 0.5, "dense", int(1e7), (40, 45, 40), {"faces": True}),
     "tracking_2d_f32_sparse": ((56, 60), 4, np.float32, (0.12, 0.1), 1.0, "sparse", int(1e7), (40, 0, 38, 42), {}),
     "tracking_2d_u8_auto_sparse": ((50, 52), 3, np.uint8, (0.1, 0.1), 1.0, "auto", 500, (0, 40, 44), {}),
+    # float32 intensities of 1000 +- 10 (a camera offset: the variance's sumsq - s^2/c cancels), distances up to 5 (R = 21)
+    "tracking_3d_f32_lowcontrast": ((10, 22, 24), 3, np.float32, (0.1, 0.1, 0.1), 1.0, "dense", int(1e7), (30, 28, 32),
+                                    {"lowcontrast": True, "dist_hi": 26}),
+    # distances up to 15 (R = 61) on a frame thinner than R in z: every ROI is clipped and its padding joins the projections
+    "tracking_3d_u16_bigroi": ((9, 28, 30), 3, np.uint16, (0.2, 0.1, 0.1), 1.0, "dense", int(1e7), (8, 7, 8),
+                               {"faces": True, "dist_hi": 226}),
+    # one marker per frame at distance 30.9 (radius 62, R = 125, the feature kernel's largest tile), the rest small
+    "tracking_2d_f32_bigroi_sparse": ((60, 64), 3, np.float32, (0.1, 0.1), 1.0, "sparse", int(1e7), (30, 32, 28),
+                                      {"big": 30.9}),
 }
 
 
-def make_stack(shape, T, dtype, n_markers, seed, bright=False, faces=False):
+def make_stack(shape, T, dtype, n_markers, seed, bright=False, faces=False, lowcontrast=False, dist_hi=10, big=None):
     rng = np.random.default_rng(seed)
     ints, frs, dists, marks = [], [], [], []
     for t in range(T):
-        if dtype == np.float32:
+        if dtype == np.float32 and lowcontrast:
+            im = rng.uniform(990.0, 1010.0, shape).astype(np.float32)
+        elif dtype == np.float32:
             im = (rng.gamma(2.0, 300.0, shape) - 150.0).astype(np.float32)          # textured, some negatives
         elif dtype == np.uint8:
             im = rng.integers(0, 256, shape).astype(np.uint8)
@@ -48,7 +59,7 @@ def make_stack(shape, T, dtype, n_markers, seed, bright=False, faces=False):
             im = rng.integers(lo, 65536 if bright else 5000, shape).astype(np.uint16)
         im[rng.random(shape) < 0.15] = 0
         fr = (rng.gamma(1.5, 2.0, shape) * (rng.random(shape) < 0.7)).astype(np.float32)
-        dist = np.sqrt(rng.integers(0, 10, shape)).astype(np.float32)
+        dist = np.sqrt(rng.integers(0, dist_hi, shape)).astype(np.float32)
         mk = np.zeros(shape, np.uint8)
         n = n_markers[t]
         if n:
@@ -60,6 +71,11 @@ def make_stack(shape, T, dtype, n_markers, seed, bright=False, faces=False):
                         p = [int(rng.integers(0, s)) for s in shape]
                         p[ax] = end
                         mk[tuple(p)] = 1
+            if big is not None:                              # one marker with a large radius, away from the others
+                p = tuple(int(rng.integers(1, s - 1)) for s in shape)
+                mk[tuple(slice(c - 1, c + 2) for c in p)] = 0
+                mk[p] = 1
+                dist[p] = big
         ints.append(im); frs.append(fr); dists.append(dist); marks.append(mk)
     return np.stack(ints), np.stack(frs), np.stack(dists), np.stack(marks)
 
@@ -105,6 +121,18 @@ def tight(feats, maxd):
     return False
 
 
+def dense_roi_path(stack, max_voxels=int(5e7)):
+    """the reference's dense ROI path (the one this port follows) holds N * R^d <= max_dense_roi_voxels_cpu in every frame"""
+    intensity, _, distance, marker = stack
+    for t in range(intensity.shape[0]):
+        m = marker[t] > 0
+        if m.any():
+            R = int(np.ceil((rs._max3(distance[t]) * np.float32(2))[m].max())) * 2 + 1
+            if int(m.sum()) * R ** marker[t].ndim > max_voxels:
+                return False
+    return True
+
+
 def main():
     make_golden.REF = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else make_golden.REF
     make_golden._import_reference()
@@ -113,6 +141,7 @@ def main():
         seed = 0
         while True:
             stack = make_stack(shape, T, dtype, nmk, seed, **extra)
+            assert dense_roi_path(stack), name
             feats, flow, maxd = reference_run(HuMomentTracking, stack, spacing, dt, mode, mdp)
             if not tight(feats, maxd):
                 break

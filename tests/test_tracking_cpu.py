@@ -47,9 +47,7 @@ def test_restatement_reproduces_golden(path):
         c, p, s, h = rs.frame_features(z["intensity"][t], z["frangi"][t], z["distance"][t], z["marker"][t], z["spacing"])
         rc, rst, rh = ref[t]
         assert np.array_equal(c, rc), "coordinates / marker order"
-        if z["intensity"].dtype.kind in "ui":
-            assert np.array_equal(s[:, :2], rst[:, :2]), "integer intensity stats are exact"
-        assert np.allclose(s, rst, rtol=1e-5, atol=0), "float stats"
+        assert np.array_equal(s, rst), "stats (integer, float32 intensity and Frangi) are exact"
         assert hu_close(h, rh), "log-Hu"
         feats.append((c, p, s, h))
     frames = [(z["intensity"][t],) for t in range(T)]
@@ -146,3 +144,32 @@ def test_run_tracking_without_markers_files_raises(tmp_path):
     from nellie_amd.run import run
     with pytest.raises(FileNotFoundError, match="im_marker"):
         run(_im_info(tmp_path), tracking=True)
+
+
+def _np_sum_lengths():
+    ns = list(range(1, 301)) + [8191, 8192, 8193, 16384, 16385]
+    for R in (13, 21, 41, 63, 125):
+        ns += [R * R, R * R * R]
+    return ns
+
+
+@pytest.mark.parametrize("data", ["offset", "zero_runs", "gamma"])
+def test_host_np_sum_matches_numpy(lib, data):
+    """the order of the feature kernel's float stats (nl_host_np_sum_f32) equals np.sum of float32 bit for bit, for the value
+    and for the float32 square, at every length up to 300, around the 8192-item blocks and at R^2 / R^3 of real ROI tiles"""
+    from nellie_amd import hipnative
+    rng = np.random.default_rng({"offset": 1, "zero_runs": 2, "gamma": 3}[data])
+    for n in _np_sum_lengths():
+        if data == "offset":                                        # camera offset: the variance's sumsq - s^2/c cancels
+            a = (1000.0 + 10.0 * rng.standard_normal(n)).astype(np.float32)
+            a[rng.random(n) < 0.2] = 0
+        elif data == "zero_runs":                                   # a zero-padded ROI: runs of data between runs of zeros
+            a = np.zeros(n, np.float32)
+            step = int(rng.integers(3, 40))
+            for s in range(0, n, 2 * step):
+                a[s:s + step] = rng.uniform(0.5, 3.0, len(a[s:s + step])).astype(np.float32) * 10.0 ** rng.integers(-3, 4)
+        else:
+            a = (rng.gamma(2.0, 300.0, n) - 100.0).astype(np.float32)
+        for x in (a, a * a):
+            got, want = hipnative.host_np_sum_f32(x), np.sum(x)
+            assert got.view(np.uint32) == want.view(np.uint32), (n, got, want)
