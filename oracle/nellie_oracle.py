@@ -176,13 +176,14 @@ def correlate1d_reflect_f32(a: np.ndarray, w: np.ndarray, axis: int) -> np.ndarr
     assert a.dtype == np.float32
     r = (len(w) - 1) // 2
     n = a.shape[axis]
-    a64 = np.moveaxis(a, axis, 0).astype(np.float64)
-    idx = np.arange(n)
-    tmp = a64 * w[r]
+    # the reflected line gathered once; every tap is then a view of it (same values, same operations as a gather per tap)
+    pad = np.moveaxis(a, axis, 0).astype(np.float64, order="C")[_reflect_index(np.arange(-r, n + r), n)]
+    tmp = pad[r:r + n] * w[r]
+    s = np.empty_like(tmp)
     for j in range(-r, 0):
-        lo = a64[_reflect_index(idx + j, n)]
-        hi = a64[_reflect_index(idx - j, n)]
-        tmp = tmp + (lo + hi) * w[r + j]
+        np.add(pad[r + j:r + j + n], pad[r - j:r - j + n], out=s)
+        s *= w[r + j]
+        tmp += s
     return np.ascontiguousarray(np.moveaxis(tmp.astype(np.float32), 0, axis))
 
 
@@ -1120,6 +1121,52 @@ def distance_transform_edt_exact(mask):
     return np.sqrt(d2.astype(np.float64))
 
 
+def marker_distance_clamped(mask, max_radius_px):
+    """distance_transform_edt(mask).astype(float32) clamped at 2 * max_radius_px, as `marker_distance_and_border` takes it,
+    with the min-plus passes limited to offsets |k| <= K = floor(2 * max_radius_px) along each axis.  Exact under the clamp:
+    a background voxel outside the (2K + 1)^d window lies at least K + 1 > clamp away, so whatever the limited passes
+    return there (a farther background voxel, or none) clamps to the same value.  O(K) passes instead of O(n)."""
+    m = np.asarray(mask, dtype=bool)
+    clamp = max_radius_px * 2.0
+    K = int(np.floor(clamp))
+    big = np.int64(1) << 40
+    d2 = np.where(m, big, np.int64(0))
+    for axis in range(m.ndim):
+        a = np.ascontiguousarray(np.moveaxis(d2, axis, 0))
+        out = a.copy()
+        n = a.shape[0]
+        for k in range(1, min(K, n - 1) + 1):            # out[i] = min_{|i - j| <= K} a[j] + (i - j)^2
+            kk = np.int64(k * k)
+            np.minimum(out[k:], a[:-k] + kk, out=out[k:])
+            np.minimum(out[:-k], a[k:] + kk, out=out[:-k])
+        d2 = np.moveaxis(out, 0, axis)
+    dist = np.sqrt(d2.astype(np.float64)).astype(np.float32)
+    np.minimum(dist, clamp, out=dist)
+    return dist
+
+
+def markers_crop_margin(dim_res, min_radius_um=0.20, max_radius_um=1, num_sigma=5, peak_min_distance=2):
+    """Planes / rows / columns (z, y, x) of a crop that an artificial face invalidates for `markers_frame`, by the chain
+    of its steps along each axis:
+        ceil(2 * max_r) - 1               the clamped distance: a background voxel k voxels out along the axis is at least
+                                          k away, and changes a value only if k < 2 * max_r (at exactly the clamp the
+                                          clamped value is the same)
+        + int(4 * sigma_axis + 0.5)       the largest LoG radius (truncate 4.0; sigma_z = sigma / z_ratio)
+        + 1                               the 3 x 3 x 3 maximum of the peak test
+        + peak_min_distance               the non-maximum suppression window
+    A face the crop shares with the volume needs no margin (the EDT, the reflect padding and the 'nearest' maxima are then
+    the volume's own).  With use_im='frangi' the distance does not feed the markers; the same margin then holds with room
+    to spare.  2-D images take the last two entries."""
+    sigmas, max_r = marker_sigmas(dim_res, min_radius_um, max_radius_um, num_sigma)
+    zr = z_ratio(dim_res)
+    dist = int(np.ceil(max_r * 2.0)) - 1
+    out = []
+    for a in range(3):
+        log_r = max(gaussian_radius(float(s) / zr if a == 0 else float(s), 4.0) for s in sigmas)
+        out.append(dist + log_r + 1 + int(peak_min_distance))
+    return tuple(out)
+
+
 def marker_distance_and_border(mask, max_radius_px):
     """mocap_marking.py:419-450."""
     if mask.ndim == 3:
@@ -1127,9 +1174,7 @@ def marker_distance_and_border(mask, max_radius_px):
     else:                                           # 2-D: the default structuring element is the 4-connected cross
         p = np.pad(mask, 1, mode="constant", constant_values=False)
         border = (p[1:-1, 1:-1] | p[:-2, 1:-1] | p[2:, 1:-1] | p[1:-1, :-2] | p[1:-1, 2:]) ^ mask
-    dist = distance_transform_edt_exact(mask).astype(np.float32)
-    np.minimum(dist, max_radius_px * 2.0, out=dist)
-    return dist, border
+    return marker_distance_clamped(mask, max_radius_px), border
 
 
 def maximum_filter_nearest(a, size):

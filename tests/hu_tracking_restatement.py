@@ -211,10 +211,13 @@ def match_sparse(phys_post, phys_pre, st_post, st_pre, hu_post, hu_pre, maxd):
         return [], [], []
     st_post, st_pre = np.asarray(st_post, np.float32), np.asarray(st_pre, np.float32)
     hu_post, hu_pre = np.asarray(hu_post, np.float32), np.asarray(hu_pre, np.float32)
-    d2 = ((phys_post[:, None, 0] - phys_pre[None, :, 0]) ** 2 + (phys_post[:, None, 1] - phys_pre[None, :, 1]) ** 2)
-    if phys_post.shape[1] == 3:
-        d2 = d2 + (phys_post[:, None, 2] - phys_pre[None, :, 2]) ** 2
-    cand = [np.nonzero(d2[i] <= maxd * maxd)[0] for i in range(n_post)]      # cKDTree.query_ball_point, sorted
+    cand = []                                                                # cKDTree.query_ball_point, sorted
+    for b0 in range(0, n_post, 256):                                         # row blocks: no N x N matrix at 57 k markers
+        p = phys_post[b0:b0 + 256]
+        d2 = ((p[:, None, 0] - phys_pre[None, :, 0]) ** 2 + (p[:, None, 1] - phys_pre[None, :, 1]) ** 2)
+        if phys_post.shape[1] == 3:
+            d2 = d2 + (p[:, None, 2] - phys_pre[None, :, 2]) ** 2
+        cand += [np.nonzero(row <= maxd * maxd)[0] for row in d2]
     n = 0
     s = np.zeros(2); ss = np.zeros((2, st_post.shape[1])); sh = np.zeros((2, hu_post.shape[1]))
     blocks = []

@@ -361,3 +361,274 @@ def test_c4_volume_partition_invariance(hip):
     with open("gpurun_out/c4_partition_invariance.json", "w") as f:
         json.dump(report, f)
     print(json.dumps(report))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Markers and Hu-moment tracking at the headline size.  The oracle's markers_frame recomputes boxes from the RAW crops
+# (labels, intensities, Frangi); oracle.markers_crop_margin gives the part of a box no artificial face reaches
+# (tests/test_oracle_golden.py pins both).  Host RAM: ~50 GB at the peak of the tracking test.
+# ---------------------------------------------------------------------------------------------------------------
+def marker_oracle_boxes(intensity, labels, frangi, outs, shape, boxes, what):
+    """marker / distance / border of a device run equal the oracle's on the valid interior of every box (boxes in threads:
+    numpy releases the GIL in its loops).  Returns the oracle markers compared."""
+    from concurrent.futures import ThreadPoolExecutor
+    from nellie_amd.synthetic import ISO_01
+    from oracle import nellie_oracle as orc
+    margin = orc.markers_crop_margin(ISO_01)
+
+    def one(box):
+        sl = tuple(slice(a, b) for a, b in box)
+        return orc.markers_frame(intensity[sl], labels[sl], ISO_01, frangi=None if frangi is None else frangi[sl])
+
+    with ThreadPoolExecutor(max_workers=min(8, len(boxes))) as ex:
+        refs = list(ex.map(one, boxes))
+    n = 0
+    for box, ref in zip(boxes, refs):
+        sl = tuple(slice(a, b) for a, b in box)
+        valid = crop_valid_slices(box, shape, margin)
+        for name, got, want in zip(("marker", "distance", "border"), outs, ref):
+            g, w = got[sl][valid], want[valid]
+            assert np.array_equal(g, w), f"{what} box {box}: {name} differs at {int((g != w).sum())} voxels, first {np.argwhere(g != w)[:4].tolist()}"
+        n += int(ref[0][valid].sum())
+    return n
+
+
+def check_marker_volume(labels, n, outs, clamp=20.0):
+    """Whole-volume invariants: border = dilation6(mask) ^ mask; distance 0 off the mask, in [1, clamp] on it and the float32
+    root of an integer below the clamp; markers only on mask & distance > 0; the count returned equals marker.sum()."""
+    from oracle import nellie_oracle as orc
+    marker, dist, border = outs
+    assert marker.dtype == np.uint8 and dist.dtype == np.float32 and border.dtype == np.uint8
+    nz = labels.shape[0]
+    for z0 in range(0, nz, 64):                     # plane blocks (plus one plane each side for the dilation)
+        z1 = min(nz, z0 + 64)
+        e0, e1 = max(0, z0 - 1), min(nz, z1 + 1)
+        m = labels[e0:e1] > 0
+        want = (orc.binary_dilation6(m) ^ m)[z0 - e0:z0 - e0 + (z1 - z0)]
+        m = m[z0 - e0:z0 - e0 + (z1 - z0)]
+        assert np.array_equal(border[z0:z1] > 0, want) and border[z0:z1].max(initial=0) <= 1, f"border, planes [{z0}, {z1})"
+        d = dist[z0:z1]
+        assert not d[~m].any(), f"distance off the mask, planes [{z0}, {z1})"
+        dm = d[m]
+        assert dm.size == 0 or (dm.min() >= 1.0 and dm.max() <= np.float32(clamp)), f"distance range, planes [{z0}, {z1})"
+        below = dm[dm < np.float32(clamp)].astype(np.float64)
+        assert np.array_equal(np.sqrt(np.round(below * below)).astype(np.float32), below.astype(np.float32)), "d^2 not integral"
+        mk = marker[z0:z1] > 0
+        assert not (mk & ~(m & (d > 0))).any() and marker[z0:z1].max(initial=0) <= 1, f"markers off the mask, planes [{z0}, {z1})"
+    assert int(np.count_nonzero(marker)) == n
+
+
+def densest_box(labels, shape, starts, size, margin):
+    """the box (from candidate starts) whose valid interior holds the most mask voxels"""
+    best, arg = -1, None
+    for s in starts:
+        box = tuple((a, a + size) for a in s)
+        sl = tuple(slice(a, b) for a, b in box)
+        valid = crop_valid_slices(box, shape, margin)
+        c = int(np.count_nonzero(labels[sl][valid]))
+        if c > best:
+            best, arg = c, box
+    return arg
+
+
+def run_markers_resident(vol, n_labels, env):
+    """Filter -> Label -> Markers on one FramePipeline, nothing leaving the device in between (use_im='distance', the float32
+    input read in place)."""
+    from nellie_amd import pipeline as pl
+    from nellie_amd.synthetic import ISO_01
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    pipe = pl.FramePipeline(SHAPE)
+    try:
+        pipe.load_input(vol)                            # resident: Filter starts from it, Markers reads its intensities there
+        pipe.filter(None, pl.FilterParams(dim_res=ISO_01))
+        assert pipe.label(pipe.frangi_threshold(), pl.min_area_pixels_of(ISO_01)) == n_labels
+        n = pipe.markers(ISO_01)
+        return n, tuple(a.reshape(SHAPE) for a in pipe.download_markers())
+    finally:
+        pipe.close()
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+@pytest.fixture(scope="module")
+def markers_run(full_run):
+    n, outs = run_markers_resident(full_run["vol"], full_run["n"], {"NELLIE_MK_SPARSE": "1", "NELLIE_MK_POISON": "0"})
+    return dict(n=n, marker=outs[0], distance=outs[1], border=outs[2])
+
+
+def test_markers_resident_chain_at_1024_cube(full_run, markers_run):
+    """Markers at the headline size (mk_edt_x_kernel and mk_nms_kernel take 8 trips of their capped grids, mk_tile_mark_kernel
+    4, the sparse LoG 16 Z chunks): whole-volume invariants, the oracle on a corner box, an X-face box and the densest interior
+    box, and the sparse LoG bit-identical to its NaN-poisoned form and to the dense LoG."""
+    from nellie_amd.synthetic import ISO_01
+    from oracle import nellie_oracle as orc
+    outs = (markers_run["marker"], markers_run["distance"], markers_run["border"])
+    lab = full_run["labels"]
+    check_marker_volume(lab, markers_run["n"], outs)
+    margin = orc.markers_crop_margin(ISO_01)
+    L, nx = 256, SHAPE[2]
+    mid = (128, 384, 640)
+    boxes = [((0, L), (0, L), (0, L)),
+             densest_box(lab, SHAPE, [(z, y, nx - L) for z in mid for y in mid], L, margin),
+             densest_box(lab, SHAPE, [(z, y, x) for z in mid for y in mid for x in mid], L, margin)]
+    n_cmp = marker_oracle_boxes(full_run["vol"], lab, None, outs, SHAPE, boxes, "1024^3")
+    print(f"1024^3 Markers: {markers_run['n']} markers, {n_cmp} compared with the oracle in boxes {boxes}")
+    assert n_cmp >= 1000
+    for env in ({"NELLIE_MK_SPARSE": "1", "NELLIE_MK_POISON": "1"}, {"NELLIE_MK_SPARSE": "0", "NELLIE_MK_POISON": "0"}):
+        n2, outs2 = run_markers_resident(full_run["vol"], full_run["n"], env)
+        assert n2 == markers_run["n"], env
+        for name, a, b in zip(("marker", "distance", "border"), outs2, outs):
+            assert np.array_equal(a, b), f"{env}: {name} differs at {int((a != b).sum())} voxels"
+        del outs2
+
+
+def test_markers_odd_frame_above_2_30_voxels(full_run):
+    """Markers from host inputs on a 1030 x 1090 x 1100 frame (1.235e9 voxels: 18-word rows with a partial last word, ny no
+    multiple of the 16-row tile or the 4-row peak group, a second trip of mk_tile_list_kernel), uint16 intensities and
+    use_im='frangi', with thick solids planted in the labels whose interiors reach the distance clamp: a ball of radius 45, a
+    60 x 200 x 200 block across the Z chunk seam at z = 128, slabs on the x = nx - 1 and z = 0 faces."""
+    from nellie_amd import pipeline as pl
+    from nellie_amd.synthetic import ISO_01
+    pad = ((3, 3), (33, 33), (38, 38))
+    lab = np.pad(full_run["labels"], pad, mode="reflect")
+    shape = lab.shape
+    assert shape == (1030, 1090, 1100) and lab.size > 2 ** 30
+    nz, ny, nx = shape
+    zz, yy, xx = np.ogrid[:nz, :ny, :nx]
+    k = int(lab.max()) + 1
+    ball = (500, 300, 700)
+    lab[455:546, 255:346, 655:746][((zz[455:546] - ball[0]) ** 2 + (yy[:, 255:346] - ball[1]) ** 2
+                                    + (xx[:, :, 655:746] - ball[2]) ** 2) <= 45 * 45] = k
+    lab[100:160, 600:800, 150:350] = k + 1
+    lab[700:760, 100:220, nx - 50:] = k + 2
+    lab[:50, 850:970, 850:970] = k + 3
+    vol = np.clip(np.rint(np.pad(full_run["vol"], pad, mode="reflect")), 0, 65535).astype(np.uint16)
+    fr = np.pad(full_run["frangi"], pad, mode="reflect")
+    pipe = pl.FramePipeline(shape)
+    try:
+        n = pipe.markers(ISO_01, labels=lab, intensity=vol, use_image=fr)
+        outs = tuple(a.reshape(shape) for a in pipe.download_markers())
+    finally:
+        pipe.close()
+    check_marker_volume(lab, n, outs)
+    dist = outs[1]
+    for name, sl in (("ball", ball), ("block", (130, 700, 250)), ("x-face slab", (730, 160, nx - 21)), ("z-face slab", (20, 910, 910))):
+        assert dist[sl] == np.float32(20.0), f"{name}: distance {dist[sl]} at {sl} does not reach the clamp"
+    boxes = [((nz - 256, nz), (ny - 256, ny), (nx - 256, nx)),          # the far corner
+             ((418, 582), (218, 382), (618, 782)),                     # the ball
+             ((65, 195), (565, 835), (115, 385)),                      # the block
+             ((665, 795), (65, 255), (nx - 85, nx)),                   # the slab on the x = nx - 1 face
+             ((0, 85), (815, 1005), (815, 1005))]                      # the slab on the z = 0 face
+    n_cmp = marker_oracle_boxes(vol, lab, fr, outs, shape, boxes, "1030x1090x1100")
+    print(f"1030x1090x1100 Markers: {n} markers, {n_cmp} compared with the oracle")
+    assert n_cmp >= 1000
+
+
+def test_markers_as_two_z_slabs_at_1024_cube(full_run, markers_run, monkeypatch):
+    """The Markers stage class with the frame cut into two Z slabs (each with its halo) writes the single-context products."""
+    from fakes import ArrayImInfo
+    from nellie_amd.segmentation.mocap_marking import Markers
+    from nellie_amd.synthetic import ISO_01
+    monkeypatch.setenv("NELLIE_FORCE_SLABS", "2")
+    im = ArrayImInfo(full_run["vol"][None], ISO_01)
+    im.store["labels"] = full_run["labels"][None].view(type(im.store["im"]))
+    mk = Markers(im, device="gpu")
+    mk.run()
+    assert mk._slab_plan(SHAPE)[0] >= 2
+    for key in ("marker", "distance", "border"):
+        a, b = np.asarray(im.store[key])[0], markers_run[key]
+        assert a.dtype == b.dtype and np.array_equal(a, b), f"{key}: {int((a != b).sum())} voxels differ"
+
+
+def _radii_at(distance, coords):
+    """ceil(2 * (3 x 3 x 3 maximum of the distance, faces clamped)) at the markers: the ROI radius of the tracker"""
+    m = np.zeros(len(coords), np.float32)
+    for off in np.ndindex(3, 3, 3):
+        c = np.clip(coords + np.array(off) - 1, 0, np.array(distance.shape) - 1)
+        m = np.maximum(m, distance[tuple(c.T)])
+    return np.ceil(m * np.float32(2)).astype(np.int64)
+
+
+def test_tracking_at_1024_cube(full_run, markers_run, tmp_path):
+    """HuMomentTracking at the headline size: frame 0 is the 1024^3 intensity, Frangi and Markers products plus markers at
+    linear index 0 and 2^30 - 1 and on both sides of 4096-voxel chunk and scan-segment edges; frame 1 is frame 0 rolled by
+    (1, 2, -1).  (Frangi voxels where the host's float32 log10 is not the correctly rounded one are zeroed.)  Coordinates equal argwhere; features of a sample (3000 seeded markers, the planted ones, every marker whose ROI a
+    face clips, the largest ROI) equal the restatement; sparse matching equals the restatement; every frame-1 marker whose
+    ROI clears the rolled faces and with no other marker nearer than the shift takes its own pre-roll copy.  Host RAM ~50 GB."""
+    import hu_tracking_restatement as rs
+    from test_hip_tracking import assert_features, bad_rows, run_stage
+    from nellie_amd import hipnative
+    spacing, shift = (0.1, 0.1, 0.1), (1, 2, -1)
+    n = int(np.prod(SHAPE))
+    marker = markers_run["marker"].copy()
+    nblk = n // 4096
+    seg = (nblk + 1023) // 1024
+    planted = {0, n - 1}
+    for kk in (1, 2, nblk // 2, nblk - 1):
+        planted |= {kk * 4096 - 1, kk * 4096}
+    for t in (1, 2, 511, 512, 1023):
+        planted |= {t * seg * 4096 - 1, t * seg * 4096}
+    planted = np.array(sorted(planted))
+    marker.flat[planted] = 1
+    # Frangi voxels whose float32 log10 is not the float64 one rounded are zeroed (as test_hip_tracking.exact_log_frangi does):
+    # numpy's float32 log10 depends on the host, the device's is the correctly rounded one
+    fr = full_run["frangi"].copy()
+    for z0 in range(0, SHAPE[0], 64):
+        blk = fr[z0:z0 + 64]
+        with np.errstate(divide="ignore"):
+            blk[(blk > 0) & (np.log10(blk) != np.log10(blk.astype(np.float64)).astype(np.float32))] = 0
+    f0 = (full_run["vol"], fr, markers_run["distance"], marker)
+    f1 = tuple(np.roll(a, shift, axis=(0, 1, 2)) for a in f0)
+    feats = []
+    with hipnative.Tracker(SHAPE, spacing) as trk:
+        trk.frame(*f0)
+        c0, s0, h0 = trk.features(0)
+        trk.frame(*f1)
+        c1, s1, h1 = trk.features(0)
+        ri, rc, ci, cc = trk.match("sparse", 1.0)
+    feats = [(c0, c0 * np.asarray(spacing), s0, h0), (c1, c1 * np.asarray(spacing), s1, h1)]
+    shp = np.array(SHAPE)
+    rng = np.random.default_rng(77)
+    for t, (fr, (c, _, s, h)) in enumerate(zip((f0, f1), feats)):
+        assert np.array_equal(c, np.argwhere(fr[3]))
+        r = _radii_at(fr[2], c)
+        pick = np.zeros(len(c), bool)
+        pick[rng.choice(len(c), 3000, replace=False)] = True
+        pick |= np.isin(np.ravel_multi_index(tuple(c.T), SHAPE), np.ravel_multi_index(tuple(np.unravel_index(planted, SHAPE)), SHAPE)
+                        if t == 0 else np.ravel_multi_index(tuple(((np.array(np.unravel_index(planted, SHAPE)).T + shift) % shp).T), SHAPE))
+        pick |= ((c - r[:, None]) < 0).any(axis=1) | ((c + r[:, None]) >= shp).any(axis=1)
+        pick[int(np.argmax(r))] = True                   # the largest ROI sets the zero-padded R^3 of the float sums
+        sample = np.zeros(SHAPE, np.uint8)
+        sample[tuple(c[pick].T)] = 1
+        want = rs.frame_features(fr[0], fr[1], fr[2], sample, spacing)
+        assert_features((c[pick], s[pick], h[pick]), want)
+        print(f"tracking 1024^3 frame {t}: {len(c)} markers, {int(pick.sum())} compared with the restatement")
+        del sample
+    stack = tuple(np.stack([a, b]) for a, b in zip(f0, f1))
+    flow = run_stage(tmp_path, stack, spacing, 1.0, "sparse")
+    want = rs.track([(stack[0][t],) for t in range(2)], spacing, mode="sparse", features=feats)
+    bad = bad_rows(flow, want)
+    n_markers = len(c0) + len(c1)
+    print(f"tracking 1024^3 sparse: {n_markers} markers, {len(want)} rows, {bad} differing")
+    assert len(want) > 0 and bad <= max(2, 2 * n_markers // 10000), bad
+    del stack
+    # known answer: the pre-roll copy wins every row whose ROI clears the rolled faces and with no rival nearer than the shift
+    pre = c1 - np.array(shift)
+    r1 = _radii_at(f1[2], c1)
+    ok = ((pre - r1[:, None] - 1) >= 0).all(axis=1) & ((pre + r1[:, None] + 1) < shp).all(axis=1)
+    ok &= ((c1 - r1[:, None] - 1) >= 0).all(axis=1) & ((c1 + r1[:, None] + 1) < shp).all(axis=1)
+    d_shift = float(np.dot(shift, shift))
+    for off in np.ndindex(5, 5, 5):
+        o = np.array(off) - 2
+        if float(np.dot(o, o)) <= d_shift and tuple(o) != tuple(shift):
+            q = np.clip(c1 - o, 0, shp - 1)
+            ok &= ~((marker[tuple(q.T)] > 0) & ((c1 - o) == q).all(axis=1))
+    own = np.searchsorted(np.ravel_multi_index(tuple(c0.T), SHAPE), np.ravel_multi_index(tuple(np.where(ok[:, None], pre, 0).T), SHAPE))
+    hit = ok & (ri == own)
+    print(f"tracking 1024^3 known answer: {int(hit.sum())} of {int(ok.sum())} eligible rows ({len(c1)} markers) take their own copy")
+    assert int(ok.sum()) >= len(c1) // 2 and int(hit.sum()) == int(ok.sum())
+    assert np.array_equal(s1[ok], s0[own[ok]]) and np.array_equal(h1[ok], h0[own[ok]])

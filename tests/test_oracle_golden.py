@@ -216,3 +216,131 @@ def test_crop_mode_reproduces_the_reference_on_crop_interiors(name, boxes):
         valid = crop_valid_slices(box, vol.shape, (3, 3, 3))
         raw = orc.filter_frame_crop(vol[sl], dr, given, None, sigmas=sigmas, **kw)
         assert not np.array_equal(raw[valid], g["run_frame"][sl][valid])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Markers at sizes the O(n^2) exact EDT cannot reach: the reach-limited clamped EDT and the crop margin of markers_frame
+# ---------------------------------------------------------------------------------------------------------------
+def _edt_masks():
+    rng = np.random.default_rng(71)
+    out = []
+    for shape in ((23, 37, 41), (61, 58)):
+        out.append(rng.random(shape) < 0.93)                                   # random background specks
+        m = np.ones(shape, bool)                                               # a thick solid: interior far beyond the clamp
+        m[(slice(0, 2),) + (slice(None),) * (len(shape) - 1)] = False
+        m[(slice(None),) * (len(shape) - 1) + (slice(-1, None),)] = False
+        out.append(m)
+        m = np.zeros(shape, bool)                                              # touching every face, background inside only
+        m[tuple(slice(None) for _ in shape)] = True
+        m[tuple(slice(s // 2, s // 2 + 2) for s in shape)] = False
+        out.append(m)
+    return out
+
+
+@pytest.mark.parametrize("max_r", [10.0, 3.3, 2.5, 1.0])
+def test_marker_distance_clamped_is_the_exact_edt_clamped(max_r):
+    """The limited min-plus passes (offsets |k| <= floor(2 max_r)) equal the O(n^2) exact transform, clamped, bit for bit."""
+    for m in _edt_masks():
+        want = orc.distance_transform_edt_exact(m).astype(np.float32)
+        np.minimum(want, max_r * 2.0, out=want)
+        got = orc.marker_distance_clamped(m, max_r)
+        assert got.dtype == np.float32 and np.array_equal(got, want), (m.shape, max_r)
+        assert not m.all() and (want[m] > 0).all() and (want[~m] == 0).all()
+
+
+@pytest.mark.parametrize("max_r", [10.0, 3.3])
+def test_marker_distance_clamped_matches_scipy(max_r):
+    ndi = pytest.importorskip("scipy.ndimage")
+    for m in _edt_masks():
+        want = ndi.distance_transform_edt(m).astype(np.float32)
+        np.minimum(want, max_r * 2.0, out=want)
+        assert np.array_equal(orc.marker_distance_clamped(m, max_r), want)
+
+
+def test_markers_crop_margin_figures():
+    """The chain at 0.1 um: 19 (distance: a background voxel 20 out leaves the value at the clamp of 20) + 11 (LoG radius of
+    sigma 2.87) + 1 (peak maximum) + 2 (NMS window); Z at 0.3 um takes the LoG radius of sigma / 3 (4)."""
+    iso = {"X": 0.1, "Y": 0.1, "Z": 0.1, "T": 1.0}
+    assert orc.markers_crop_margin(iso) == (33, 33, 33)
+    assert orc.markers_crop_margin({"X": 0.1, "Y": 0.1, "Z": 0.3, "T": 1.0}) == (26, 33, 33)
+    assert orc.markers_crop_margin(iso, peak_min_distance=3) == (34, 34, 34)
+    assert orc.markers_crop_margin({"X": 0.3, "Y": 0.3, "Z": 0.3, "T": 1.0})[2] == 6 + 4 + 1 + 2      # clamp 6.67: 6 out matters
+
+
+def _marker_solids(shape, seed, n, rmin, rmax):
+    """labels of random balls (radii up to rmax: interiors past the distance clamp) and a float32 intensity"""
+    rng = np.random.default_rng(seed)
+    lab = np.zeros(shape, np.int32)
+    grid = np.ogrid[tuple(slice(0, s) for s in shape)]
+    for k in range(n):
+        c = [int(rng.integers(0, s)) for s in shape]
+        r = rng.uniform(rmin, rmax)
+        lab[sum((g - ci) ** 2 for g, ci in zip(grid, c)) <= r * r] = k + 1
+    return rng.normal(100, 5, shape).astype(np.float32), lab
+
+
+def _check_marker_crops(vol, lab, dr, boxes, frangi=None, margin=None):
+    full = orc.markers_frame(vol, lab, dr, frangi=frangi)
+    margin = margin or orc.markers_crop_margin(dr)[-vol.ndim:]
+    n = 0
+    for box in boxes:
+        sl = tuple(slice(a, b) for a, b in box)
+        valid = crop_valid_slices(box, vol.shape, margin)
+        assert all(v.stop > v.start for v in valid), (box, margin)
+        got = orc.markers_frame(vol[sl], lab[sl], dr, frangi=None if frangi is None else frangi[sl])
+        for name, a, b in zip(("marker", "distance", "border"), got, full):
+            assert np.array_equal(a[valid], b[sl][valid]), f"{name} differs in box {box}"
+        n += int(full[0][sl][valid].sum())
+    return full, n
+
+
+@pytest.mark.parametrize("case", ["iso", "aniso_z0.3", "frangi"])
+def test_markers_crop_mode_reproduces_the_whole_frame(case):
+    """markers_frame of a crop equals the whole-frame result on the crop's valid interior (markers_crop_margin in from every
+    face that is not the volume's) for marker, distance and border.  What licenses the box checks of Markers at 1024^3."""
+    from nellie_amd.synthetic import ANISO_03, ISO_01, make_volume
+    dr = ANISO_03 if case == "aniso_z0.3" else ISO_01
+    shape = (40, 100, 110) if case == "aniso_z0.3" else (70, 100, 110)
+    vol, lab = _marker_solids(shape, {"iso": 1, "aniso_z0.3": 2, "frangi": 3}[case], 14, 3, 30)
+    frangi = make_volume(shape, 9) if case == "frangi" else None
+    mz, my, mx = orc.markers_crop_margin(dr)
+    boxes = [((0, shape[0]), (0, shape[1]), (0, mx + 30)),                       # one artificial face (X)
+             ((0, shape[0]), (shape[1] - my - 25, shape[1]), (0, shape[2])),      # one artificial face (Y)
+             ((0, mz + 6), (0, my + 30), (shape[2] - mx - 28, shape[2])),        # artificial faces on all three axes
+             ((shape[0] - mz - 5, shape[0]), (20, shape[1]), (5, shape[2] - 4))]
+    full, n = _check_marker_crops(vol, lab, dr, boxes, frangi)
+    assert n >= 20, n
+    assert float(full[1].max()) == 20.0, "no interior reaches the distance clamp"
+
+
+def test_markers_crop_mode_on_a_golden():
+    """The same on a Markers golden (the reference's own outputs): a crop with one artificial face (X) whose valid interior
+    holds markers reproduces the golden there."""
+    g = load_golden("markers2d_iso_130x200_s2")
+    dr = g["dim_res_dict"]
+    box = ((0, 130), (0, 120))
+    margin = orc.markers_crop_margin(dr)[-2:]
+    sl = tuple(slice(a, b) for a, b in box)
+    valid = crop_valid_slices(box, g["input"].shape, margin)
+    got = orc.markers_frame(g["input"][sl], g["labels_in"][sl], dr)
+    for a, key in zip(got, ("marker", "distance", "border")):
+        assert np.array_equal(a[valid], g[key][sl][valid]), key
+    assert int(g["marker"][sl][valid].sum()) >= 10 and float(g["distance"][sl][valid].max()) > 5
+
+
+def test_markers_crop_margin_distance_term_is_needed():
+    """A background face 19 voxels beyond the crop still moves the distance (19 < clamp 20): with that term one smaller the
+    distance differs.  (The whole chain is a bound: the markers' own observed reach on random 1-D profiles is 26 of 33.)"""
+    from nellie_amd.synthetic import ISO_01
+    nx = 120
+    lab = np.ones((6, 6, nx), np.int32)
+    lab[:, :, :2] = 0
+    lab[:, :, 90:] = 0
+    vol = np.random.default_rng(4).normal(100, 5, lab.shape).astype(np.float32)
+    full = orc.markers_frame(vol, lab, ISO_01)
+    x1 = 90                                                                  # the crop ends where the background starts
+    crop = orc.markers_frame(vol[:, :, :x1], lab[:, :, :x1], ISO_01)
+    d = orc.markers_crop_margin(ISO_01)[2] - 11 - 1 - 2                     # the distance term: 19
+    assert d == 19
+    assert np.array_equal(crop[1][:, :, :x1 - d], full[1][:, :, :x1 - d])
+    assert not np.array_equal(crop[1][:, :, :x1 - d + 1], full[1][:, :, :x1 - d + 1])
