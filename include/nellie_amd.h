@@ -556,6 +556,23 @@ int nl_host_half_round(const double *in, uint16_t *out, int64_t n, char *err, si
 int nl_host_half_nansum(const uint16_t *in, int64_t rows, int k, uint16_t *out, char *err, size_t errlen);
 int nl_host_np_sum_f32(const float *in, int64_t n, float *out, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ flow-vector interpolation -------- */
+/* nellie/tracking/flow_interpolation.py on the device.  A flow field has its own stream and buffers.
+   nl_flow_create      : ndim 2 or 3, spacing ((Z,) Y, X in um) and the search radius r in um (max(max_distance_um * dt, 0.5)).
+   nl_flow_load        : the rows of one time point and direction, float64: check coordinates (n, ndim) in voxels (the row's
+                         position, forward; position + vector, backward), vectors (n, ndim) and costs (n).  They replace the
+                         rows loaded before, are binned into a grid of cells of edge r and stay on the device.  n may be 0.
+   nl_flow_interpolate : n query rows (n, ndim) float64 in voxels -> out (n, ndim) float64.  Neighbours of a query are the rows
+                         with sum_axes (q*s - c*s)^2 <= r*r; a row without one (a NaN row included) is NaN.  n_found = the number
+                         of rows that found a neighbour.  Inputs of any length: the library runs them in chunks.
+   nl_flow_kernel_ms   : device time of the kernels of the last nl_flow_interpolate call, transfers excluded. */
+typedef struct nl_flow nl_flow;
+int nl_flow_create(nl_flow **out, int device, int ndim, const double *spacing, double r, char *err, size_t errlen);
+int nl_flow_destroy(nl_flow *field);
+int nl_flow_load(nl_flow *field, const double *coords, const double *vectors, const double *costs, int64_t n, char *err, size_t errlen);
+int nl_flow_interpolate(nl_flow *field, const double *queries, int64_t n, double *out, int64_t *n_found, char *err, size_t errlen);
+int nl_flow_kernel_ms(nl_flow *field, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit
    Hessians h6[n][6] = (hxx,hxy,hxz,hyy,hyz,hzz) writes out4[n][4] = (l1,l2,l3 sorted by |.|, Frangi

@@ -1,0 +1,186 @@
+// Translation unit of libnellie_hip.so (gfx950): flow-vector interpolation (nellie/tracking/flow_interpolation.py).  C-ABI in
+// include/nellie_amd.h; kernels in flow.inc.  A flow field owns its buffers and stream: it needs none of a Filter context's volumes.
+#include "nl_host.h"
+#include "flow.inc"
+
+#define FLOW_CHUNK ((i64)1 << 22)      // query rows per launch: 96 MB in and 96 MB out on the device at D = 3
+
+struct nl_flow {
+    int device = 0, ndim = 3;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    FlowSpacing sp{{1.0, 1.0, 1.0}};
+    double r = 0.5;
+    i64 n_rows = 0, row_cap = 0;
+    double *d_in = nullptr;            // uploaded rows: coords (n, D) | vectors (n, D) | costs (n)
+    int *d_cell = nullptr, *d_perm = nullptr;
+    FlowRow *d_rows = nullptr;
+    FlowGrid *d_grid = nullptr;
+    int *d_start = nullptr, *d_cursor = nullptr;      // FLOW_MAX_CELLS + 1 entries
+    double *d_q = nullptr, *d_out = nullptr; i64 q_cap = 0;
+    unsigned long long *d_found = nullptr, *h_found = nullptr;
+    float kernel_ms = 0.f;             // device time of the last nl_flow_interpolate's kernels
+};
+
+#define FLOW_ENTER(f)                                                      \
+    if (!(f)) return nl_fail(err, errlen, NL_EINVAL, "flow field is NULL"); \
+    NL_HIP(hipSetDevice((f)->device));
+
+extern "C" int nl_flow_destroy(nl_flow *f) {
+    if (!f) return NL_OK;
+    hipSetDevice(f->device);
+    if (f->stream) hipStreamSynchronize(f->stream);
+    void *ps[] = {f->d_in, f->d_cell, f->d_perm, f->d_rows, f->d_grid, f->d_start, f->d_cursor, f->d_q, f->d_out, f->d_found};
+    for (void *p : ps) if (p) hipFree(p);
+    if (f->h_found) hipHostFree(f->h_found);
+    if (f->ev_a) hipEventDestroy(f->ev_a);
+    if (f->ev_b) hipEventDestroy(f->ev_b);
+    if (f->stream) hipStreamDestroy(f->stream);
+    (void)hipGetLastError();
+    delete f;
+    return NL_OK;
+}
+
+extern "C" int nl_flow_create(nl_flow **out, int device, int ndim, const double *spacing, double r, char *err, size_t errlen) {
+    if (!out) return nl_fail(err, errlen, NL_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (ndim != 2 && ndim != 3) return nl_fail(err, errlen, NL_EINVAL, "ndim must be 2 or 3");
+    if (!spacing) return nl_fail(err, errlen, NL_EINVAL, "spacing is NULL");
+    for (int a = 0; a < ndim; ++a)
+        if (!(spacing[a] > 0.0) || !(spacing[a] < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "spacing must be positive and finite");
+    if (!(r > 0.0) || !(r < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "the radius must be positive and finite");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        (void)hipGetLastError();
+        return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but no HIP device is visible");
+    }
+    if (device < 0 || device >= count) return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but device %d does not exist", device);
+    nl_flow *f = new nl_flow();
+    f->device = device;
+    f->ndim = ndim;
+    f->r = r;
+    for (int a = 0; a < ndim; ++a) f->sp.s[3 - ndim + a] = spacing[a];
+    auto fail = [&](int rc) { nl_flow_destroy(f); return rc; };
+#define FLOW_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); \
+        return fail(nl_fail(err, errlen, e_ == hipErrorOutOfMemory ? NL_ENOMEM : NL_EHIP, "%s: %s%s", #expr, hipGetErrorString(e_), \
+                            e_ == hipErrorOutOfMemory ? " [out of memory]" : "")); } } while (0)
+    FLOW_TRY(hipSetDevice(device));
+    FLOW_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    FLOW_TRY(hipEventCreate(&f->ev_a));
+    FLOW_TRY(hipEventCreate(&f->ev_b));
+    FLOW_TRY(hipMalloc((void **)&f->d_grid, sizeof(FlowGrid)));
+    FLOW_TRY(hipMalloc((void **)&f->d_start, (size_t)(FLOW_MAX_CELLS + 1) * 4));
+    FLOW_TRY(hipMalloc((void **)&f->d_cursor, (size_t)(FLOW_MAX_CELLS + 1) * 4));
+    FLOW_TRY(hipMalloc((void **)&f->d_found, 8));
+    FLOW_TRY(hipHostMalloc((void **)&f->h_found, 8, hipHostMallocDefault));
+#undef FLOW_TRY
+    *out = f;
+    return NL_OK;
+}
+
+template <typename P> static int flow_grow(P **p, i64 have, i64 need, size_t elem, char *err, size_t errlen) {
+    if (need <= have) return NL_OK;
+    if (*p) NL_HIP(hipFree(*p));
+    *p = nullptr;
+    NL_HIP(hipMalloc((void **)p, (size_t)need * elem));
+    return NL_OK;
+}
+
+// The rows of one time point and direction: check coordinates (n, ndim) in voxels (the row's position, forward; position +
+// vector, backward), vectors (n, ndim), costs (n), all float64.  They replace the rows loaded before and stay on the device.
+extern "C" int nl_flow_load(nl_flow *f, const double *coords, const double *vectors, const double *costs, int64_t n, char *err, size_t errlen) {
+    FLOW_ENTER(f);
+    if (n < 0 || n > (i64)1 << 30) return nl_fail(err, errlen, NL_EINVAL, "row count must be 0 .. 2^30");
+    if (n > 0 && (!coords || !vectors || !costs)) return nl_fail(err, errlen, NL_EINVAL, "NULL rows");
+    f->n_rows = 0;
+    if (n == 0) return NL_OK;
+    const int D = f->ndim;
+    const i64 W = 2 * D + 1;
+    if (n > f->row_cap) {
+        const i64 nc = n > 2 * f->row_cap ? n : 2 * f->row_cap;
+        const i64 have = f->row_cap;
+        f->row_cap = 0;
+        if (int rc = flow_grow(&f->d_in, have * W, nc * W, 8, err, errlen)) return rc;
+        if (int rc = flow_grow(&f->d_cell, have, nc, 4, err, errlen)) return rc;
+        if (int rc = flow_grow(&f->d_perm, have, nc, 4, err, errlen)) return rc;
+        if (int rc = flow_grow(&f->d_rows, have, nc, sizeof(FlowRow), err, errlen)) return rc;
+        f->row_cap = nc;
+    }
+    hipStream_t st = f->stream;
+    double *d_c = f->d_in, *d_v = f->d_in + n * D, *d_k = f->d_in + 2 * n * D;
+    NL_HIP(hipMemcpyAsync(d_c, coords, (size_t)n * D * 8, hipMemcpyHostToDevice, st));
+    NL_HIP(hipMemcpyAsync(d_v, vectors, (size_t)n * D * 8, hipMemcpyHostToDevice, st));
+    NL_HIP(hipMemcpyAsync(d_k, costs, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    i64 cells = 8 * n;                  // more cells than a few per row only lengthen the scan
+    if (cells < FLOW_MIN_CELLS) cells = FLOW_MIN_CELLS;
+    if (cells > FLOW_MAX_CELLS) cells = FLOW_MAX_CELLS;
+    const unsigned gn = (unsigned)((n + 255) / 256);
+    flow_grid_kernel<<<1, 1024, 0, st>>>(d_c, D, (int)n, f->sp, f->r, (int)cells, f->d_grid, f->d_start);
+    NL_CHECK_LAUNCH();
+    flow_count_kernel<<<gn, 256, 0, st>>>(d_c, D, (int)n, f->sp, f->d_grid, f->d_start, f->d_cell);
+    NL_CHECK_LAUNCH();
+    flow_scan_kernel<<<1, 1024, 0, st>>>(f->d_grid, f->d_start, f->d_cursor);
+    NL_CHECK_LAUNCH();
+    flow_place_kernel<<<gn, 256, 0, st>>>((int)n, f->d_cell, f->d_cursor, f->d_perm);
+    NL_CHECK_LAUNCH();
+    flow_sort_write_kernel<<<grid1d(cells, 256, 256), 256, 0, st>>>(d_c, d_v, d_k, D, f->sp, f->d_grid, f->d_start, f->d_perm, f->d_rows);
+    NL_CHECK_LAUNCH();
+    NL_HIP(hipStreamSynchronize(st));   // the host arrays may go away after the call
+    f->n_rows = n;
+    return NL_OK;
+}
+
+// Interpolates n query rows (n, ndim) float64 (voxels) into out (n, ndim) float64; a row without a neighbour (a NaN row
+// included) is NaN.  n_found = rows that found a neighbour.  Longer inputs run in chunks of FLOW_CHUNK rows.
+extern "C" int nl_flow_interpolate(nl_flow *f, const double *queries, int64_t n, double *out, int64_t *n_found, char *err, size_t errlen) {
+    FLOW_ENTER(f);
+    if (n < 0) return nl_fail(err, errlen, NL_EINVAL, "negative query count");
+    if (!n_found) return nl_fail(err, errlen, NL_EINVAL, "n_found is NULL");
+    if (n > 0 && (!queries || !out)) return nl_fail(err, errlen, NL_EINVAL, "NULL queries or output");
+    *n_found = 0;
+    f->kernel_ms = 0.f;
+    if (n == 0) return NL_OK;
+    const int D = f->ndim;
+    if (f->n_rows == 0) {               // no rows for this time point: every query row is NaN
+        const double nan = __builtin_nan("");
+        for (i64 i = 0; i < n * D; ++i) out[i] = nan;
+        return NL_OK;
+    }
+    const i64 chunk = n < FLOW_CHUNK ? n : FLOW_CHUNK;
+    if (chunk > f->q_cap) {
+        const i64 have = f->q_cap;
+        f->q_cap = 0;
+        if (int rc = flow_grow(&f->d_q, have * D, chunk * D, 8, err, errlen)) return rc;
+        if (int rc = flow_grow(&f->d_out, have * D, chunk * D, 8, err, errlen)) return rc;
+        f->q_cap = chunk;
+    }
+    hipStream_t st = f->stream;
+    NL_HIP(hipMemsetAsync(f->d_found, 0, 8, st));
+    const double r2 = f->r * f->r;
+    for (i64 at = 0; at < n; at += chunk) {
+        const i64 m = n - at < chunk ? n - at : chunk;
+        NL_HIP(hipMemcpyAsync(f->d_q, queries + at * D, (size_t)m * D * 8, hipMemcpyHostToDevice, st));
+        NL_HIP(hipEventRecord(f->ev_a, st));
+        const unsigned g = (unsigned)((m + 255) / 256);
+        if (D == 3) flow_interp_kernel<3><<<g, 256, 0, st>>>(f->d_q, m, f->d_rows, f->d_start, f->d_grid, f->sp, r2, f->d_out, f->d_found);
+        else flow_interp_kernel<2><<<g, 256, 0, st>>>(f->d_q, m, f->d_rows, f->d_start, f->d_grid, f->sp, r2, f->d_out, f->d_found);
+        NL_CHECK_LAUNCH();
+        NL_HIP(hipEventRecord(f->ev_b, st));
+        NL_HIP(hipMemcpyAsync(out + at * D, f->d_out, (size_t)m * D * 8, hipMemcpyDeviceToHost, st));
+        NL_HIP(hipStreamSynchronize(st));
+        float ms = 0.f;
+        NL_HIP(hipEventElapsedTime(&ms, f->ev_a, f->ev_b));
+        f->kernel_ms += ms;
+    }
+    NL_HIP(hipMemcpyAsync(f->h_found, f->d_found, 8, hipMemcpyDeviceToHost, st));
+    NL_HIP(hipStreamSynchronize(st));
+    *n_found = (int64_t)*f->h_found;
+    return NL_OK;
+}
+
+// Device time (ms) of the kernels of the last nl_flow_interpolate call (transfers excluded).
+extern "C" int nl_flow_kernel_ms(nl_flow *f, float *ms, char *err, size_t errlen) {
+    if (!f || !ms) return nl_fail(err, errlen, NL_EINVAL, "flow field or ms is NULL");
+    *ms = f->kernel_ms;
+    return NL_OK;
+}

@@ -146,6 +146,10 @@ _PROTOS = {
     "nl_track_frame": [_p, _p, _int, _p, _p, _p, C.POINTER(_i64)],
     "nl_track_features": [_p, _int, _p, _p, _p],
     "nl_track_match": [_p, _int, _f64, _p, _p, _p, _p, _p],
+    "nl_flow_create": [C.POINTER(_p), _int, _int, _p, _f64],
+    "nl_flow_load": [_p, _p, _p, _p, _i64],
+    "nl_flow_interpolate": [_p, _p, _i64, _p, C.POINTER(_i64)],
+    "nl_flow_kernel_ms": [_p, C.POINTER(_f32)],
     "nl_host_half_round": [_p, _p, _i64],
     "nl_host_half_nansum": [_p, _i64, _int, _p],
     "nl_host_np_sum_f32": [_p, _i64, _p],
@@ -162,6 +166,7 @@ _PLAIN = {
     "nl_host_unregister": (_int, [_p]),
     "nl_ctx_info": (_int, [_p, C.c_char_p, C.POINTER(_f64)]),
     "nl_track_destroy": (_int, [_p]),
+    "nl_flow_destroy": (_int, [_p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
 
@@ -1135,3 +1140,62 @@ class Tracker:
         self._call("nl_track_match", 0 if mode == "dense" else 1, float(max_distance), _ptr(ri), _ptr(rc), _ptr(ci), _ptr(cc),
                    None if m is None else _ptr(m))
         return (ri, rc, ci, cc, m) if full else (ri, rc, ci, cc)
+
+
+class FlowField:
+    """Device state of flow-vector interpolation (include/nellie_amd.h nl_flow_*): the flow rows of one time point and direction,
+    binned into a grid of cells of edge r, stay on the device until the next load()."""
+
+    def __init__(self, ndim, spacing, r, device=0):
+        self.lib = load()
+        self.ndim = int(ndim)
+        if self.ndim not in (2, 3):
+            raise ValueError(f"flow fields are 2-D or 3-D, got ndim {ndim}")
+        sp = np.ascontiguousarray(spacing, dtype=np.float64)
+        if sp.size != self.ndim:
+            raise ValueError(f"spacing needs {self.ndim} values")
+        h = _p()
+        self.lib.call("nl_flow_create", C.byref(h), int(device), self.ndim, _ptr(sp), float(r))
+        self._h = h
+        self.n_rows = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.cdll.nl_flow_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _call(self, name, *args):
+        if not self._h:
+            raise NellieHipError(NL_ESTATE, "flow field is closed")
+        self.lib.call(name, self._h, *args)
+
+    def load(self, coords, vectors, costs):
+        """check coordinates (n, ndim), vectors (n, ndim) and costs (n) of one time point and direction"""
+        c = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1, self.ndim)
+        v = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, self.ndim)
+        k = np.ascontiguousarray(costs, dtype=np.float64).reshape(-1)
+        if not (len(c) == len(v) == len(k)):
+            raise ValueError(f"coords, vectors and costs disagree in length: {len(c)}, {len(v)}, {len(k)}")
+        self._call("nl_flow_load", _ptr(c), _ptr(v), _ptr(k), len(c))
+        self.n_rows = len(c)
+
+    def interpolate(self, queries):
+        """(vectors (n, ndim) float64 with NaN rows where no flow row is within r, number of rows that found one)"""
+        q = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, self.ndim)
+        out = np.empty((len(q), self.ndim), np.float64)
+        found = _i64(0)
+        self._call("nl_flow_interpolate", _ptr(q), len(q), _ptr(out), C.byref(found))
+        return out, int(found.value)
+
+    def kernel_ms(self) -> float:
+        ms = _f32(0)
+        self._call("nl_flow_kernel_ms", C.byref(ms))
+        return float(ms.value)
