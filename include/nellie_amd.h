@@ -565,13 +565,43 @@ int nl_host_np_sum_f32(const float *in, int64_t n, float *out, char *err, size_t
    nl_flow_interpolate : n query rows (n, ndim) float64 in voxels -> out (n, ndim) float64.  Neighbours of a query are the rows
                          with sum_axes (q*s - c*s)^2 <= r*r; a row without one (a NaN row included) is NaN.  n_found = the number
                          of rows that found a neighbour.  Inputs of any length: the library runs them in chunks.
-   nl_flow_kernel_ms   : device time of the kernels of the last nl_flow_interpolate call, transfers excluded. */
+   nl_flow_interpolate_dev : the same for n query rows and an output that are already on the field's device (device pointers),
+                         in one launch: nothing crosses the host.  The caller's work on the queries must be complete.  With
+                         no rows loaded nothing is written and n_found = 0.
+   nl_flow_kernel_ms   : device time of the kernels of the last nl_flow_interpolate(_dev) call, transfers excluded. */
 typedef struct nl_flow nl_flow;
 int nl_flow_create(nl_flow **out, int device, int ndim, const double *spacing, double r, char *err, size_t errlen);
 int nl_flow_destroy(nl_flow *field);
 int nl_flow_load(nl_flow *field, const double *coords, const double *vectors, const double *costs, int64_t n, char *err, size_t errlen);
 int nl_flow_interpolate(nl_flow *field, const double *queries, int64_t n, double *out, int64_t *n_found, char *err, size_t errlen);
+int nl_flow_interpolate_dev(nl_flow *field, const double *d_queries, int64_t n, double *d_out, int64_t *n_found, char *err, size_t errlen);
 int nl_flow_kernel_ms(nl_flow *field, float *ms, char *err, size_t errlen);
+
+/* ------------------------------------------------------------------ voxel reassignment -------- */
+/* nellie/tracking/voxel_reassignment.py on the device.  A reassigner has its own stream and buffers and
+   keeps the last two frames of a label stack: union mask (1 bit / voxel), labelled voxels in raster order, their labels and
+   their reassigned labels.
+   nl_reassign_create  : ndim 2 or 3 (nz = 1 for 2), the frame's shape, spacing ((Z,) Y, X in um) and the radius r in um.
+   nl_reassign_frame   : the next frame: branch and object labels (int32, frame shape).  The frame loaded before becomes
+                         "prev".  seed != 0: the frame's reassigned labels are its labels (frame 0).  n_vox = labelled voxels.
+   nl_reassign_pair    : matches the last two frames.  fw: a flow field with the forward rows of t loaded, bw: one with the
+                         backward rows of t + 1; NULL gives no candidates of that direction.  The predicted centroids never
+                         leave the device (nl_flow_interpolate_dev).  Writes the reassigned labels of the later frame.
+                         n_candidates = 0: no candidate at all, the later frame stays unassigned.
+   nl_reassign_fetch   : which = 0 the last frame, 1 the one before: linear voxel indices (n_vox, raster order), reassigned
+                         branch / object labels per labelled voxel, and (which = 0, after a pair with candidates) per voxel the
+                         rank of the best pair's source among the voxels of the frame before, -1 without a candidate.
+                         NULL pointers are skipped.
+   nl_reassign_kernel_ms : device time of the last nl_reassign_pair, its flow interpolation included, transfers excluded. */
+typedef struct nl_reassign nl_reassign;
+int nl_reassign_create(nl_reassign **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, const double *spacing, double r,
+                       char *err, size_t errlen);
+int nl_reassign_destroy(nl_reassign *reassigner);
+int nl_reassign_frame(nl_reassign *reassigner, const int32_t *branch, const int32_t *obj, int seed, int64_t *n_vox, char *err, size_t errlen);
+int nl_reassign_pair(nl_reassign *reassigner, nl_flow *fw, nl_flow *bw, int64_t *n_candidates, char *err, size_t errlen);
+int nl_reassign_fetch(nl_reassign *reassigner, int which, int64_t *vox, int32_t *re_branch, int32_t *re_obj, int32_t *best_src,
+                      char *err, size_t errlen);
+int nl_reassign_kernel_ms(nl_reassign *reassigner, float *ms, char *err, size_t errlen);
 
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit

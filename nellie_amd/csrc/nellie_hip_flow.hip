@@ -178,7 +178,34 @@ extern "C" int nl_flow_interpolate(nl_flow *f, const double *queries, int64_t n,
     return NL_OK;
 }
 
-// Device time (ms) of the kernels of the last nl_flow_interpolate call (transfers excluded).
+// nl_flow_interpolate for queries and results that are already on this field's device: n rows (n, ndim) float64 at d_queries ->
+// d_out, in one launch, nothing crosses the host.  The caller's work on d_queries must be complete; the call returns when d_out
+// is.  With no rows loaded nothing is written and n_found = 0.
+extern "C" int nl_flow_interpolate_dev(nl_flow *f, const double *d_queries, int64_t n, double *d_out, int64_t *n_found, char *err, size_t errlen) {
+    FLOW_ENTER(f);
+    if (n < 0 || n > (i64)1 << 31) return nl_fail(err, errlen, NL_EINVAL, "query count must be 0 .. 2^31");
+    if (!n_found) return nl_fail(err, errlen, NL_EINVAL, "n_found is NULL");
+    if (n > 0 && (!d_queries || !d_out)) return nl_fail(err, errlen, NL_EINVAL, "NULL queries or output");
+    *n_found = 0;
+    f->kernel_ms = 0.f;
+    if (n == 0 || f->n_rows == 0) return NL_OK;
+    hipStream_t st = f->stream;
+    NL_HIP(hipMemsetAsync(f->d_found, 0, 8, st));
+    const double r2 = f->r * f->r;
+    NL_HIP(hipEventRecord(f->ev_a, st));
+    const unsigned g = (unsigned)((n + 255) / 256);
+    if (f->ndim == 3) flow_interp_kernel<3><<<g, 256, 0, st>>>(d_queries, n, f->d_rows, f->d_start, f->d_grid, f->sp, r2, d_out, f->d_found);
+    else flow_interp_kernel<2><<<g, 256, 0, st>>>(d_queries, n, f->d_rows, f->d_start, f->d_grid, f->sp, r2, d_out, f->d_found);
+    NL_CHECK_LAUNCH();
+    NL_HIP(hipEventRecord(f->ev_b, st));
+    NL_HIP(hipMemcpyAsync(f->h_found, f->d_found, 8, hipMemcpyDeviceToHost, st));
+    NL_HIP(hipStreamSynchronize(st));
+    NL_HIP(hipEventElapsedTime(&f->kernel_ms, f->ev_a, f->ev_b));
+    *n_found = (int64_t)*f->h_found;
+    return NL_OK;
+}
+
+// Device time (ms) of the kernels of the last nl_flow_interpolate / nl_flow_interpolate_dev call (transfers excluded).
 extern "C" int nl_flow_kernel_ms(nl_flow *f, float *ms, char *err, size_t errlen) {
     if (!f || !ms) return nl_fail(err, errlen, NL_EINVAL, "flow field or ms is NULL");
     *ms = f->kernel_ms;

@@ -149,7 +149,13 @@ _PROTOS = {
     "nl_flow_create": [C.POINTER(_p), _int, _int, _p, _f64],
     "nl_flow_load": [_p, _p, _p, _p, _i64],
     "nl_flow_interpolate": [_p, _p, _i64, _p, C.POINTER(_i64)],
+    "nl_flow_interpolate_dev": [_p, _p, _i64, _p, C.POINTER(_i64)],
     "nl_flow_kernel_ms": [_p, C.POINTER(_f32)],
+    "nl_reassign_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _f64],
+    "nl_reassign_frame": [_p, _p, _p, _int, C.POINTER(_i64)],
+    "nl_reassign_pair": [_p, _p, _p, C.POINTER(_i64)],
+    "nl_reassign_fetch": [_p, _int, _p, _p, _p, _p],
+    "nl_reassign_kernel_ms": [_p, C.POINTER(_f32)],
     "nl_host_half_round": [_p, _p, _i64],
     "nl_host_half_nansum": [_p, _i64, _int, _p],
     "nl_host_np_sum_f32": [_p, _i64, _p],
@@ -167,6 +173,7 @@ _PLAIN = {
     "nl_ctx_info": (_int, [_p, C.c_char_p, C.POINTER(_f64)]),
     "nl_track_destroy": (_int, [_p]),
     "nl_flow_destroy": (_int, [_p]),
+    "nl_reassign_destroy": (_int, [_p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
 
@@ -1198,4 +1205,81 @@ class FlowField:
     def kernel_ms(self) -> float:
         ms = _f32(0)
         self._call("nl_flow_kernel_ms", C.byref(ms))
+        return float(ms.value)
+
+
+class Reassigner:
+    """Device state of voxel reassignment for one label stack (include/nellie_amd.h nl_reassign_*): the last two frames stay on
+    the device -- mask, labelled voxels, labels and reassigned labels -- so a frame is uploaded once and only the reassigned
+    labels of the labelled voxels (and the best pairs, when asked for) come back."""
+
+    def __init__(self, shape, spacing, r, device=0):
+        self.lib = load()
+        self.ndim = len(shape)
+        if self.ndim not in (2, 3):
+            raise ValueError(f"label frames are 2-D or 3-D, got shape {tuple(shape)}")
+        self.shape = tuple(int(s) for s in shape)
+        nz, ny, nx = (1,) + self.shape if self.ndim == 2 else self.shape
+        sp = np.ascontiguousarray(spacing, dtype=np.float64)
+        if sp.size != self.ndim:
+            raise ValueError(f"spacing needs {self.ndim} values")
+        h = _p()
+        self.lib.call("nl_reassign_create", C.byref(h), int(device), self.ndim, nz, ny, nx, _ptr(sp), float(r))
+        self._h = h
+        self.n = [0, 0]                                   # labelled voxels of the last frame, of the one before
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.cdll.nl_reassign_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _call(self, name, *args):
+        if not self._h:
+            raise NellieHipError(NL_ESTATE, "reassigner is closed")
+        self.lib.call(name, self._h, *args)
+
+    def frame(self, branch, obj, seed=False) -> int:
+        """uploads the next frame's labels; returns its number of labelled voxels (branch > 0 | obj > 0)"""
+        arrs = []
+        for a in (branch, obj):
+            a = np.asarray(a)
+            if a.shape != self.shape:
+                raise ValueError(f"frame shape {a.shape} does not match the reassigner's {self.shape}")
+            arrs.append(np.ascontiguousarray(a, dtype=np.int32))
+        n = _i64(0)
+        self._call("nl_reassign_frame", _ptr(arrs[0]), _ptr(arrs[1]), 1 if seed else 0, C.byref(n))
+        self.n = [int(n.value), self.n[0]]
+        return self.n[0]
+
+    def pair(self, flow_fw=None, flow_bw=None) -> int:
+        """matches the last two frames with the rows loaded in the two FlowFields (None: no candidates of that direction);
+        returns the number of candidates"""
+        n = _i64(0)
+        self._call("nl_reassign_pair", flow_fw._h if flow_fw is not None else None, flow_bw._h if flow_bw is not None else None,
+                   C.byref(n))
+        return int(n.value)
+
+    def fetch(self, which=0, voxels=True, labels=True, best=False):
+        """(linear voxel indices, reassigned branch labels, reassigned object labels, best-pair source ranks) of a frame, None
+        for what was not asked for"""
+        n = self.n[which]
+        vox = np.empty(n, np.int64) if voxels else None
+        rb = np.empty(n, np.int32) if labels else None
+        ro = np.empty(n, np.int32) if labels else None
+        bs = np.empty(n, np.int32) if best else None
+        opt = lambda a: None if a is None else _ptr(a)   # noqa: E731
+        self._call("nl_reassign_fetch", int(which), opt(vox), opt(rb), opt(ro), opt(bs))
+        return vox, rb, ro, bs
+
+    def kernel_ms(self) -> float:
+        ms = _f32(0)
+        self._call("nl_reassign_kernel_ms", C.byref(ms))
         return float(ms.value)

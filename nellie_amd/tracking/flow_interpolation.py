@@ -85,6 +85,13 @@ class FlowInterpolator:
         self._field.load(self.check_coords, self.check_rows[:, 1 + nd:1 + 2 * nd], self.check_rows[:, -1])
         self.current_t = t
 
+    def device_field(self, t):
+        """the device field (hipnative.FlowField) with the rows of time point t loaded, None when t has no rows: for stages that
+        interpolate at coordinates which are already on the device (VoxelReassigner)"""
+        if self.current_t != t:
+            self._load_t(t)
+        return self._field if len(self.check_rows) else None
+
     def interpolate_coord(self, coords, t):
         """flow vectors (n, D) at coords (n, D) for time point t; NaN rows where no flow row is in reach; shape (0, D) when no
         row of the call found one (flow_interpolation.py:165-170)"""
