@@ -603,6 +603,45 @@ int nl_reassign_fetch(nl_reassign *reassigner, int which, int64_t *vox, int32_t 
                       char *err, size_t errlen);
 int nl_reassign_kernel_ms(nl_reassign *reassigner, float *ms, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ voxel-level features -------- */
+/* Voxels of nellie/feature_extraction/hierarchical.py on the device.  The object has its own stream and
+   buffers and keeps one frame: mask (1 bit / voxel), the labelled voxels in raster order and their values.
+   nl_voxfeat_create   : ndim 2 or 3 (nz = 1 for 2), the frame's shape, spacing ((Z,) Y, X in um) and the time step dt in s.
+   nl_voxfeat_frame    : component and branch labels (int32), intensity and structure frames in their own dtypes (the dtype codes of
+                         nl_filter_load).  Lists the voxels with component > 0 and gathers their four values.  n_vox = their number.
+   nl_voxfeat_fetch_voxels : linear voxel indices (n_vox, raster order), the two labels, intensity and structure values (n_vox
+                         elements of the uploaded dtypes).  NULL pointers are skipped.
+   nl_voxfeat_motility : bw: a flow field with the backward rows of the frame's time point loaded (vec01), fw: one with its
+                         forward rows (vec12); NULL: the direction does not exist.  The flow is interpolated at every voxel on
+                         the device (nl_flow_interpolate_dev); a direction without a field, rows or any neighbour is all NaN.
+                         Then the pivot voxel of every branch label and direction (smallest |vec|, lowest index on a tie) and the
+                         motility features in float64.  n_found_*: voxels with a flow neighbour.
+   nl_voxfeat_fetch_motility : out = 13 host pointers (NULL ones skipped), float32: vec01 (n, D), vec12 (n, D), linear_vel_vector
+                         (n, D), linear_vel, angular_vel_vector ((n) in 2-D, (n, 3) in 3-D), angular_vel, linear_acc,
+                         angular_acc, rel_linear_vel, rel_angular_vel, rel_linear_acc, rel_angular_acc, rel_directionality.
+   nl_voxfeat_nodes    : pixel_class (any dtype code) and distance (float32 or float64) frames.  Nodes are the voxels with pixel
+                         class > 0 in raster order; a node's box is trunc(radius * -+1 + index) per axis, upper limit + 1, clamped
+                         to [0, size]; a voxel belongs to the node when every coordinate is within the limits, ends included.
+   nl_voxfeat_fetch_nodes : the limits per axis (n_nodes, 2) int64 (lims2 in 3-D only) and both lists as CSR of int32 ranks:
+                         node_start (n_nodes) / node_val (n_pairs): the voxels of every node, ascending; vox_start (n_vox) /
+                         vox_val (n_pairs): the nodes of every voxel, ascending.  The last list ends at n_pairs.
+   nl_voxfeat_kernel_ms : ms[5], device time since the last nl_voxfeat_frame: frame load and compaction, flow interpolation,
+                         pivots, motility, node assignment.  Transfers excluded. */
+typedef struct nl_voxfeat nl_voxfeat;
+int nl_voxfeat_create(nl_voxfeat **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, const double *spacing, double dt,
+                      char *err, size_t errlen);
+int nl_voxfeat_destroy(nl_voxfeat *voxfeat);
+int nl_voxfeat_frame(nl_voxfeat *voxfeat, const int32_t *comp, const int32_t *branch, const void *raw, int raw_dtype, const void *structure,
+                     int struct_dtype, int64_t *n_vox, char *err, size_t errlen);
+int nl_voxfeat_fetch_voxels(nl_voxfeat *voxfeat, int64_t *vox, int32_t *comp, int32_t *branch, void *raw, void *structure, char *err, size_t errlen);
+int nl_voxfeat_motility(nl_voxfeat *voxfeat, nl_flow *bw, nl_flow *fw, int64_t *n_found_bw, int64_t *n_found_fw, char *err, size_t errlen);
+int nl_voxfeat_fetch_motility(nl_voxfeat *voxfeat, float *const *out, char *err, size_t errlen);
+int nl_voxfeat_nodes(nl_voxfeat *voxfeat, const void *pixel_class, int class_dtype, const void *distance, int dist_dtype, int64_t *n_nodes,
+                     int64_t *n_pairs, char *err, size_t errlen);
+int nl_voxfeat_fetch_nodes(nl_voxfeat *voxfeat, int64_t *lims0, int64_t *lims1, int64_t *lims2, int32_t *node_start, int32_t *node_val,
+                           int32_t *vox_start, int32_t *vox_val, char *err, size_t errlen);
+int nl_voxfeat_kernel_ms(nl_voxfeat *voxfeat, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit
    Hessians h6[n][6] = (hxx,hxy,hxz,hyy,hyz,hzz) writes out4[n][4] = (l1,l2,l3 sorted by |.|, Frangi

@@ -156,6 +156,14 @@ _PROTOS = {
     "nl_reassign_pair": [_p, _p, _p, C.POINTER(_i64)],
     "nl_reassign_fetch": [_p, _int, _p, _p, _p, _p],
     "nl_reassign_kernel_ms": [_p, C.POINTER(_f32)],
+    "nl_voxfeat_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _f64],
+    "nl_voxfeat_frame": [_p, _p, _p, _p, _int, _p, _int, C.POINTER(_i64)],
+    "nl_voxfeat_fetch_voxels": [_p, _p, _p, _p, _p, _p],
+    "nl_voxfeat_motility": [_p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
+    "nl_voxfeat_fetch_motility": [_p, C.POINTER(_p)],
+    "nl_voxfeat_nodes": [_p, _p, _int, _p, _int, C.POINTER(_i64), C.POINTER(_i64)],
+    "nl_voxfeat_fetch_nodes": [_p, _p, _p, _p, _p, _p, _p, _p],
+    "nl_voxfeat_kernel_ms": [_p, _p],
     "nl_host_half_round": [_p, _p, _i64],
     "nl_host_half_nansum": [_p, _i64, _int, _p],
     "nl_host_np_sum_f32": [_p, _i64, _p],
@@ -174,6 +182,7 @@ _PLAIN = {
     "nl_track_destroy": (_int, [_p]),
     "nl_flow_destroy": (_int, [_p]),
     "nl_reassign_destroy": (_int, [_p]),
+    "nl_voxfeat_destroy": (_int, [_p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
 
@@ -1283,3 +1292,121 @@ class Reassigner:
         ms = _f32(0)
         self._call("nl_reassign_kernel_ms", C.byref(ms))
         return float(ms.value)
+
+
+class VoxelFeatures:
+    """Device state of the voxel level of the hierarchy for one stack (include/nellie_amd.h nl_voxfeat_*): one frame stays on
+    the device -- mask, labelled voxels and their values -- while its flow vectors, pivots, motility features and node lists are
+    computed; only per-voxel results, the two CSR lists and the node limits come back."""
+
+    PARTS = ("load", "flow", "pivot", "motility", "nodes")
+    MOTILITY = ("vec01", "vec12", "linear_vel_vector", "linear_vel", "angular_vel_vector", "angular_vel", "linear_acc", "angular_acc",
+                "rel_linear_vel", "rel_angular_vel", "rel_linear_acc", "rel_angular_acc", "rel_directionality")
+
+    def __init__(self, shape, spacing, dt, device=0):
+        self.lib = load()
+        self.ndim = len(shape)
+        if self.ndim not in (2, 3):
+            raise ValueError(f"frames are 2-D or 3-D, got shape {tuple(shape)}")
+        self.shape = tuple(int(s) for s in shape)
+        nz, ny, nx = (1,) + self.shape if self.ndim == 2 else self.shape
+        sp = np.ascontiguousarray(spacing, dtype=np.float64)
+        if sp.size != self.ndim:
+            raise ValueError(f"spacing needs {self.ndim} values")
+        h = _p()
+        self.lib.call("nl_voxfeat_create", C.byref(h), int(device), self.ndim, nz, ny, nx, _ptr(sp), float(dt))
+        self._h = h
+        self.n = 0                                        # labelled voxels of the loaded frame
+        self.n_nodes = self.n_pairs = 0
+        self._dtypes = (np.dtype(np.uint8), np.dtype(np.uint8))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.cdll.nl_voxfeat_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _call(self, name, *args):
+        if not self._h:
+            raise NellieHipError(NL_ESTATE, "voxel-feature object is closed")
+        self.lib.call(name, self._h, *args)
+
+    def _frame_array(self, a, what, dtype=None):
+        a = np.asarray(a)
+        if a.shape != self.shape:
+            raise ValueError(f"{what} shape {a.shape} does not match the object's {self.shape}")
+        if dtype is None and a.dtype not in DTYPE_CODES:
+            raise TypeError(f"unsupported {what} dtype {a.dtype}")
+        return np.ascontiguousarray(a, dtype=dtype)
+
+    def frame(self, comp, branch, raw, structure) -> int:
+        """uploads a frame; returns the number of voxels with component label > 0"""
+        c, b = self._frame_array(comp, "component label", np.int32), self._frame_array(branch, "branch label", np.int32)
+        r, s = self._frame_array(raw, "intensity"), self._frame_array(structure, "structure")
+        n = _i64(0)
+        self._call("nl_voxfeat_frame", _ptr(c), _ptr(b), _ptr(r), DTYPE_CODES[r.dtype], _ptr(s), DTYPE_CODES[s.dtype], C.byref(n))
+        self.n, self._dtypes = int(n.value), (r.dtype, s.dtype)
+        self.n_nodes = self.n_pairs = 0
+        return self.n
+
+    def fetch_voxels(self):
+        """(linear voxel indices, component labels, branch labels (int32), intensity, structure) of the loaded frame"""
+        vox, c, b = np.empty(self.n, np.int64), np.empty(self.n, np.int32), np.empty(self.n, np.int32)
+        r, s = np.empty(self.n, self._dtypes[0]), np.empty(self.n, self._dtypes[1])
+        self._call("nl_voxfeat_fetch_voxels", _ptr(vox), _ptr(c), _ptr(b), _ptr(r), _ptr(s))
+        return vox, c, b, r, s
+
+    def motility(self, flow_bw=None, flow_fw=None):
+        """the motility features of the loaded frame from the rows loaded in the two FlowFields (None: the direction does not
+        exist); returns (voxels with a backward neighbour, with a forward neighbour)"""
+        a, b = _i64(0), _i64(0)
+        self._call("nl_voxfeat_motility", flow_bw._h if flow_bw is not None else None, flow_fw._h if flow_fw is not None else None,
+                   C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def fetch_motility(self):
+        """{name: float32 array} for every name of MOTILITY"""
+        D, A = self.ndim, (3 if self.ndim == 3 else 1)
+        widths = (D, D, D, 1, A, 1, 1, 1, 1, 1, 1, 1, 1)
+        out = {k: np.empty((self.n, w) if w > 1 else self.n, np.float32) for k, w in zip(self.MOTILITY, widths)}
+        ptrs = (_p * len(widths))(*[_ptr(out[k]) for k in self.MOTILITY])
+        self._call("nl_voxfeat_fetch_motility", ptrs)
+        return out
+
+    def nodes(self, pixel_class, distance):
+        """assigns the loaded frame's voxels to the nodes (pixel class > 0) whose radius box holds them; returns (nodes, pairs)"""
+        pc = self._frame_array(pixel_class, "pixel class")
+        d = np.asarray(distance)
+        d = self._frame_array(d, "distance", None if d.dtype in (np.float32, np.float64) else (np.float32 if d.dtype == np.float16 else np.float64))
+        m, p = _i64(0), _i64(0)
+        self._call("nl_voxfeat_nodes", _ptr(pc), DTYPE_CODES[pc.dtype], _ptr(d), DTYPE_CODES[d.dtype], C.byref(m), C.byref(p))
+        self.n_nodes, self.n_pairs = int(m.value), int(p.value)
+        return self.n_nodes, self.n_pairs
+
+    def fetch_nodes(self):
+        """(limits per axis [(n_nodes, 2) int64] * ndim, (node offsets (n_nodes + 1), voxel ranks), (voxel offsets (n + 1), node
+        ranks)): both lists as CSR, ascending within a list"""
+        m, p = self.n_nodes, self.n_pairs
+        lims = [np.zeros((m, 2), np.int64) for _ in range(self.ndim)]
+        nstart, vstart = np.zeros(m + 1, np.int32), np.zeros(self.n + 1, np.int32)
+        nval, vval = np.zeros(p, np.int32), np.zeros(p, np.int32)
+        self._call("nl_voxfeat_fetch_nodes", _ptr(lims[0]), _ptr(lims[1]), _ptr(lims[2]) if self.ndim == 3 else None, _ptr(nstart), _ptr(nval),
+                   _ptr(vstart), _ptr(vval))
+        nstart[m] = vstart[self.n] = p
+        return lims, (nstart.astype(np.int64), nval.astype(np.int64)), (vstart.astype(np.int64), vval.astype(np.int64))
+
+    def kernel_ms_parts(self) -> dict:
+        ms = (_f32 * len(self.PARTS))()
+        self._call("nl_voxfeat_kernel_ms", ms)
+        return dict(zip(self.PARTS, (float(v) for v in ms)))
+
+    def kernel_ms(self) -> float:
+        """device time of the kernels since the last frame(), transfers excluded"""
+        return sum(self.kernel_ms_parts().values())

@@ -1,0 +1,214 @@
+"""GPU tests of the voxel level of the hierarchy (nellie_amd.feature_extraction, csrc/voxfeat.inc): every golden of the
+reference's Voxels class through the public `Voxels`, the voxel table through `VoxelFeatures` on files, reuse of the hierarchy's
+interpolators, and determinism.
+
+Integers, both node lists (CSR), the node limits and the NaN pattern are compared exactly.  A float32 output is within
+one float32 ulp of the reference value + K * 2^-52 * S, S the attribute's scale (scale()); K and the measured error behind it
+are in DESIGN.md section 13.  No voxel is left out of a comparison."""
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+import voxel_goldens as vg
+
+pytestmark = pytest.mark.gpu
+NAMES = vg.names()
+# K is 8 x the largest measured error beyond the float32 ulp, in units of 2^-52 * S, rounded up to a power of two (DESIGN.md
+# section 13).  No measurement on an MI355X exists yet: until one does, K is the smallest value that rule can give, 1 -- the
+# float32 ulp of the reference value is 2^29 times the float64 ulp, so a float64 chain that differs from numpy's in the last bits of
+# atan2 / sqrt / a summation order moves a float32 result by at most that one ulp.  test_golden prints every measured excess.
+K = 1.0
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from nellie_amd import build, hipnative
+    build.build(verbose=False)
+    lib = hipnative.load()
+    assert lib.device_count() > 0, "no HIP device"
+    return lib
+
+
+def scale(g, name):
+    """S of an attribute: the largest coordinate in um, / dt for velocities, / dt^2 for accelerations; 1 / dt and 1 / dt^2 for the
+    3-D angular quantities, pi / dt and pi / dt^2 for the 2-D ones; 1 for directionality"""
+    dt = g["dt"]
+    length = float(np.max(np.asarray(g["comp"].shape[1:]) * g["spacing"]))
+    turn = np.pi if g["D"] == 2 else 1.0
+    return {"vec01": length, "vec12": length, "linear_vel_vector": length / dt, "linear_vel": length / dt, "rel_linear_vel": length / dt,
+            "linear_acc": length / dt ** 2, "rel_linear_acc": length / dt ** 2, "angular_vel_vector": turn / dt, "angular_vel": turn / dt,
+            "rel_angular_vel": turn / dt, "angular_acc": turn / dt ** 2, "rel_angular_acc": turn / dt ** 2, "rel_directionality": 1.0}[name]
+
+
+def excess(got, want, s):
+    """the largest error beyond one float32 ulp of the reference value, in units of 2^-52 * S; the NaN patterns must agree"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32, (got.shape, want.shape, got.dtype, want.dtype)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), ("NaN pattern", int(np.sum(np.isnan(got) != np.isnan(want))))
+    assert np.array_equal(np.isinf(got), np.isinf(want)) and np.array_equal(got[np.isinf(got)], want[np.isinf(want)])
+    ok = np.isfinite(want)
+    err = np.abs(got[ok].astype(np.float64) - want[ok].astype(np.float64)) - np.spacing(np.abs(want[ok])).astype(np.float64)
+    return float(np.max(err, initial=0.0)) / (2.0 ** -52 * s) if err.size else 0.0
+
+
+def flow_files(tmp_path, g):
+    """the golden's hierarchy double with this package's interpolators on its flow array"""
+    from nellie_amd.tracking.flow_interpolation import FlowInterpolator
+    root = tmp_path / f"run{len(os.listdir(tmp_path))}"
+    root.mkdir()
+    path = str(root / "flow.npy")
+    np.save(path, g["flow"])
+    h = vg.hierarchy_double(g)
+    h.im_info.im_path = "im"
+    h.im_info.pipeline_paths = {"flow_vector_array": path}
+    h.im_info.get_memmap = lambda p, read_mode="r+": g["raw"]
+    h.flow_interpolator_fw = FlowInterpolator(h.im_info)
+    h.flow_interpolator_bw = FlowInterpolator(h.im_info, forward=False)
+    return h
+
+
+def run_voxels(tmp_path, g):
+    from nellie_amd.feature_extraction import Voxels
+    h = flow_files(tmp_path, g)
+    try:
+        v = Voxels(h)
+        v.run()
+    finally:
+        h.flow_interpolator_fw.close()
+        h.flow_interpolator_bw.close()
+    return v
+
+
+def same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+
+
+def assert_equals_reference(g, v):
+    """-> the largest excess of the golden, per attribute"""
+    ref = g["ref"]
+    worst = {}
+    assert v.stats_to_aggregate == ref["stats_to_aggregate"] and v.features_to_save == ref["features_to_save"]
+    for t in range(g["T"]):
+        n = len(ref["coords"][t])
+        for k in vg.PER_VOXEL:
+            assert same(getattr(v, k)[t], ref[k][t]), (k, t)
+        assert v.image_name[t].dtype == object and list(v.image_name[t]) == [g["filename"]] * n
+        for k in vg.FLOAT_ATTRS:
+            got, want = getattr(v, k)[t], ref[k][t]
+            if k in ("vec01", "vec12") and len(want) == 0 and n > 0:         # no voxel had a flow neighbour: (0, D) there, NaN here
+                assert got.shape == (n, g["D"]) and got.dtype == np.float32 and np.isnan(got).all(), (k, t)
+                continue
+            worst[k] = max(worst.get(k, 0.0), excess(got, want, scale(g, k)))
+        if g["skip_nodes"]:
+            continue
+        for ax, got in enumerate((v.node_dim0_lims[t], v.node_dim1_lims[t], v.node_dim2_lims[t])):
+            want = ref[f"node_dim{ax}_lims"][t]
+            assert (got is None and want is None and ax >= g["D"]) or same(got, want), ("limits", ax, t)
+        for got, csr, want in ((v.node_voxel_idxs[t], v.node_voxel_idxs_csr[t], ref["node_voxel_idxs_csr"][t]),
+                               (v.node_labels[t], v.node_labels_csr[t], ref["node_labels_csr"][t])):
+            if n == 0 and got is v.node_labels[t]:
+                assert got == []                                            # the reference has no list for a frame without voxels
+                continue
+            assert same(csr[0], want[0]) and same(csr[1], want[1]), ("CSR", t)
+            lists = vg.split_node_lists(*want)
+            assert len(got) == len(lists) and all(same(a, b) for a, b in zip(got, lists)), ("lists", t)
+    if g["skip_nodes"]:
+        assert v.node_labels == [] and v.node_voxel_idxs == [] and v.node_dim0_lims == [] and v.node_dim2_lims == []
+    return worst
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_golden(hip, tmp_path, name):
+    g = vg.load(name)
+    v = run_voxels(tmp_path, g)
+    worst = assert_equals_reference(g, v)
+    for k, w in sorted(worst.items()):
+        print(f"{name} {k}: excess {w:.3g} x 2^-52 S")
+    assert all(w <= K for w in worst.values()), worst
+    assert len(v.kernel_ms) == g["T"] and all(set(p) == {"load", "flow", "pivot", "motility", "nodes"} for p in v.kernel_ms)
+
+
+def test_two_runs_give_identical_bits(hip, tmp_path):
+    g = vg.load("voxels_3d_sparse_flow")
+    a, b = run_voxels(tmp_path, g), run_voxels(tmp_path, g)
+    for k in vg.PER_VOXEL + vg.FLOAT_ATTRS:
+        for x, y in zip(getattr(a, k), getattr(b, k)):
+            assert x.dtype == y.dtype and x.tobytes() == y.tobytes(), k
+    for x, y in zip(a.node_labels_csr + a.node_voxel_idxs_csr, b.node_labels_csr + b.node_voxel_idxs_csr):
+        assert x[0].tobytes() == y[0].tobytes() and x[1].tobytes() == y[1].tobytes()
+    assert sum(len(c) for c in a.coords) > 1000 and sum(len(c[1]) for c in a.node_labels_csr) > 1000
+
+
+def test_hierarchy_interpolators_are_used_not_reloaded(hip, tmp_path, monkeypatch):
+    """interpolators of this package (they have device_field) are queried on the device; none is built, none is closed"""
+    from nellie_amd.feature_extraction import Voxels
+    from nellie_amd.tracking import flow_interpolation as fi
+    g = vg.load("voxels_2d")
+    h = flow_files(tmp_path, g)
+    calls = []
+    for obj, key in ((h.flow_interpolator_fw, "fw"), (h.flow_interpolator_bw, "bw")):
+        inner = obj.device_field
+        obj.device_field = lambda t, inner=inner, key=key: calls.append((key, t)) or inner(t)
+    built = []
+    monkeypatch.setattr(fi.FlowInterpolator, "__init__", lambda self, *a, **k: built.append(1))
+    v = Voxels(h)
+    v.run()
+    assert not built
+    assert sorted(calls) == [("bw", 1), ("bw", 2), ("bw", 3), ("fw", 0), ("fw", 1), ("fw", 2)]
+    assert h.flow_interpolator_fw._field is not None and h.flow_interpolator_bw._field is not None      # still open
+    assert_equals_reference(g, v)
+    h.flow_interpolator_fw.close()
+    h.flow_interpolator_bw.close()
+
+
+def test_foreign_interpolators_are_replaced_and_closed(hip, tmp_path):
+    """interpolators without device_field (the reference's): this package's are built from im_info and closed afterwards"""
+    from nellie_amd.feature_extraction import Voxels
+    g = vg.load("voxels_3d_x70")
+    h = flow_files(tmp_path, g)
+    h.flow_interpolator_fw.close()
+    h.flow_interpolator_bw.close()
+    h.flow_interpolator_fw = h.flow_interpolator_bw = SimpleNamespace(interpolate_coord=None)
+    v = Voxels(h)
+    v.run()
+    assert v._own_interpolators == [] and v._engine is None
+    assert all(w <= K for w in assert_equals_reference(g, v).values())
+
+
+def test_voxel_features_writes_the_reference_table(hip, tmp_path):
+    """VoxelFeatures(im_info).run() on a stack written with the project's ImInfo: header and rows of features_voxels against the
+    table the reference's saving rule gives from the golden attributes (integers, intensity and structure exactly, the motility
+    columns within the bound of the goldens)"""
+    from nellie_amd.feature_extraction import VoxelFeatures
+    from nellie_amd.im_info.verifier import ImInfo
+    g = vg.load("voxels_3d_aniso")
+    dim_res = dict(zip("ZYX", (float(s) for s in g["spacing"])), T=g["dt"])
+    im_info = ImInfo(g["raw"], dim_res=dim_res, output_dir=str(tmp_path), name="voxels")
+    paths = im_info.pipeline_paths
+    for key, data in (("im_preprocessed", g["struct"]), ("im_distance", g["distance"]), ("im_skel", (g["pixel_class"] > 0).astype(np.uint8)),
+                      ("im_instance_label", g["comp"]), ("im_skel_relabelled", g["branch"]), ("im_border", np.zeros(g["comp"].shape, np.uint8)),
+                      ("im_pixel_class", g["pixel_class"])):
+        im_info.allocate_memory(paths[key], dtype=str(data.dtype), data=data, description=key)
+    np.save(paths["flow_vector_array"], g["flow"])
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        VoxelFeatures(im_info, device="cpu")
+    vf = VoxelFeatures(im_info)
+    assert vf.run() is vf.voxels
+    g_named = dict(g, filename=vf.voxels.image_name[0][0])
+    assert all(w <= K for w in assert_equals_reference(g_named, vf.voxels).values())
+    want = vg.expected_csv(g["ref"]).splitlines()
+    got = open(paths["features_voxels"]).read().splitlines()
+    assert got[0] == want[0] == "t,label," + ",".join(f + "_raw" for f in g["ref"]["features_to_save"])
+    assert len(got) == len(want) == 1 + sum(len(c) for c in g["ref"]["coords"])
+    a = np.array([[float(x) if x else np.nan for x in row.split(",")] for row in got[1:]])
+    b = np.array([[float(x) if x else np.nan for x in row.split(",")] for row in want[1:]])
+    for j, col in enumerate(got[0].split(",")):
+        name = col[:-4] if col.endswith("_raw") else col
+        if name in vg.FLOAT_ATTRS:
+            w = excess(a[:, j].astype(np.float32), b[:, j].astype(np.float32), scale(g, name))
+            assert w <= K, (col, w)
+        else:
+            assert np.array_equal(a[:, j], b[:, j], equal_nan=True), col
