@@ -1,14 +1,12 @@
 // Translation unit of libnellie_hip.so (gfx950): flow-vector interpolation (nellie/tracking/flow_interpolation.py).  C-ABI in
 // include/nellie_amd.h; kernels in flow.inc.  A flow field owns its buffers and stream: it needs none of a Filter context's volumes.
-#include "nl_host.h"
+#include "nl_stage.h"
 #include "flow.inc"
 
 #define FLOW_CHUNK ((i64)1 << 22)      // query rows per launch: 96 MB in and 96 MB out on the device at D = 3
 
-struct nl_flow {
-    int device = 0, ndim = 3;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+struct nl_flow : StageBase {
+    int ndim = 3;
     FlowSpacing sp{{1.0, 1.0, 1.0}};
     double r = 0.5;
     i64 n_rows = 0, row_cap = 0;
@@ -22,21 +20,9 @@ struct nl_flow {
     float kernel_ms = 0.f;             // device time of the last nl_flow_interpolate's kernels
 };
 
-#define FLOW_ENTER(f)                                                      \
-    if (!(f)) return nl_fail(err, errlen, NL_EINVAL, "flow field is NULL"); \
-    NL_HIP(hipSetDevice((f)->device));
-
 extern "C" int nl_flow_destroy(nl_flow *f) {
     if (!f) return NL_OK;
-    hipSetDevice(f->device);
-    if (f->stream) hipStreamSynchronize(f->stream);
-    void *ps[] = {f->d_in, f->d_cell, f->d_perm, f->d_rows, f->d_grid, f->d_start, f->d_cursor, f->d_q, f->d_out, f->d_found};
-    for (void *p : ps) if (p) hipFree(p);
-    if (f->h_found) hipHostFree(f->h_found);
-    if (f->ev_a) hipEventDestroy(f->ev_a);
-    if (f->ev_b) hipEventDestroy(f->ev_b);
-    if (f->stream) hipStreamDestroy(f->stream);
-    (void)hipGetLastError();
+    stage_close(*f, {f->d_in, f->d_cell, f->d_perm, f->d_rows, f->d_grid, f->d_start, f->d_cursor, f->d_q, f->d_out, f->d_found}, {f->h_found});
     delete f;
     return NL_OK;
 }
@@ -44,68 +30,35 @@ extern "C" int nl_flow_destroy(nl_flow *f) {
 extern "C" int nl_flow_create(nl_flow **out, int device, int ndim, const double *spacing, double r, char *err, size_t errlen) {
     if (!out) return nl_fail(err, errlen, NL_EINVAL, "out is NULL");
     *out = nullptr;
-    if (ndim != 2 && ndim != 3) return nl_fail(err, errlen, NL_EINVAL, "ndim must be 2 or 3");
-    if (!spacing) return nl_fail(err, errlen, NL_EINVAL, "spacing is NULL");
-    for (int a = 0; a < ndim; ++a)
-        if (!(spacing[a] > 0.0) || !(spacing[a] < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "spacing must be positive and finite");
-    if (!(r > 0.0) || !(r < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "the radius must be positive and finite");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        (void)hipGetLastError();
-        return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but no HIP device is visible");
-    }
-    if (device < 0 || device >= count) return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but device %d does not exist", device);
+    if (int rc = stage_check_frame(ndim, spacing, 1, 1, 1, err, errlen)) return rc;
+    if (int rc = stage_check_positive(r, "the radius", err, errlen)) return rc;
+    if (int rc = stage_check_device(device, err, errlen)) return rc;
     nl_flow *f = new nl_flow();
-    f->device = device;
     f->ndim = ndim;
     f->r = r;
     for (int a = 0; a < ndim; ++a) f->sp.s[3 - ndim + a] = spacing[a];
-    auto fail = [&](int rc) { nl_flow_destroy(f); return rc; };
-#define FLOW_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); \
-        return fail(nl_fail(err, errlen, e_ == hipErrorOutOfMemory ? NL_ENOMEM : NL_EHIP, "%s: %s%s", #expr, hipGetErrorString(e_), \
-                            e_ == hipErrorOutOfMemory ? " [out of memory]" : "")); } } while (0)
-    FLOW_TRY(hipSetDevice(device));
-    FLOW_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
-    FLOW_TRY(hipEventCreate(&f->ev_a));
-    FLOW_TRY(hipEventCreate(&f->ev_b));
-    FLOW_TRY(hipMalloc((void **)&f->d_grid, sizeof(FlowGrid)));
-    FLOW_TRY(hipMalloc((void **)&f->d_start, (size_t)(FLOW_MAX_CELLS + 1) * 4));
-    FLOW_TRY(hipMalloc((void **)&f->d_cursor, (size_t)(FLOW_MAX_CELLS + 1) * 4));
-    FLOW_TRY(hipMalloc((void **)&f->d_found, 8));
-    FLOW_TRY(hipHostMalloc((void **)&f->h_found, 8, hipHostMallocDefault));
-#undef FLOW_TRY
+    if (int rc = stage_open(*f, device, true, err, errlen)) { nl_flow_destroy(f); return rc; }
+    STAGE_HIP(stage_alloc(&f->d_grid, 1, sizeof(FlowGrid)), nl_flow_destroy(f));
+    STAGE_HIP(stage_alloc(&f->d_start, FLOW_MAX_CELLS + 1, 4), nl_flow_destroy(f));
+    STAGE_HIP(stage_alloc(&f->d_cursor, FLOW_MAX_CELLS + 1, 4), nl_flow_destroy(f));
+    STAGE_HIP(stage_alloc(&f->d_found, 1, 8), nl_flow_destroy(f));
+    STAGE_HIP(hipHostMalloc((void **)&f->h_found, 8, hipHostMallocDefault), nl_flow_destroy(f));
     *out = f;
-    return NL_OK;
-}
-
-template <typename P> static int flow_grow(P **p, i64 have, i64 need, size_t elem, char *err, size_t errlen) {
-    if (need <= have) return NL_OK;
-    if (*p) NL_HIP(hipFree(*p));
-    *p = nullptr;
-    NL_HIP(hipMalloc((void **)p, (size_t)need * elem));
     return NL_OK;
 }
 
 // The rows of one time point and direction: check coordinates (n, ndim) in voxels (the row's position, forward; position +
 // vector, backward), vectors (n, ndim), costs (n), all float64.  They replace the rows loaded before and stay on the device.
 extern "C" int nl_flow_load(nl_flow *f, const double *coords, const double *vectors, const double *costs, int64_t n, char *err, size_t errlen) {
-    FLOW_ENTER(f);
+    STAGE_ENTER(f, "flow field");
     if (n < 0 || n > (i64)1 << 30) return nl_fail(err, errlen, NL_EINVAL, "row count must be 0 .. 2^30");
     if (n > 0 && (!coords || !vectors || !costs)) return nl_fail(err, errlen, NL_EINVAL, "NULL rows");
     f->n_rows = 0;
     if (n == 0) return NL_OK;
     const int D = f->ndim;
     const i64 W = 2 * D + 1;
-    if (n > f->row_cap) {
-        const i64 nc = n > 2 * f->row_cap ? n : 2 * f->row_cap;
-        const i64 have = f->row_cap;
-        f->row_cap = 0;
-        if (int rc = flow_grow(&f->d_in, have * W, nc * W, 8, err, errlen)) return rc;
-        if (int rc = flow_grow(&f->d_cell, have, nc, 4, err, errlen)) return rc;
-        if (int rc = flow_grow(&f->d_perm, have, nc, 4, err, errlen)) return rc;
-        if (int rc = flow_grow(&f->d_rows, have, nc, sizeof(FlowRow), err, errlen)) return rc;
-        f->row_cap = nc;
-    }
+    if (int rc = stage_grow(&f->row_cap, n, stage_doubled(f->row_cap, n),
+                            {{&f->d_in, (size_t)W * 8}, {&f->d_cell, 4}, {&f->d_perm, 4}, {&f->d_rows, sizeof(FlowRow)}}, err, errlen)) return rc;
     hipStream_t st = f->stream;
     double *d_c = f->d_in, *d_v = f->d_in + n * D, *d_k = f->d_in + 2 * n * D;
     NL_HIP(hipMemcpyAsync(d_c, coords, (size_t)n * D * 8, hipMemcpyHostToDevice, st));
@@ -133,7 +86,7 @@ extern "C" int nl_flow_load(nl_flow *f, const double *coords, const double *vect
 // Interpolates n query rows (n, ndim) float64 (voxels) into out (n, ndim) float64; a row without a neighbour (a NaN row
 // included) is NaN.  n_found = rows that found a neighbour.  Longer inputs run in chunks of FLOW_CHUNK rows.
 extern "C" int nl_flow_interpolate(nl_flow *f, const double *queries, int64_t n, double *out, int64_t *n_found, char *err, size_t errlen) {
-    FLOW_ENTER(f);
+    STAGE_ENTER(f, "flow field");
     if (n < 0) return nl_fail(err, errlen, NL_EINVAL, "negative query count");
     if (!n_found) return nl_fail(err, errlen, NL_EINVAL, "n_found is NULL");
     if (n > 0 && (!queries || !out)) return nl_fail(err, errlen, NL_EINVAL, "NULL queries or output");
@@ -147,30 +100,21 @@ extern "C" int nl_flow_interpolate(nl_flow *f, const double *queries, int64_t n,
         return NL_OK;
     }
     const i64 chunk = n < FLOW_CHUNK ? n : FLOW_CHUNK;
-    if (chunk > f->q_cap) {
-        const i64 have = f->q_cap;
-        f->q_cap = 0;
-        if (int rc = flow_grow(&f->d_q, have * D, chunk * D, 8, err, errlen)) return rc;
-        if (int rc = flow_grow(&f->d_out, have * D, chunk * D, 8, err, errlen)) return rc;
-        f->q_cap = chunk;
-    }
+    if (int rc = stage_grow(&f->q_cap, chunk, chunk, {{&f->d_q, (size_t)D * 8}, {&f->d_out, (size_t)D * 8}}, err, errlen)) return rc;
     hipStream_t st = f->stream;
     NL_HIP(hipMemsetAsync(f->d_found, 0, 8, st));
     const double r2 = f->r * f->r;
     for (i64 at = 0; at < n; at += chunk) {
         const i64 m = n - at < chunk ? n - at : chunk;
         NL_HIP(hipMemcpyAsync(f->d_q, queries + at * D, (size_t)m * D * 8, hipMemcpyHostToDevice, st));
-        NL_HIP(hipEventRecord(f->ev_a, st));
+        if (int rc = stage_start(*f, err, errlen)) return rc;
         const unsigned g = (unsigned)((m + 255) / 256);
         if (D == 3) flow_interp_kernel<3><<<g, 256, 0, st>>>(f->d_q, m, f->d_rows, f->d_start, f->d_grid, f->sp, r2, f->d_out, f->d_found);
         else flow_interp_kernel<2><<<g, 256, 0, st>>>(f->d_q, m, f->d_rows, f->d_start, f->d_grid, f->sp, r2, f->d_out, f->d_found);
         NL_CHECK_LAUNCH();
-        NL_HIP(hipEventRecord(f->ev_b, st));
+        if (int rc = stage_stop_record(*f, err, errlen)) return rc;
         NL_HIP(hipMemcpyAsync(out + at * D, f->d_out, (size_t)m * D * 8, hipMemcpyDeviceToHost, st));
-        NL_HIP(hipStreamSynchronize(st));
-        float ms = 0.f;
-        NL_HIP(hipEventElapsedTime(&ms, f->ev_a, f->ev_b));
-        f->kernel_ms += ms;
+        if (int rc = stage_stop_wait(*f, &f->kernel_ms, err, errlen)) return rc;
     }
     NL_HIP(hipMemcpyAsync(f->h_found, f->d_found, 8, hipMemcpyDeviceToHost, st));
     NL_HIP(hipStreamSynchronize(st));
@@ -182,7 +126,7 @@ extern "C" int nl_flow_interpolate(nl_flow *f, const double *queries, int64_t n,
 // d_out, in one launch, nothing crosses the host.  The caller's work on d_queries must be complete; the call returns when d_out
 // is.  With no rows loaded nothing is written and n_found = 0.
 extern "C" int nl_flow_interpolate_dev(nl_flow *f, const double *d_queries, int64_t n, double *d_out, int64_t *n_found, char *err, size_t errlen) {
-    FLOW_ENTER(f);
+    STAGE_ENTER(f, "flow field");
     if (n < 0 || n > (i64)1 << 31) return nl_fail(err, errlen, NL_EINVAL, "query count must be 0 .. 2^31");
     if (!n_found) return nl_fail(err, errlen, NL_EINVAL, "n_found is NULL");
     if (n > 0 && (!d_queries || !d_out)) return nl_fail(err, errlen, NL_EINVAL, "NULL queries or output");
@@ -192,15 +136,14 @@ extern "C" int nl_flow_interpolate_dev(nl_flow *f, const double *d_queries, int6
     hipStream_t st = f->stream;
     NL_HIP(hipMemsetAsync(f->d_found, 0, 8, st));
     const double r2 = f->r * f->r;
-    NL_HIP(hipEventRecord(f->ev_a, st));
+    if (int rc = stage_start(*f, err, errlen)) return rc;
     const unsigned g = (unsigned)((n + 255) / 256);
     if (f->ndim == 3) flow_interp_kernel<3><<<g, 256, 0, st>>>(d_queries, n, f->d_rows, f->d_start, f->d_grid, f->sp, r2, d_out, f->d_found);
     else flow_interp_kernel<2><<<g, 256, 0, st>>>(d_queries, n, f->d_rows, f->d_start, f->d_grid, f->sp, r2, d_out, f->d_found);
     NL_CHECK_LAUNCH();
-    NL_HIP(hipEventRecord(f->ev_b, st));
+    if (int rc = stage_stop_record(*f, err, errlen)) return rc;
     NL_HIP(hipMemcpyAsync(f->h_found, f->d_found, 8, hipMemcpyDeviceToHost, st));
-    NL_HIP(hipStreamSynchronize(st));
-    NL_HIP(hipEventElapsedTime(&f->kernel_ms, f->ev_a, f->ev_b));
+    if (int rc = stage_stop_wait(*f, &f->kernel_ms, err, errlen)) return rc;
     *n_found = (int64_t)*f->h_found;
     return NL_OK;
 }

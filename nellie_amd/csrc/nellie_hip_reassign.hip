@@ -3,15 +3,11 @@
 // device; the flow vectors come from two flow fields (nellie_hip_flow.hip) through nl_flow_interpolate_dev, device to device.
 #include <algorithm>
 #include <math.h>
-#include "nl_host.h"
+#include "nl_stage.h"
 #include "reassign.inc"
 
 #define RA_MAX_OFFSETS ((i64)1 << 22)
 #define RA_MAX_ROWS ((i64)1 << 30)          // labelled voxels per frame: ranks, candidate ids and their sums are ints
-
-struct nl_flow;
-extern "C" int nl_flow_interpolate_dev(nl_flow *f, const double *d_queries, int64_t n, double *d_out, int64_t *n_found, char *err, size_t errlen);
-extern "C" int nl_flow_kernel_ms(nl_flow *f, float *ms, char *err, size_t errlen);
 
 struct RaSlot {                       // one frame
     i64 n = 0, cap = 0;               // labelled voxels
@@ -21,17 +17,15 @@ struct RaSlot {                       // one frame
     int *lab_b = nullptr, *lab_o = nullptr, *re_b = nullptr, *re_o = nullptr;
 };
 
-struct nl_reassign {
-    int device = 0, ndim = 3;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+struct nl_reassign : StageBase {
+    int ndim = 3;
     RaGeom g{};
     double r = 0.5, half_diag = 0.0;
-    i64 words = 0;                    // mask words per frame (a multiple of 4: one workgroup of ra_mask_kernel writes 4)
+    i64 words = 0;                    // mask words per frame (a multiple of 4: one workgroup of rank_mask_kernel writes 4)
     RaOffset *d_table = nullptr; int ntab = 0;
     int *d_branch = nullptr, *d_obj = nullptr;       // the frame being loaded
     int *d_wcount = nullptr;
-    i64 *d_bsum = nullptr, *d_total = nullptr, *h_total = nullptr;
+    RankScan scan;
     RaSlot slot[2]; int cur = 0, frames = 0;
     // temporaries of a pair
     double *d_q = nullptr, *d_v = nullptr; i64 q_cap = 0;
@@ -42,30 +36,12 @@ struct nl_reassign {
     float kernel_ms = 0.f;
 };
 
-#define RA_ENTER(h)                                                        \
-    if (!(h)) return nl_fail(err, errlen, NL_EINVAL, "reassigner is NULL"); \
-    NL_HIP(hipSetDevice((h)->device));
-
-static void ra_free_slot(RaSlot &s) {
-    void *ps[] = {s.bits, s.pre, s.vox, s.lab_b, s.lab_o, s.re_b, s.re_o};
-    for (void *p : ps) if (p) hipFree(p);
-    s = RaSlot();
-}
-
 extern "C" int nl_reassign_destroy(nl_reassign *h) {
     if (!h) return NL_OK;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    ra_free_slot(h->slot[0]);
-    ra_free_slot(h->slot[1]);
-    void *ps[] = {h->d_table, h->d_branch, h->d_obj, h->d_wcount, h->d_bsum, h->d_total, h->d_q, h->d_v, h->d_fw_match, h->d_bw_match,
-                  h->d_fw_d, h->d_bw_d, h->d_cnt, h->d_start, h->d_cursor, h->d_best, h->d_ent};
-    for (void *p : ps) if (p) hipFree(p);
-    if (h->h_total) hipHostFree(h->h_total);
-    if (h->ev_a) hipEventDestroy(h->ev_a);
-    if (h->ev_b) hipEventDestroy(h->ev_b);
-    if (h->stream) hipStreamDestroy(h->stream);
-    (void)hipGetLastError();
+    std::vector<void *> ps = {h->d_table, h->d_branch, h->d_obj, h->d_wcount, h->scan.d_bsum, h->scan.d_total, h->d_q, h->d_v, h->d_fw_match,
+                              h->d_bw_match, h->d_fw_d, h->d_bw_d, h->d_cnt, h->d_start, h->d_cursor, h->d_best, h->d_ent};
+    for (const RaSlot &s : h->slot) ps.insert(ps.end(), {s.bits, s.pre, s.vox, s.lab_b, s.lab_o, s.re_b, s.re_o});
+    stage_close(*h, ps, {h->scan.h_total});
     delete h;
     return NL_OK;
 }
@@ -100,19 +76,9 @@ extern "C" int nl_reassign_create(nl_reassign **out, int device, int ndim, int64
                                   char *err, size_t errlen) {
     if (!out) return nl_fail(err, errlen, NL_EINVAL, "out is NULL");
     *out = nullptr;
-    if (ndim != 2 && ndim != 3) return nl_fail(err, errlen, NL_EINVAL, "ndim must be 2 or 3");
-    if (!spacing) return nl_fail(err, errlen, NL_EINVAL, "spacing is NULL");
-    if (nz < 1 || ny < 1 || nx < 1 || (ndim == 2 && nz != 1)) return nl_fail(err, errlen, NL_EINVAL, "bad frame shape");
-    if ((double)nz * (double)ny * (double)nx > 9e15) return nl_fail(err, errlen, NL_EINVAL, "frame too large");
-    for (int a = 0; a < ndim; ++a)
-        if (!(spacing[a] > 0.0) || !(spacing[a] < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "spacing must be positive and finite");
-    if (!(r > 0.0) || !(r < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "the radius must be positive and finite");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        (void)hipGetLastError();
-        return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but no HIP device is visible");
-    }
-    if (device < 0 || device >= count) return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but device %d does not exist", device);
+    if (int rc = stage_check_frame(ndim, spacing, nz, ny, nx, err, errlen)) return rc;
+    if (int rc = stage_check_positive(r, "the radius", err, errlen)) return rc;
+    if (int rc = stage_check_device(device, err, errlen)) return rc;
     double s[3] = {1.0, 1.0, 1.0};
     for (int a = 0; a < ndim; ++a) s[3 - ndim + a] = spacing[a];
     double diag2 = 0.0;
@@ -122,7 +88,6 @@ extern "C" int nl_reassign_create(nl_reassign **out, int device, int ndim, int64
     if (!ra_offsets(ndim, s, r + diag, table))
         return nl_fail(err, errlen, NL_EINVAL, "the radius spans too many voxels (more than %lld lattice offsets)", (long long)RA_MAX_OFFSETS);
     nl_reassign *h = new nl_reassign();
-    h->device = device;
     h->ndim = ndim;
     h->r = r;
     h->half_diag = 0.5 * diag;
@@ -130,62 +95,28 @@ extern "C" int nl_reassign_create(nl_reassign **out, int device, int ndim, int64
     for (int a = 0; a < 3; ++a) h->g.s[a] = s[a];
     h->words = ((h->g.n + 255) / 256) * 4;
     h->ntab = (int)table.size();
-    auto fail = [&](int rc) { nl_reassign_destroy(h); return rc; };
-#define RA_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); \
-        return fail(nl_fail(err, errlen, e_ == hipErrorOutOfMemory ? NL_ENOMEM : NL_EHIP, "%s: %s%s", #expr, hipGetErrorString(e_), \
-                            e_ == hipErrorOutOfMemory ? " [out of memory]" : "")); } } while (0)
-    RA_TRY(hipSetDevice(device));
-    RA_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    RA_TRY(hipEventCreate(&h->ev_a));
-    RA_TRY(hipEventCreate(&h->ev_b));
-    RA_TRY(hipMalloc((void **)&h->d_table, table.size() * sizeof(RaOffset)));
-    RA_TRY(hipMemcpy(h->d_table, table.data(), table.size() * sizeof(RaOffset), hipMemcpyHostToDevice));
-    RA_TRY(hipMalloc((void **)&h->d_branch, (size_t)h->g.n * 4));
-    RA_TRY(hipMalloc((void **)&h->d_obj, (size_t)h->g.n * 4));
-    RA_TRY(hipMalloc((void **)&h->d_wcount, (size_t)h->words * 4));
-    RA_TRY(hipMalloc((void **)&h->d_total, 8));
-    RA_TRY(hipHostMalloc((void **)&h->h_total, 8, hipHostMallocDefault));
+    if (int rc = stage_open(*h, device, true, err, errlen)) { nl_reassign_destroy(h); return rc; }
+    STAGE_HIP(stage_alloc(&h->d_table, (i64)table.size(), sizeof(RaOffset)), nl_reassign_destroy(h));
+    STAGE_HIP(hipMemcpy(h->d_table, table.data(), table.size() * sizeof(RaOffset), hipMemcpyHostToDevice), nl_reassign_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_branch, h->g.n, 4), nl_reassign_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_obj, h->g.n, 4), nl_reassign_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_wcount, h->words, 4), nl_reassign_destroy(h));
+    // the workgroup sums are sized once for the longest scan a frame of this shape can ask for
+    STAGE_HIP(stage_alloc(&h->scan.d_bsum, rank_scan_sums(h->words > h->g.n ? h->words : h->g.n), 8), nl_reassign_destroy(h));
+    STAGE_HIP(stage_alloc(&h->scan.d_total, 1, 8), nl_reassign_destroy(h));
+    STAGE_HIP(hipHostMalloc((void **)&h->scan.h_total, 8, hipHostMallocDefault), nl_reassign_destroy(h));
     for (RaSlot &sl : h->slot) {
-        RA_TRY(hipMalloc((void **)&sl.bits, (size_t)h->words * 8));
-        RA_TRY(hipMalloc((void **)&sl.pre, (size_t)h->words * 4));
+        STAGE_HIP(stage_alloc(&sl.bits, h->words, 8), nl_reassign_destroy(h));
+        STAGE_HIP(stage_alloc(&sl.pre, h->words, 4), nl_reassign_destroy(h));
     }
-#undef RA_TRY
     *out = h;
-    return NL_OK;
-}
-
-template <typename P> static int ra_grow(P **p, i64 need, size_t elem, char *err, size_t errlen) {
-    if (*p) NL_HIP(hipFree(*p));
-    *p = nullptr;
-    NL_HIP(hipMalloc((void **)p, (size_t)(need > 0 ? need : 1) * elem));
-    return NL_OK;
-}
-
-// Exclusive scan of cnt[0 .. m) into pre, the total into *total (an error above `limit`).  Synchronises the stream.
-static int ra_scan(nl_reassign *h, const int *cnt, i64 m, int *pre, i64 limit, const char *what, i64 *total, char *err, size_t errlen) {
-    const i64 nb = (m + RA_SCAN_CHUNK - 1) / RA_SCAN_CHUNK;
-    hipStream_t st = h->stream;
-    if (!h->d_bsum) {                                   // sized once for the longest scan a frame of this shape can ask for
-        const i64 longest = h->words > h->g.n ? h->words : h->g.n;
-        if (int rc = ra_grow(&h->d_bsum, (longest + RA_SCAN_CHUNK - 1) / RA_SCAN_CHUNK + 1, 8, err, errlen)) return rc;
-    }
-    ra_scan_sums_kernel<<<(unsigned)nb, 256, 0, st>>>(cnt, m, h->d_bsum);
-    NL_CHECK_LAUNCH();
-    ra_scan_top_kernel<<<1, 1024, 0, st>>>(h->d_bsum, nb, h->d_total);
-    NL_CHECK_LAUNCH();
-    NL_HIP(hipMemcpyAsync(h->h_total, h->d_total, 8, hipMemcpyDeviceToHost, st));
-    NL_HIP(hipStreamSynchronize(st));
-    *total = *h->h_total;
-    if (*total > limit) return nl_fail(err, errlen, NL_EINVAL, "more than %lld %s", (long long)limit, what);
-    ra_scan_write_kernel<<<(unsigned)nb, 256, 0, st>>>(cnt, m, h->d_bsum, pre);
-    NL_CHECK_LAUNCH();
     return NL_OK;
 }
 
 // The next frame of the stack: branch and object labels (int32, the frame's shape).  The frame loaded before becomes "prev".
 // seed != 0: its reassigned labels are its own labels (frame 0); otherwise they are 0 until nl_reassign_pair votes.
 extern "C" int nl_reassign_frame(nl_reassign *h, const int32_t *branch, const int32_t *obj, int seed, int64_t *n_vox, char *err, size_t errlen) {
-    RA_ENTER(h);
+    STAGE_ENTER(h, "reassigner");
     if (!branch || !obj || !n_vox) return nl_fail(err, errlen, NL_EINVAL, "NULL labels or n_vox");
     hipStream_t st = h->stream;
     const i64 n = h->g.n;
@@ -199,19 +130,11 @@ extern "C" int nl_reassign_frame(nl_reassign *h, const int32_t *branch, const in
     NL_HIP(hipMemcpyAsync(h->d_branch, branch, (size_t)n * 4, hipMemcpyHostToDevice, st));
     NL_HIP(hipMemcpyAsync(h->d_obj, obj, (size_t)n * 4, hipMemcpyHostToDevice, st));
     const unsigned gv = (unsigned)((n + 255) / 256);
-    ra_mask_kernel<<<gv, 256, 0, st>>>(h->d_branch, h->d_obj, n, s.bits, h->d_wcount);
+    rank_mask_kernel<<<gv, 256, 0, st>>>(RaLabelled{h->d_branch, h->d_obj}, n, s.bits, h->d_wcount);
     NL_CHECK_LAUNCH();
     i64 total = 0;
-    if (int rc = ra_scan(h, h->d_wcount, h->words, s.pre, RA_MAX_ROWS, "labelled voxels in one frame", &total, err, errlen)) return rc;
-    if (total > s.cap) {
-        s.cap = 0;
-        if (int rc = ra_grow(&s.vox, total, 8, err, errlen)) return rc;
-        if (int rc = ra_grow(&s.lab_b, total, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&s.lab_o, total, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&s.re_b, total, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&s.re_o, total, 4, err, errlen)) return rc;
-        s.cap = total;
-    }
+    if (int rc = rank_scan(h->scan, st, h->d_wcount, h->words, s.pre, RA_MAX_ROWS, "labelled voxels in one frame", &total, err, errlen)) return rc;
+    if (int rc = stage_grow(&s.cap, total, total, {{&s.vox, 8}, {&s.lab_b, 4}, {&s.lab_o, 4}, {&s.re_b, 4}, {&s.re_o, 4}}, err, errlen)) return rc;
     if (total > 0) {
         ra_compact_kernel<<<gv, 256, 0, st>>>(h->d_branch, h->d_obj, n, s.bits, s.pre, seed ? 1 : 0, s.vox, s.lab_b, s.lab_o, s.re_b, s.re_o);
         NL_CHECK_LAUNCH();
@@ -230,14 +153,10 @@ static int ra_direction(nl_reassign *h, nl_flow *flow, const RaSlot &q, const Ra
     const unsigned gq = (unsigned)((q.n + 255) / 256);
     int64_t found = 0;
     if (flow) {
-        NL_HIP(hipEventRecord(h->ev_a, st));
-        ra_coords_kernel<<<gq, 256, 0, st>>>(q.vox, q.n, h->g, h->ndim, h->d_q);
+        if (int rc = stage_start(*h, err, errlen)) return rc;
+        rank_coords_kernel<<<gq, 256, 0, st>>>(q.vox, q.n, h->g.ny, h->g.nx, h->ndim, h->d_q);
         NL_CHECK_LAUNCH();
-        NL_HIP(hipEventRecord(h->ev_b, st));
-        NL_HIP(hipStreamSynchronize(st));
-        float ms_q = 0.f;
-        NL_HIP(hipEventElapsedTime(&ms_q, h->ev_a, h->ev_b));
-        h->kernel_ms += ms_q;
+        if (int rc = stage_stop(*h, &h->kernel_ms, err, errlen)) return rc;      // the queries are complete before the field reads them
         if (int rc = nl_flow_interpolate_dev(flow, h->d_q, q.n, h->d_v, &found, err, errlen)) return rc;
         float ms = 0.f;
         if (int rc = nl_flow_kernel_ms(flow, &ms, err, errlen)) return rc;
@@ -248,23 +167,18 @@ static int ra_direction(nl_reassign *h, nl_flow *flow, const RaSlot &q, const Ra
         NL_HIP(hipMemsetAsync(match, 0xff, (size_t)q.n * 4, st));
         return NL_OK;
     }
-    NL_HIP(hipEventRecord(h->ev_a, st));
+    if (int rc = stage_start(*h, err, errlen)) return rc;
     if (h->ndim == 3) ra_search_kernel<3><<<gq, 256, 0, st>>>(q.vox, q.n, h->d_v, sign, h->g, m.bits, m.pre, h->d_table, h->ntab, h->half_diag, h->r, match, dist);
     else ra_search_kernel<2><<<gq, 256, 0, st>>>(q.vox, q.n, h->d_v, sign, h->g, m.bits, m.pre, h->d_table, h->ntab, h->half_diag, h->r, match, dist);
     NL_CHECK_LAUNCH();
-    NL_HIP(hipEventRecord(h->ev_b, st));
-    NL_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    NL_HIP(hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    h->kernel_ms += ms;
-    return NL_OK;
+    return stage_stop(*h, &h->kernel_ms, err, errlen);
 }
 
 // Matches the last two frames: forward candidates from the flow field `fw` (rows of t loaded), backward ones from `bw` (rows of
 // t + 1 loaded); a NULL field gives no candidates of its direction.  Then the best pair and the two votes per voxel of the
 // later frame, whose reassigned labels are written.  n_candidates = 0: no candidate at all (the caller's loop stops).
 extern "C" int nl_reassign_pair(nl_reassign *h, nl_flow *fw, nl_flow *bw, int64_t *n_candidates, char *err, size_t errlen) {
-    RA_ENTER(h);
+    STAGE_ENTER(h, "reassigner");
     if (!n_candidates) return nl_fail(err, errlen, NL_EINVAL, "n_candidates is NULL");
     *n_candidates = 0;
     if (h->frames < 2) return nl_fail(err, errlen, NL_ESTATE, "nl_reassign_pair needs two frames");
@@ -275,46 +189,20 @@ extern "C" int nl_reassign_pair(nl_reassign *h, nl_flow *fw, nl_flow *bw, int64_
     hipStream_t st = h->stream;
     const i64 n0 = pv.n, n1 = nx.n, big = n0 > n1 ? n0 : n1;
     const int D = h->ndim;
-    if (big > h->q_cap) {
-        h->q_cap = 0;
-        if (int rc = ra_grow(&h->d_q, big * D, 8, err, errlen)) return rc;
-        if (int rc = ra_grow(&h->d_v, big * D, 8, err, errlen)) return rc;
-        h->q_cap = big;
-    }
-    if (n0 > h->fw_cap) {
-        h->fw_cap = 0;
-        if (int rc = ra_grow(&h->d_fw_match, n0, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&h->d_fw_d, n0, 4, err, errlen)) return rc;
-        h->fw_cap = n0;
-    }
-    if (n1 > h->bw_cap) {
-        h->bw_cap = 0;
-        if (int rc = ra_grow(&h->d_bw_match, n1, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&h->d_bw_d, n1, 4, err, errlen)) return rc;
-        h->bw_cap = n1;
-    }
-    if (n1 > h->t_cap) {
-        h->t_cap = 0;
-        if (int rc = ra_grow(&h->d_cnt, n1, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&h->d_start, n1, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&h->d_cursor, n1, 4, err, errlen)) return rc;
-        if (int rc = ra_grow(&h->d_best, n1, 4, err, errlen)) return rc;
-        h->t_cap = n1;
-    }
-    if (n0 + n1 > h->ent_cap) {
-        h->ent_cap = 0;
-        if (int rc = ra_grow(&h->d_ent, n0 + n1, 4, err, errlen)) return rc;
-        h->ent_cap = n0 + n1;
-    }
+    if (int rc = stage_grow(&h->q_cap, big, big, {{&h->d_q, (size_t)D * 8}, {&h->d_v, (size_t)D * 8}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->fw_cap, n0, n0, {{&h->d_fw_match, 4}, {&h->d_fw_d, 4}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->bw_cap, n1, n1, {{&h->d_bw_match, 4}, {&h->d_bw_d, 4}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->t_cap, n1, n1, {{&h->d_cnt, 4}, {&h->d_start, 4}, {&h->d_cursor, 4}, {&h->d_best, 4}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->ent_cap, n0 + n1, n0 + n1, {{&h->d_ent, 4}}, err, errlen)) return rc;
     if (int rc = ra_direction(h, fw, pv, nx, 1.0, h->d_fw_match, h->d_fw_d, err, errlen)) return rc;
     if (int rc = ra_direction(h, bw, nx, pv, -1.0, h->d_bw_match, h->d_bw_d, err, errlen)) return rc;
     const unsigned gc = (unsigned)((n0 + n1 + 255) / 256), gt = (unsigned)((n1 + 255) / 256);
-    NL_HIP(hipEventRecord(h->ev_a, st));
+    if (int rc = stage_start(*h, err, errlen)) return rc;
     NL_HIP(hipMemsetAsync(h->d_cnt, 0, (size_t)n1 * 4, st));
     ra_count_kernel<<<gc, 256, 0, st>>>(h->d_fw_match, n0, h->d_bw_match, n1, h->d_cnt);
     NL_CHECK_LAUNCH();
     i64 total = 0;
-    if (int rc = ra_scan(h, h->d_cnt, n1, h->d_start, 2 * RA_MAX_ROWS - 1, "candidates in one frame pair", &total, err, errlen)) return rc;
+    if (int rc = rank_scan(h->scan, st, h->d_cnt, n1, h->d_start, 2 * RA_MAX_ROWS - 1, "candidates in one frame pair", &total, err, errlen)) return rc;
     *n_candidates = total;
     if (total == 0) return NL_OK;
     NL_HIP(hipMemcpyAsync(h->d_cursor, h->d_start, (size_t)n1 * 4, hipMemcpyDeviceToDevice, st));
@@ -323,11 +211,7 @@ extern "C" int nl_reassign_pair(nl_reassign *h, nl_flow *fw, nl_flow *bw, int64_
     RaCand cd{h->d_fw_match, h->d_bw_match, h->d_fw_d, h->d_bw_d, (int)n0};
     ra_vote_kernel<<<gt, 256, 0, st>>>(n1, cd, h->d_start, h->d_cnt, h->d_ent, pv.re_b, pv.re_o, nx.lab_b, nx.lab_o, nx.re_b, nx.re_o, h->d_best);
     NL_CHECK_LAUNCH();
-    NL_HIP(hipEventRecord(h->ev_b, st));
-    NL_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    NL_HIP(hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    h->kernel_ms += ms;
+    if (int rc = stage_stop(*h, &h->kernel_ms, err, errlen)) return rc;
     h->has_best = true;
     return NL_OK;
 }
@@ -337,7 +221,7 @@ extern "C" int nl_reassign_pair(nl_reassign *h, nl_flow *fw, nl_flow *bw, int64_
 // of the best pair's source among the voxels of the frame before, -1 without a candidate.  NULL pointers are skipped.
 extern "C" int nl_reassign_fetch(nl_reassign *h, int which, int64_t *vox, int32_t *re_branch, int32_t *re_obj, int32_t *best_src,
                                  char *err, size_t errlen) {
-    RA_ENTER(h);
+    STAGE_ENTER(h, "reassigner");
     if (which != 0 && which != 1) return nl_fail(err, errlen, NL_EINVAL, "which must be 0 or 1");
     if (h->frames < 1 + which) return nl_fail(err, errlen, NL_ESTATE, "no such frame");
     if (best_src && (which != 0 || !h->has_best)) return nl_fail(err, errlen, NL_ESTATE, "no best pairs to fetch");

@@ -1,6 +1,6 @@
 // Translation unit of libnellie_hip.so (gfx950): Hu-moment marker tracking (nellie/tracking/hu_tracking.py).  C-ABI in
 // include/nellie_amd.h; kernels in track.inc.  A tracker owns its buffers and stream: it needs none of a Filter context's volumes.
-#include "nl_host.h"
+#include "nl_stage.h"
 #include "track.inc"
 
 struct TrkSlot {
@@ -12,11 +12,10 @@ struct TrkSlot {
     i64 n = 0, cap = 0;
 };
 
-struct nl_track {
-    int device = 0, two_d = 0;
-    hipStream_t stream = nullptr;
+struct nl_track : StageBase {      // times nothing: no event pair
+    int two_d = 0;
     i64 nz = 0, ny = 0, nx = 0, n = 0;
-    void *d_int = nullptr; size_t int_bytes = 0;
+    void *d_int = nullptr; i64 int_bytes = 0;
     float *d_fr = nullptr, *d_dist = nullptr;
     uint8_t *d_mk = nullptr;
     unsigned int *d_blk = nullptr;
@@ -29,49 +28,11 @@ struct nl_track {
     int *d_idx = nullptr; float *d_val = nullptr; i64 res_cap = 0;   // row results | column results
 };
 
-#define TRK_ENTER(t)                                                   \
-    if (!(t)) return nl_fail(err, errlen, NL_EINVAL, "tracker is NULL"); \
-    NL_HIP(hipSetDevice((t)->device));
-
-template <typename P> static int trk_grow(P **p, i64 *cap, i64 need, size_t elem, char *err, size_t errlen) {
-    if (need <= *cap) return NL_OK;
-    const i64 nc = need > 2 * *cap ? need : 2 * *cap;
-    if (*p) NL_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    NL_HIP(hipMalloc((void **)p, (size_t)nc * elem));
-    *cap = nc;
-    return NL_OK;
-}
-
-static int slot_grow(TrkSlot &s, i64 need, char *err, size_t errlen) {
-    if (need <= s.cap) return NL_OK;
-    const i64 nc = need > 2 * s.cap ? need : 2 * s.cap;
-    void **ps[5] = {(void **)&s.coord, (void **)&s.phys, (void **)&s.rad, (void **)&s.stats, (void **)&s.hu};
-    const size_t el[5] = {12, 24, 4, 16, 8 * TRK_NH_MAX};
-    for (int k = 0; k < 5; ++k) {
-        if (*ps[k]) NL_HIP(hipFree(*ps[k]));
-        *ps[k] = nullptr;
-    }
-    s.cap = 0;
-    for (int k = 0; k < 5; ++k) NL_HIP(hipMalloc(ps[k], (size_t)nc * el[k]));
-    s.cap = nc;
-    return NL_OK;
-}
-
 extern "C" int nl_track_destroy(nl_track *t) {
     if (!t) return NL_OK;
-    hipSetDevice(t->device);
-    if (t->stream) hipStreamSynchronize(t->stream);
-    void *ps[] = {t->d_int, t->d_fr, t->d_dist, t->d_mk, t->d_blk, t->d_small, t->d_scale, t->d_part, t->d_mom, t->d_idx, t->d_val};
-    for (void *p : ps) if (p) hipFree(p);
-    for (auto &s : t->slot) {
-        void *qs[] = {s.coord, s.phys, s.rad, s.stats, s.hu};
-        for (void *p : qs) if (p) hipFree(p);
-    }
-    if (t->h_small) hipHostFree(t->h_small);
-    if (t->stream) hipStreamDestroy(t->stream);
-    (void)hipGetLastError();
+    std::vector<void *> ps = {t->d_int, t->d_fr, t->d_dist, t->d_mk, t->d_blk, t->d_small, t->d_scale, t->d_part, t->d_mom, t->d_idx, t->d_val};
+    for (const TrkSlot &s : t->slot) ps.insert(ps.end(), {s.coord, s.phys, s.rad, s.stats, s.hu});
+    stage_close(*t, ps, {t->h_small});
     delete t;
     return NL_OK;
 }
@@ -80,38 +41,25 @@ extern "C" int nl_track_create(nl_track **out, int device, int ndim, int64_t nz,
                                char *err, size_t errlen) {
     if (!out) return nl_fail(err, errlen, NL_EINVAL, "out is NULL");
     *out = nullptr;
-    if (ndim != 2 && ndim != 3) return nl_fail(err, errlen, NL_EINVAL, "ndim must be 2 or 3");
     if (ndim == 2) nz = 1;
-    if (nz < 1 || ny < 1 || nx < 1 || ny > INT32_MAX || nx > INT32_MAX || nz > INT32_MAX || nz * ny * nx > ((i64)1 << 40))
-        return nl_fail(err, errlen, NL_EINVAL, "bad frame shape");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        (void)hipGetLastError();
-        return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but no HIP device is visible");
-    }
-    if (device < 0 || device >= count) return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but device %d does not exist", device);
+    if (int rc = stage_check_frame(ndim, spacing, nz, ny, nx, err, errlen)) return rc;
+    if (ny > INT32_MAX || nx > INT32_MAX || nz > INT32_MAX || nz * ny * nx > ((i64)1 << 40)) return nl_fail(err, errlen, NL_EINVAL, "bad frame shape");
+    if (int rc = stage_check_device(device, err, errlen)) return rc;
     nl_track *t = new nl_track();
-    t->device = device;
     t->two_d = ndim == 2;
     t->nz = nz; t->ny = ny; t->nx = nx; t->n = nz * ny * nx;
-    auto fail = [&](int rc) { nl_track_destroy(t); return rc; };
-#define TRK_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); \
-        return fail(nl_fail(err, errlen, e_ == hipErrorOutOfMemory ? NL_ENOMEM : NL_EHIP, "%s: %s%s", #expr, hipGetErrorString(e_), \
-                            e_ == hipErrorOutOfMemory ? " [out of memory]" : "")); } } while (0)
-    TRK_TRY(hipSetDevice(device));
-    TRK_TRY(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    if (int rc = stage_open(*t, device, false, err, errlen)) { nl_track_destroy(t); return rc; }
     const i64 nblk = (t->n + TRK_CHUNK - 1) / TRK_CHUNK;
-    TRK_TRY(hipMalloc((void **)&t->d_fr, (size_t)t->n * 4));
-    TRK_TRY(hipMalloc((void **)&t->d_dist, (size_t)t->n * 4));
-    TRK_TRY(hipMalloc((void **)&t->d_mk, (size_t)t->n));
-    TRK_TRY(hipMalloc((void **)&t->d_blk, (size_t)nblk * 4));
-    TRK_TRY(hipMalloc((void **)&t->d_small, 64));
-    TRK_TRY(hipHostMalloc((void **)&t->h_small, 64, hipHostMallocDefault));
-    TRK_TRY(hipMalloc((void **)&t->d_scale, 24));
-    TRK_TRY(hipMalloc((void **)&t->d_mom, 2 * TRK_NF_MAX * 8));
+    STAGE_HIP(stage_alloc(&t->d_fr, t->n, 4), nl_track_destroy(t));
+    STAGE_HIP(stage_alloc(&t->d_dist, t->n, 4), nl_track_destroy(t));
+    STAGE_HIP(stage_alloc(&t->d_mk, t->n, 1), nl_track_destroy(t));
+    STAGE_HIP(stage_alloc(&t->d_blk, nblk, 4), nl_track_destroy(t));
+    STAGE_HIP(stage_alloc(&t->d_small, 16, 4), nl_track_destroy(t));
+    STAGE_HIP(hipHostMalloc((void **)&t->h_small, 64, hipHostMallocDefault), nl_track_destroy(t));
+    STAGE_HIP(stage_alloc(&t->d_scale, 3, 8), nl_track_destroy(t));
+    STAGE_HIP(stage_alloc(&t->d_mom, 2 * TRK_NF_MAX, 8), nl_track_destroy(t));
     double sc[3] = {ndim == 2 ? 1.0 : spacing[0], spacing[ndim == 2 ? 0 : 1], spacing[ndim == 2 ? 1 : 2]};
-    TRK_TRY(hipMemcpy(t->d_scale, sc, 24, hipMemcpyHostToDevice));
-#undef TRK_TRY
+    STAGE_HIP(hipMemcpy(t->d_scale, sc, 24, hipMemcpyHostToDevice), nl_track_destroy(t));
     *out = t;
     return NL_OK;
 }
@@ -119,17 +67,12 @@ extern "C" int nl_track_create(nl_track **out, int device, int ndim, int64_t nz,
 // Uploads one frame, computes its features into the current slot; the previous frame's features stay resident as "pre".
 extern "C" int nl_track_frame(nl_track *t, const void *intensity, int dtype, const float *frangi, const float *distance,
                               const uint8_t *marker, int64_t *n_markers, char *err, size_t errlen) {
-    TRK_ENTER(t);
+    STAGE_ENTER(t, "tracker");
     if (!intensity || !frangi || !distance || !marker) return nl_fail(err, errlen, NL_EINVAL, "NULL frame");
     if (dtype != NL_U8 && dtype != NL_U16 && dtype != NL_F32)
         return nl_fail(err, errlen, NL_EINVAL, "tracking intensities must be uint8, uint16 or float32 (dtype code %d)", dtype);
     const size_t esz = dtype_size(dtype);
-    if (t->int_bytes < (size_t)t->n * esz) {
-        if (t->d_int) NL_HIP(hipFree(t->d_int));
-        t->d_int = nullptr; t->int_bytes = 0;
-        NL_HIP(hipMalloc(&t->d_int, (size_t)t->n * esz));
-        t->int_bytes = (size_t)t->n * esz;
-    }
+    if (int rc = stage_grow(&t->int_bytes, t->n * (i64)esz, t->n * (i64)esz, {{&t->d_int, 1}}, err, errlen)) return rc;
     hipStream_t st = t->stream;
     NL_HIP(hipMemcpyAsync(t->d_int, intensity, (size_t)t->n * esz, hipMemcpyHostToDevice, st));
     NL_HIP(hipMemcpyAsync(t->d_fr, frangi, (size_t)t->n * 4, hipMemcpyHostToDevice, st));
@@ -151,7 +94,8 @@ extern "C" int nl_track_frame(nl_track *t, const void *intensity, int dtype, con
     s.n = 0;
     *n_markers = n;
     if (n == 0) return NL_OK;
-    if (int rc = slot_grow(s, n, err, errlen)) return rc;
+    if (int rc = stage_grow(&s.cap, n, stage_doubled(s.cap, n), {{&s.coord, 12}, {&s.phys, 24}, {&s.rad, 4}, {&s.stats, 16}, {&s.hu, 8 * TRK_NH_MAX}},
+                            err, errlen)) return rc;
     trk_mark_write_kernel<<<(unsigned)nblk, 256, 0, st>>>(t->d_mk, t->n, t->d_blk, s.coord, (int)t->ny, (int)t->nx);
     NL_CHECK_LAUNCH();
     trk_frangi_log_kernel<<<grid1d(t->n), 256, 0, st>>>(t->d_fr, t->n, t->d_small + 1);
@@ -182,7 +126,7 @@ extern "C" int nl_track_frame(nl_track *t, const void *intensity, int dtype, con
 // Downloads a slot's features (which = 0: the last frame, 1: the one before): coords (n, ndim) int64, stats (n, 4) float32,
 // log-Hu (n, 6 | 18) float64.  NULL pointers are skipped.
 extern "C" int nl_track_features(nl_track *t, int which, int64_t *coords, float *stats, double *hu, char *err, size_t errlen) {
-    TRK_ENTER(t);
+    STAGE_ENTER(t, "tracker");
     if (which != 0 && which != 1) return nl_fail(err, errlen, NL_EINVAL, "which must be 0 or 1");
     if (which == 1 && t->frames < 2) return nl_fail(err, errlen, NL_ESTATE, "no previous frame");
     TrkSlot &s = t->slot[which == 0 ? t->cur : t->cur ^ 1];
@@ -207,7 +151,7 @@ extern "C" int nl_track_features(nl_track *t, int which, int64_t *coords, float 
 // the (n_post, n_pre) float16 cost matrix.
 extern "C" int nl_track_match(nl_track *t, int mode, double max_distance, int32_t *row_idx, float *row_cost, int32_t *col_idx,
                               float *col_cost, uint16_t *full, char *err, size_t errlen) {
-    TRK_ENTER(t);
+    STAGE_ENTER(t, "tracker");
     if (t->frames < 2) return nl_fail(err, errlen, NL_ESTATE, "nl_track_match needs two frames");
     if (mode != 0 && mode != 1) return nl_fail(err, errlen, NL_EINVAL, "mode must be 0 (dense) or 1 (sparse)");
     if (mode == 1 && full) return nl_fail(err, errlen, NL_EINVAL, "the full cost matrix is a dense-mode output");
@@ -217,12 +161,8 @@ extern "C" int nl_track_match(nl_track *t, int mode, double max_distance, int32_
     TrkPair P{(int)a.n, (int)b.n, t->two_d ? 2 : 3, nh, a.phys, b.phys, a.stats, b.stats, a.hu, b.hu, max_distance};
     hipStream_t st = t->stream;
     const i64 pw = mode == 0 ? 1 + nf : 1 + 2 * nf;
-    if (int rc = trk_grow(&t->d_part, &t->part_cap, a.n * pw, 8, err, errlen)) return rc;
-    i64 cap = t->res_cap;
-    if (int rc = trk_grow(&t->d_idx, &cap, a.n + b.n, 4, err, errlen)) return rc;
-    cap = t->res_cap;
-    if (int rc = trk_grow(&t->d_val, &cap, a.n + b.n, 4, err, errlen)) return rc;
-    t->res_cap = cap;
+    if (int rc = stage_grow(&t->part_cap, a.n * pw, stage_doubled(t->part_cap, a.n * pw), {{&t->d_part, 8}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&t->res_cap, a.n + b.n, stage_doubled(t->res_cap, a.n + b.n), {{&t->d_idx, 4}, {&t->d_val, 4}}, err, errlen)) return rc;
     uint16_t *d_full = nullptr;
     const unsigned gr = (unsigned)((a.n + 127) / 128), gc = (unsigned)((b.n + 127) / 128);
     if (mode == 0) {

@@ -3,29 +3,23 @@
 // device; the flow vectors come from two flow fields (nellie_hip_flow.hip) through nl_flow_interpolate_dev, device to device.
 #include <math.h>
 #include <string.h>
-#include "nl_host.h"
+#include "nl_stage.h"
 #include "voxfeat.inc"
 
 #define VF_MAX_ROWS ((i64)1 << 30)          // labelled voxels (and nodes) per frame: ranks are ints
 #define VF_MAX_PAIRS (((i64)1 << 31) - 1)   // (node, voxel) pairs per frame: CSR offsets are ints
 enum { VF_MS_LOAD, VF_MS_FLOW, VF_MS_PIVOT, VF_MS_MOTILITY, VF_MS_NODES, VF_MS_PARTS };
 
-struct nl_flow;
-extern "C" int nl_flow_interpolate_dev(nl_flow *f, const double *d_queries, int64_t n, double *d_out, int64_t *n_found, char *err, size_t errlen);
-extern "C" int nl_flow_kernel_ms(nl_flow *f, float *ms, char *err, size_t errlen);
-
-struct nl_voxfeat {
-    int device = 0, ndim = 3;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+struct nl_voxfeat : StageBase {
+    int ndim = 3;
     VfGeom g{};
-    i64 words = 0;                                  // mask words per frame (a multiple of 4: one workgroup of vf_mask_kernel writes 4)
+    i64 words = 0;                                  // mask words per frame (a multiple of 4: one workgroup of rank_mask_kernel writes 4)
     // the frame as uploaded (dense): labels, and two 8-byte-per-voxel buffers for raw / structure, then pixel class / distance
     int *d_comp = nullptr, *d_branch = nullptr;
     void *d_a = nullptr, *d_b = nullptr;
     u64 *bits = nullptr, *nbits = nullptr;          // masks: labelled voxels, nodes
     int *pre = nullptr, *npre = nullptr, *d_wcount = nullptr;
-    i64 *d_bsum = nullptr, *d_total = nullptr, *h_total = nullptr;
+    RankScan scan;
     int *d_maxlab = nullptr, *h_maxlab = nullptr;
     // labelled voxels
     i64 n = 0, cap = 0; int raw_size = 1, st_size = 1, nlab = 0; bool has_frame = false;
@@ -40,24 +34,12 @@ struct nl_voxfeat {
     float ms[VF_MS_PARTS] = {0.f, 0.f, 0.f, 0.f, 0.f};
 };
 
-#define VF_ENTER(h)                                                                  \
-    if (!(h)) return nl_fail(err, errlen, NL_EINVAL, "voxel-feature object is NULL"); \
-    NL_HIP(hipSetDevice((h)->device));
-
 extern "C" int nl_voxfeat_destroy(nl_voxfeat *h) {
     if (!h) return NL_OK;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    void *ps[] = {h->d_comp, h->d_branch, h->d_a, h->d_b, h->bits, h->nbits, h->pre, h->npre, h->d_wcount, h->d_bsum, h->d_total, h->d_maxlab,
-                  h->vox, h->lab_c, h->lab_b, h->raw_c, h->st_c, h->d_q, h->d_v01, h->d_v12, h->d_out, h->d_best, h->d_pivot, h->node_vox,
-                  h->lims, h->radius, h->ncount, h->nstart, h->vcount, h->vstart, h->cursor, h->node_val, h->vox_val};
-    for (void *p : ps) if (p) hipFree(p);
-    if (h->h_total) hipHostFree(h->h_total);
-    if (h->h_maxlab) hipHostFree(h->h_maxlab);
-    if (h->ev_a) hipEventDestroy(h->ev_a);
-    if (h->ev_b) hipEventDestroy(h->ev_b);
-    if (h->stream) hipStreamDestroy(h->stream);
-    (void)hipGetLastError();
+    stage_close(*h, {h->d_comp, h->d_branch, h->d_a, h->d_b, h->bits, h->nbits, h->pre, h->npre, h->d_wcount, h->scan.d_bsum, h->scan.d_total,
+                     h->d_maxlab, h->vox, h->lab_c, h->lab_b, h->raw_c, h->st_c, h->d_q, h->d_v01, h->d_v12, h->d_out, h->d_best, h->d_pivot,
+                     h->node_vox, h->lims, h->radius, h->ncount, h->nstart, h->vcount, h->vstart, h->cursor, h->node_val, h->vox_val},
+                {h->scan.h_total, h->h_maxlab});
     delete h;
     return NL_OK;
 }
@@ -66,87 +48,33 @@ extern "C" int nl_voxfeat_create(nl_voxfeat **out, int device, int ndim, int64_t
                                  char *err, size_t errlen) {
     if (!out) return nl_fail(err, errlen, NL_EINVAL, "out is NULL");
     *out = nullptr;
-    if (ndim != 2 && ndim != 3) return nl_fail(err, errlen, NL_EINVAL, "ndim must be 2 or 3");
-    if (!spacing) return nl_fail(err, errlen, NL_EINVAL, "spacing is NULL");
-    if (nz < 1 || ny < 1 || nx < 1 || (ndim == 2 && nz != 1)) return nl_fail(err, errlen, NL_EINVAL, "bad frame shape");
-    if ((double)nz * (double)ny * (double)nx > 9e15) return nl_fail(err, errlen, NL_EINVAL, "frame too large");
-    for (int a = 0; a < ndim; ++a)
-        if (!(spacing[a] > 0.0) || !(spacing[a] < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "spacing must be positive and finite");
-    if (!(dt > 0.0) || !(dt < 1e300)) return nl_fail(err, errlen, NL_EINVAL, "the time step must be positive and finite");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        (void)hipGetLastError();
-        return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but no HIP device is visible");
-    }
-    if (device < 0 || device >= count) return nl_fail(err, errlen, NL_ENODEV, "GPU backend requested but device %d does not exist", device);
+    if (int rc = stage_check_frame(ndim, spacing, nz, ny, nx, err, errlen)) return rc;
+    if (int rc = stage_check_positive(dt, "the time step", err, errlen)) return rc;
+    if (int rc = stage_check_device(device, err, errlen)) return rc;
     nl_voxfeat *h = new nl_voxfeat();
-    h->device = device;
     h->ndim = ndim;
     h->g.nz = nz; h->g.ny = ny; h->g.nx = nx; h->g.n = nz * ny * nx;
     for (int a = 0; a < 3; ++a) h->g.s[a] = a < ndim ? spacing[a] : 1.0;
     h->g.dt = dt;
     h->words = ((h->g.n + 255) / 256) * 4;
-    const i64 n = h->g.n, longest = h->words > n ? h->words : n;
-    auto fail = [&](int rc) { nl_voxfeat_destroy(h); return rc; };
-#define VF_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); \
-        return fail(nl_fail(err, errlen, e_ == hipErrorOutOfMemory ? NL_ENOMEM : NL_EHIP, "%s: %s%s", #expr, hipGetErrorString(e_), \
-                            e_ == hipErrorOutOfMemory ? " [out of memory]" : "")); } } while (0)
-    VF_TRY(hipSetDevice(device));
-    VF_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    VF_TRY(hipEventCreate(&h->ev_a));
-    VF_TRY(hipEventCreate(&h->ev_b));
-    VF_TRY(hipMalloc((void **)&h->d_comp, (size_t)n * 4));
-    VF_TRY(hipMalloc((void **)&h->d_branch, (size_t)n * 4));
-    VF_TRY(hipMalloc(&h->d_a, (size_t)n * 8));
-    VF_TRY(hipMalloc(&h->d_b, (size_t)n * 8));
-    VF_TRY(hipMalloc((void **)&h->bits, (size_t)h->words * 8));
-    VF_TRY(hipMalloc((void **)&h->nbits, (size_t)h->words * 8));
-    VF_TRY(hipMalloc((void **)&h->pre, (size_t)h->words * 4));
-    VF_TRY(hipMalloc((void **)&h->npre, (size_t)h->words * 4));
-    VF_TRY(hipMalloc((void **)&h->d_wcount, (size_t)h->words * 4));
-    VF_TRY(hipMalloc((void **)&h->d_bsum, (size_t)((longest + RA_SCAN_CHUNK - 1) / RA_SCAN_CHUNK + 1) * 8));
-    VF_TRY(hipMalloc((void **)&h->d_total, 8));
-    VF_TRY(hipMalloc((void **)&h->d_maxlab, 4));
-    VF_TRY(hipHostMalloc((void **)&h->h_total, 8, hipHostMallocDefault));
-    VF_TRY(hipHostMalloc((void **)&h->h_maxlab, 4, hipHostMallocDefault));
-#undef VF_TRY
+    const i64 n = h->g.n;
+    if (int rc = stage_open(*h, device, true, err, errlen)) { nl_voxfeat_destroy(h); return rc; }
+    STAGE_HIP(stage_alloc(&h->d_comp, n, 4), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_branch, n, 4), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_a, n, 8), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_b, n, 8), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->bits, h->words, 8), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->nbits, h->words, 8), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->pre, h->words, 4), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->npre, h->words, 4), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_wcount, h->words, 4), nl_voxfeat_destroy(h));
+    // the workgroup sums are sized once for the longest scan a frame of this shape can ask for
+    STAGE_HIP(stage_alloc(&h->scan.d_bsum, rank_scan_sums(h->words > n ? h->words : n), 8), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->scan.d_total, 1, 8), nl_voxfeat_destroy(h));
+    STAGE_HIP(stage_alloc(&h->d_maxlab, 1, 4), nl_voxfeat_destroy(h));
+    STAGE_HIP(hipHostMalloc((void **)&h->scan.h_total, 8, hipHostMallocDefault), nl_voxfeat_destroy(h));
+    STAGE_HIP(hipHostMalloc((void **)&h->h_maxlab, 4, hipHostMallocDefault), nl_voxfeat_destroy(h));
     *out = h;
-    return NL_OK;
-}
-
-template <typename P> static int vf_grow(P **p, i64 need, size_t elem, char *err, size_t errlen) {
-    if (*p) NL_HIP(hipFree(*p));
-    *p = nullptr;
-    NL_HIP(hipMalloc((void **)p, (size_t)(need > 0 ? need : 1) * elem));
-    return NL_OK;
-}
-
-// Exclusive scan of cnt[0 .. m) into pre, the total into *total (an error above `limit`).  Synchronises the stream.
-static int vf_scan(nl_voxfeat *h, const int *cnt, i64 m, int *pre, i64 limit, const char *what, i64 *total, char *err, size_t errlen) {
-    *total = 0;
-    if (m <= 0) return NL_OK;
-    const i64 nb = (m + RA_SCAN_CHUNK - 1) / RA_SCAN_CHUNK;
-    hipStream_t st = h->stream;
-    ra_scan_sums_kernel<<<(unsigned)nb, 256, 0, st>>>(cnt, m, h->d_bsum);
-    NL_CHECK_LAUNCH();
-    ra_scan_top_kernel<<<1, 1024, 0, st>>>(h->d_bsum, nb, h->d_total);
-    NL_CHECK_LAUNCH();
-    NL_HIP(hipMemcpyAsync(h->h_total, h->d_total, 8, hipMemcpyDeviceToHost, st));
-    NL_HIP(hipStreamSynchronize(st));
-    *total = *h->h_total;
-    if (*total > limit) return nl_fail(err, errlen, NL_EINVAL, "more than %lld %s", (long long)limit, what);
-    ra_scan_write_kernel<<<(unsigned)nb, 256, 0, st>>>(cnt, m, h->d_bsum, pre);
-    NL_CHECK_LAUNCH();
-    return NL_OK;
-}
-
-// ev_b is recorded now; the time since ev_a goes to part `which`.  Synchronises the stream.
-static int vf_stop(nl_voxfeat *h, int which, char *err, size_t errlen) {
-    NL_HIP(hipEventRecord(h->ev_b, h->stream));
-    NL_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    NL_HIP(hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    h->ms[which] += ms;
     return NL_OK;
 }
 
@@ -154,7 +82,7 @@ static int vf_stop(nl_voxfeat *h, int which, char *err, size_t errlen) {
 // object's shape.  The voxels with component > 0 are listed in raster order with their four values.  n_vox = their number.
 extern "C" int nl_voxfeat_frame(nl_voxfeat *h, const int32_t *comp, const int32_t *branch, const void *raw, int raw_dtype, const void *structure,
                                 int struct_dtype, int64_t *n_vox, char *err, size_t errlen) {
-    VF_ENTER(h);
+    STAGE_ENTER(h, "voxel-feature object");
     if (!comp || !branch || !raw || !structure || !n_vox) return nl_fail(err, errlen, NL_EINVAL, "NULL frame or n_vox");
     const size_t rs = dtype_size(raw_dtype), ss = dtype_size(struct_dtype);
     if (!rs || !ss) return nl_fail(err, errlen, NL_EINVAL, "unsupported dtype code");
@@ -167,21 +95,13 @@ extern "C" int nl_voxfeat_frame(nl_voxfeat *h, const int32_t *comp, const int32_
     NL_HIP(hipMemcpyAsync(h->d_branch, branch, (size_t)n * 4, hipMemcpyHostToDevice, st));
     NL_HIP(hipMemcpyAsync(h->d_a, raw, (size_t)n * rs, hipMemcpyHostToDevice, st));
     NL_HIP(hipMemcpyAsync(h->d_b, structure, (size_t)n * ss, hipMemcpyHostToDevice, st));
-    NL_HIP(hipEventRecord(h->ev_a, st));
+    if (int rc = stage_start(*h, err, errlen)) return rc;
     const unsigned gv = (unsigned)((n + 255) / 256);
-    vf_mask_kernel<<<gv, 256, 0, st>>>(h->d_comp, NL_I32, n, h->bits, h->d_wcount);
+    rank_mask_kernel<<<gv, 256, 0, st>>>(VfPositive{h->d_comp, NL_I32}, n, h->bits, h->d_wcount);
     NL_CHECK_LAUNCH();
     i64 total = 0;
-    if (int rc = vf_scan(h, h->d_wcount, h->words, h->pre, VF_MAX_ROWS, "labelled voxels in one frame", &total, err, errlen)) return rc;
-    if (total > h->cap) {
-        h->cap = 0;
-        if (int rc = vf_grow(&h->vox, total, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->lab_c, total, 4, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->lab_b, total, 4, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->raw_c, total, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->st_c, total, 8, err, errlen)) return rc;
-        h->cap = total;
-    }
+    if (int rc = rank_scan(h->scan, st, h->d_wcount, h->words, h->pre, VF_MAX_ROWS, "labelled voxels in one frame", &total, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->cap, total, total, {{&h->vox, 8}, {&h->lab_c, 4}, {&h->lab_b, 4}, {&h->raw_c, 8}, {&h->st_c, 8}}, err, errlen)) return rc;
     NL_HIP(hipMemsetAsync(h->d_maxlab, 0, 4, st));
     if (total > 0) {
         vf_compact_kernel<<<gv, 256, 0, st>>>(h->d_comp, h->d_branch, h->d_a, (int)rs, h->d_b, (int)ss, n, h->bits, h->pre, h->vox, h->lab_c,
@@ -189,7 +109,7 @@ extern "C" int nl_voxfeat_frame(nl_voxfeat *h, const int32_t *comp, const int32_
         NL_CHECK_LAUNCH();
     }
     NL_HIP(hipMemcpyAsync(h->h_maxlab, h->d_maxlab, 4, hipMemcpyDeviceToHost, st));
-    if (int rc = vf_stop(h, VF_MS_LOAD, err, errlen)) return rc;          // the host arrays may go away after the call
+    if (int rc = stage_stop(*h, &h->ms[VF_MS_LOAD], err, errlen)) return rc;          // the host arrays may go away after the call
     h->n = total;
     h->raw_size = (int)rs;
     h->st_size = (int)ss;
@@ -202,7 +122,7 @@ extern "C" int nl_voxfeat_frame(nl_voxfeat *h, const int32_t *comp, const int32_
 // Downloads the frame's voxel list: linear indices (n_vox, raster order), component and branch labels, intensity and structure
 // values (n_vox elements of the uploaded dtypes).  NULL pointers are skipped.
 extern "C" int nl_voxfeat_fetch_voxels(nl_voxfeat *h, int64_t *vox, int32_t *comp, int32_t *branch, void *raw, void *structure, char *err, size_t errlen) {
-    VF_ENTER(h);
+    STAGE_ENTER(h, "voxel-feature object");
     if (!h->has_frame) return nl_fail(err, errlen, NL_ESTATE, "no frame loaded");
     hipStream_t st = h->stream;
     if (h->n > 0) {
@@ -233,7 +153,7 @@ static int vf_direction(nl_voxfeat *h, nl_flow *flow, double *d_v, int64_t *foun
 // The motility features of the loaded frame.  bw: a flow field with the backward rows of the frame's time point loaded (vec01),
 // fw: one with its forward rows (vec12); NULL: the direction does not exist.  n_found_*: voxels with a flow neighbour.
 extern "C" int nl_voxfeat_motility(nl_voxfeat *h, nl_flow *bw, nl_flow *fw, int64_t *n_found_bw, int64_t *n_found_fw, char *err, size_t errlen) {
-    VF_ENTER(h);
+    STAGE_ENTER(h, "voxel-feature object");
     if (!n_found_bw || !n_found_fw) return nl_fail(err, errlen, NL_EINVAL, "n_found is NULL");
     if (!h->has_frame) return nl_fail(err, errlen, NL_ESTATE, "no frame loaded");
     *n_found_bw = *n_found_fw = 0;
@@ -245,31 +165,20 @@ extern "C" int nl_voxfeat_motility(nl_voxfeat *h, nl_flow *bw, nl_flow *fw, int6
     hipStream_t st = h->stream;
     int off[VF_OUT_BLOCKS + 1];
     vf_out_layout(D, off);
-    if (n > h->m_cap) {
-        h->m_cap = 0;
-        if (int rc = vf_grow(&h->d_q, n * D, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->d_v01, n * D, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->d_v12, n * D, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->d_out, n * off[VF_OUT_BLOCKS], 4, err, errlen)) return rc;
-        h->m_cap = n;
-    }
-    if (h->nlab > h->lab_cap) {
-        h->lab_cap = 0;
-        if (int rc = vf_grow(&h->d_best, 2 * (i64)h->nlab, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->d_pivot, 2 * (i64)h->nlab, 4, err, errlen)) return rc;
-        h->lab_cap = h->nlab;
-    }
+    if (int rc = stage_grow(&h->m_cap, n, n, {{&h->d_q, (size_t)D * 8}, {&h->d_v01, (size_t)D * 8}, {&h->d_v12, (size_t)D * 8},
+                                              {&h->d_out, (size_t)off[VF_OUT_BLOCKS] * 4}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->lab_cap, h->nlab, h->nlab, {{&h->d_best, 2 * 8}, {&h->d_pivot, 2 * 4}}, err, errlen)) return rc;      // two tables each
     const unsigned gq = (unsigned)((n + 255) / 256);
-    NL_HIP(hipEventRecord(h->ev_a, st));
-    vf_coords_kernel<<<gq, 256, 0, st>>>(h->vox, n, h->g, D, h->d_q);
+    if (int rc = stage_start(*h, err, errlen)) return rc;
+    rank_coords_kernel<<<gq, 256, 0, st>>>(h->vox, n, h->g.ny, h->g.nx, D, h->d_q);
     NL_CHECK_LAUNCH();
-    if (int rc = vf_stop(h, VF_MS_FLOW, err, errlen)) return rc;          // the queries are complete before the fields read them
+    if (int rc = stage_stop(*h, &h->ms[VF_MS_FLOW], err, errlen)) return rc;          // the queries are complete before the fields read them
     if (int rc = vf_direction(h, bw, h->d_v01, n_found_bw, err, errlen)) return rc;
     if (int rc = vf_direction(h, fw, h->d_v12, n_found_fw, err, errlen)) return rc;
     const int nlab = h->nlab;
     u64 *best01 = h->d_best, *best12 = h->d_best + nlab;
     int *piv01 = h->d_pivot, *piv12 = h->d_pivot + nlab;
-    NL_HIP(hipEventRecord(h->ev_a, st));
+    if (int rc = stage_start(*h, err, errlen)) return rc;
     NL_HIP(hipMemsetAsync(h->d_best, 0xff, (size_t)2 * nlab * 8, st));
     NL_HIP(hipMemsetAsync(h->d_pivot, 0x7f, (size_t)2 * nlab * 4, st));
     const double *vs[2] = {h->d_v01, h->d_v12};
@@ -287,12 +196,12 @@ extern "C" int nl_voxfeat_motility(nl_voxfeat *h, nl_flow *bw, nl_flow *fw, int6
         }
         NL_CHECK_LAUNCH();
     }
-    if (int rc = vf_stop(h, VF_MS_PIVOT, err, errlen)) return rc;
-    NL_HIP(hipEventRecord(h->ev_a, st));
+    if (int rc = stage_stop(*h, &h->ms[VF_MS_PIVOT], err, errlen)) return rc;
+    if (int rc = stage_start(*h, err, errlen)) return rc;
     if (D == 3) vf_motility_kernel<3><<<gq, 256, 0, st>>>(h->vox, n, h->g, h->lab_b, nlab, h->d_v01, h->d_v12, piv01, piv12, h->d_out);
     else vf_motility_kernel<2><<<gq, 256, 0, st>>>(h->vox, n, h->g, h->lab_b, nlab, h->d_v01, h->d_v12, piv01, piv12, h->d_out);
     NL_CHECK_LAUNCH();
-    if (int rc = vf_stop(h, VF_MS_MOTILITY, err, errlen)) return rc;
+    if (int rc = stage_stop(*h, &h->ms[VF_MS_MOTILITY], err, errlen)) return rc;
     h->has_motility = true;
     return NL_OK;
 }
@@ -301,7 +210,7 @@ extern "C" int nl_voxfeat_motility(nl_voxfeat *h, nl_flow *bw, nl_flow *fw, int6
 // linear_vel_vector (n, D), linear_vel, angular_vel_vector ((n) in 2-D, (n, 3) in 3-D), angular_vel, linear_acc, angular_acc,
 // rel_linear_vel, rel_angular_vel, rel_linear_acc, rel_angular_acc, rel_directionality.  out: 13 host pointers, NULL ones skipped.
 extern "C" int nl_voxfeat_fetch_motility(nl_voxfeat *h, float *const *out, char *err, size_t errlen) {
-    VF_ENTER(h);
+    STAGE_ENTER(h, "voxel-feature object");
     if (!out) return nl_fail(err, errlen, NL_EINVAL, "out is NULL");
     if (!h->has_motility) return nl_fail(err, errlen, NL_ESTATE, "no motility results to fetch");
     int off[VF_OUT_BLOCKS + 1];
@@ -318,7 +227,7 @@ extern "C" int nl_voxfeat_fetch_motility(nl_voxfeat *h, float *const *out, char 
 // Nodes are the voxels with pixel class > 0 in raster order.  n_nodes, n_pairs: nodes, (node, voxel) pairs.
 extern "C" int nl_voxfeat_nodes(nl_voxfeat *h, const void *pixel_class, int class_dtype, const void *distance, int dist_dtype, int64_t *n_nodes,
                                 int64_t *n_pairs, char *err, size_t errlen) {
-    VF_ENTER(h);
+    STAGE_ENTER(h, "voxel-feature object");
     if (!pixel_class || !distance || !n_nodes || !n_pairs) return nl_fail(err, errlen, NL_EINVAL, "NULL frame or counter");
     if (!h->has_frame) return nl_fail(err, errlen, NL_ESTATE, "no frame loaded");
     const size_t cs = dtype_size(class_dtype);
@@ -332,28 +241,14 @@ extern "C" int nl_voxfeat_nodes(nl_voxfeat *h, const void *pixel_class, int clas
     *n_nodes = *n_pairs = 0;
     NL_HIP(hipMemcpyAsync(h->d_a, pixel_class, (size_t)n * cs, hipMemcpyHostToDevice, st));
     NL_HIP(hipMemcpyAsync(h->d_b, distance, (size_t)n * dtype_size(dist_dtype), hipMemcpyHostToDevice, st));
-    NL_HIP(hipEventRecord(h->ev_a, st));
+    if (int rc = stage_start(*h, err, errlen)) return rc;
     const unsigned gv = (unsigned)((n + 255) / 256);
-    vf_mask_kernel<<<gv, 256, 0, st>>>(h->d_a, class_dtype, n, h->nbits, h->d_wcount);
+    rank_mask_kernel<<<gv, 256, 0, st>>>(VfPositive{h->d_a, class_dtype}, n, h->nbits, h->d_wcount);
     NL_CHECK_LAUNCH();
     i64 m = 0, pairs = 0, pairs_v = 0;
-    if (int rc = vf_scan(h, h->d_wcount, h->words, h->npre, VF_MAX_ROWS, "nodes in one frame", &m, err, errlen)) return rc;
-    if (m > h->node_cap) {
-        h->node_cap = 0;
-        if (int rc = vf_grow(&h->node_vox, m, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->radius, m, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->lims, 6 * m, 8, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->ncount, m, 4, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->nstart, m, 4, err, errlen)) return rc;
-        h->node_cap = m;
-    }
-    if (nv > h->vcnt_cap) {
-        h->vcnt_cap = 0;
-        if (int rc = vf_grow(&h->vcount, nv, 4, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->vstart, nv, 4, err, errlen)) return rc;
-        if (int rc = vf_grow(&h->cursor, nv, 4, err, errlen)) return rc;
-        h->vcnt_cap = nv;
-    }
+    if (int rc = rank_scan(h->scan, st, h->d_wcount, h->words, h->npre, VF_MAX_ROWS, "nodes in one frame", &m, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->node_cap, m, m, {{&h->node_vox, 8}, {&h->radius, 8}, {&h->lims, 6 * 8}, {&h->ncount, 4}, {&h->nstart, 4}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->vcnt_cap, nv, nv, {{&h->vcount, 4}, {&h->vstart, 4}, {&h->cursor, 4}}, err, errlen)) return rc;
     if (m > 0) {
         const unsigned gm = (unsigned)((m + 255) / 256);
         vf_node_compact_kernel<<<gv, 256, 0, st>>>(h->d_b, dist_dtype, n, h->nbits, h->npre, h->node_vox, h->radius);
@@ -364,15 +259,10 @@ extern "C" int nl_voxfeat_nodes(nl_voxfeat *h, const void *pixel_class, int clas
             NL_HIP(hipMemsetAsync(h->vcount, 0, (size_t)nv * 4, st));
             vf_node_count_kernel<<<gm, 256, 0, st>>>(h->lims, m, h->g, D, h->bits, h->pre, h->ncount, h->vcount);
             NL_CHECK_LAUNCH();
-            if (int rc = vf_scan(h, h->ncount, m, h->nstart, VF_MAX_PAIRS, "(node, voxel) pairs in one frame", &pairs, err, errlen)) return rc;
-            if (int rc = vf_scan(h, h->vcount, nv, h->vstart, VF_MAX_PAIRS, "(node, voxel) pairs in one frame", &pairs_v, err, errlen)) return rc;
+            if (int rc = rank_scan(h->scan, st, h->ncount, m, h->nstart, VF_MAX_PAIRS, "(node, voxel) pairs in one frame", &pairs, err, errlen)) return rc;
+            if (int rc = rank_scan(h->scan, st, h->vcount, nv, h->vstart, VF_MAX_PAIRS, "(node, voxel) pairs in one frame", &pairs_v, err, errlen)) return rc;
             if (pairs_v != pairs) return nl_fail(err, errlen, NL_ESTATE, "node and voxel pair counts disagree");
-            if (pairs > h->pair_cap) {
-                h->pair_cap = 0;
-                if (int rc = vf_grow(&h->node_val, pairs, 4, err, errlen)) return rc;
-                if (int rc = vf_grow(&h->vox_val, pairs, 4, err, errlen)) return rc;
-                h->pair_cap = pairs;
-            }
+            if (int rc = stage_grow(&h->pair_cap, pairs, pairs, {{&h->node_val, 4}, {&h->vox_val, 4}}, err, errlen)) return rc;
             if (pairs > 0) {
                 NL_HIP(hipMemcpyAsync(h->cursor, h->vstart, (size_t)nv * 4, hipMemcpyDeviceToDevice, st));
                 vf_node_place_kernel<<<gm, 256, 0, st>>>(h->lims, m, h->g, D, h->bits, h->pre, h->nstart, h->node_val, h->cursor, h->vox_val);
@@ -385,7 +275,7 @@ extern "C" int nl_voxfeat_nodes(nl_voxfeat *h, const void *pixel_class, int clas
             NL_HIP(hipMemsetAsync(h->nstart, 0, (size_t)m * 4, st));
         }
     }
-    if (int rc = vf_stop(h, VF_MS_NODES, err, errlen)) return rc;
+    if (int rc = stage_stop(*h, &h->ms[VF_MS_NODES], err, errlen)) return rc;
     h->m = m;
     h->pairs = pairs;
     h->has_nodes = true;
@@ -400,7 +290,7 @@ extern "C" int nl_voxfeat_nodes(nl_voxfeat *h, const void *pixel_class, int clas
 // pointers are skipped.
 extern "C" int nl_voxfeat_fetch_nodes(nl_voxfeat *h, int64_t *lims0, int64_t *lims1, int64_t *lims2, int32_t *node_start, int32_t *node_val,
                                       int32_t *vox_start, int32_t *vox_val, char *err, size_t errlen) {
-    VF_ENTER(h);
+    STAGE_ENTER(h, "voxel-feature object");
     if (!h->has_nodes) return nl_fail(err, errlen, NL_ESTATE, "no node assignment to fetch");
     hipStream_t st = h->stream;
     const i64 m = h->m;

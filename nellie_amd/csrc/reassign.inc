@@ -10,7 +10,7 @@
 // Compiled with -ffp-contract=off: the distances are products and sums, never a fused multiply-add.
 #pragma once
 
-#include "rank_scan.inc"            // the exclusive scan, ra_rank, u64
+#include "rank_scan.inc"            // mask, exclusive scan, ra_rank, query coordinates, u64
 
 struct RaGeom {
     i64 nz, ny, nx, n;
@@ -24,17 +24,10 @@ struct RaOffset {                     // 24 bytes
 };
 
 // ---- mask, scan, compaction ---------------------------------------------------------------------------------------------
-// One lane per voxel, one wave per mask word: bits[w] and the word's population count.
-__global__ __launch_bounds__(256) void ra_mask_kernel(const int *__restrict__ branch, const int *__restrict__ obj, i64 n,
-                                                      u64 *__restrict__ bits, int *__restrict__ wcount) {
-    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n && (branch[i] > 0 || obj[i] > 0);
-    const u64 b = __ballot(on);
-    if ((threadIdx.x & 63) == 0) {
-        bits[i >> 6] = b;
-        wcount[i >> 6] = __popcll(b);
-    }
-}
+struct RaLabelled {                   // rank_mask_kernel's predicate: the union mask
+    const int *branch, *obj;
+    __device__ bool operator()(i64 i) const { return branch[i] > 0 || obj[i] > 0; }
+};
 
 // One lane per voxel: the labelled ones write their row.  seed: reassigned = the labels themselves (frame 0), else 0.
 __global__ __launch_bounds__(256) void ra_compact_kernel(const int *__restrict__ branch, const int *__restrict__ obj, i64 n,
@@ -53,23 +46,7 @@ __global__ __launch_bounds__(256) void ra_compact_kernel(const int *__restrict__
     re_o[k] = seed && o > 0 ? o : 0;
 }
 
-// ---- queries ------------------------------------------------------------------------------------------------------------
-// The labelled voxels as float64 query rows (n, D) of the flow interpolation.
-__global__ __launch_bounds__(256) void ra_coords_kernel(const i64 *__restrict__ vox, i64 n, RaGeom g, int D, double *__restrict__ q) {
-    const i64 k = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    const i64 i = vox[k];
-    const i64 x = i % g.nx, y = (i / g.nx) % g.ny, z = i / (g.nx * g.ny);
-    if (D == 3) {
-        q[k * 3] = (double)z;
-        q[k * 3 + 1] = (double)y;
-        q[k * 3 + 2] = (double)x;
-    } else {
-        q[k * 2] = (double)y;
-        q[k * 2 + 1] = (double)x;
-    }
-}
-
+// ---- search -------------------------------------------------------------------------------------------------------------
 // One lane per query voxel: c = voxel + sign * vector; the nearest labelled voxel m of the other frame under
 // d2 = sum_axes (float64(float32(c)) * s - m * s)^2, the lowest linear index on a tie; d = float32(|float32(c - m) * s|).
 // match[k] = the rank of m when float64(d) < r, else -1 (a NaN vector included).

@@ -37,17 +37,11 @@ __device__ __forceinline__ bool vf_positive(const void *__restrict__ p, int dtyp
     }
 }
 
-// One lane per voxel, one wave per mask word: bits[w] and the word's population count.
-__global__ __launch_bounds__(256) void vf_mask_kernel(const void *__restrict__ src, int dtype, i64 n, u64 *__restrict__ bits,
-                                                      int *__restrict__ wcount) {
-    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n && vf_positive(src, dtype, i);
-    const u64 b = __ballot(on);
-    if ((threadIdx.x & 63) == 0) {
-        bits[i >> 6] = b;
-        wcount[i >> 6] = __popcll(b);
-    }
-}
+struct VfPositive {                   // rank_mask_kernel's predicate: positive in dtype `dtype`
+    const void *src;
+    int dtype;
+    __device__ bool operator()(i64 i) const { return vf_positive(src, dtype, i); }
+};
 
 __device__ __forceinline__ void vf_copy_elem(const void *__restrict__ src, i64 i, void *__restrict__ dst, i64 k, int size) {
     switch (size) {
@@ -87,15 +81,6 @@ __device__ __forceinline__ void vf_position(i64 i, const VfGeom &g, int D, doubl
         p[0] = (double)(i / g.nx);
         p[1] = (double)(i % g.nx);
     }
-}
-
-// The labelled voxels as float64 query rows (n, D) of the flow interpolation.
-__global__ __launch_bounds__(256) void vf_coords_kernel(const i64 *__restrict__ vox, i64 n, VfGeom g, int D, double *__restrict__ q) {
-    const i64 k = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    double p[3];
-    vf_position(vox[k], g, D, p);
-    for (int a = 0; a < D; ++a) q[k * D + a] = p[a];
 }
 
 // sqrt of the squares added in axis order

@@ -433,25 +433,26 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(_p)
 
 
-class Context:
-    """One device context = one (device, local slab shape) pair (include/nellie_amd.h nl_ctx)."""
+def _opt(a):
+    return None if a is None else _ptr(a)
 
-    def __init__(self, shape, device=0, gz0=0, gnz=None, own=None):
+
+class _Handle:
+    """An opaque handle of the library: created by `nl_*_create`, passed first to every call, destroyed once."""
+
+    _destroy = None      # the destroy symbol (no error buffer)
+    _noun = None         # what the error messages call the object
+    _h = None
+
+    def _create(self, name, *args):
         self.lib = load()
-        nz, ny, nx = (int(s) for s in shape)
-        self.shape = (nz, ny, nx)
-        self.gz0 = int(gz0)
-        self.gnz = int(gnz) if gnz is not None else nz
-        self.own = (0, nz) if own is None else (int(own[0]), int(own[1]))
-        self.device = int(device)
         h = _p()
-        self.lib.call("nl_ctx_create", C.byref(h), self.device, nz, ny, nx, self.gz0, self.gnz,
-                      self.own[0], self.own[1])
+        self.lib.call(name, C.byref(h), *args)
         self._h = h
 
     def close(self):
-        if getattr(self, "_h", None):
-            self.lib.cdll.nl_ctx_destroy(self._h)
+        if self._h:
+            getattr(self.lib.cdll, self._destroy)(self._h)
             self._h = None
 
     __del__ = close
@@ -464,8 +465,55 @@ class Context:
 
     def _call(self, name, *args):
         if not self._h:
-            raise NellieHipError(NL_ESTATE, "context is closed")
+            raise NellieHipError(NL_ESTATE, f"{self._noun} is closed")
         self.lib.call(name, self._h, *args)
+
+
+def _frame_geometry(what, spacing, shape=None, ndim=None):
+    """The constructor checks of the stage handles -> (ndim, shape, (nz, ny, nx), spacing as float64); a handle without a frame
+    shape gives its ndim instead and gets None for both shapes."""
+    got = f"ndim {ndim}" if shape is None else f"shape {tuple(shape)}"
+    ndim = int(ndim) if shape is None else len(shape)
+    if ndim not in (2, 3):
+        raise ValueError(f"{what} are 2-D or 3-D, got {got}")
+    if shape is not None:
+        shape = tuple(int(s) for s in shape)
+    sp = np.ascontiguousarray(spacing, dtype=np.float64)
+    if sp.size != ndim:
+        raise ValueError(f"spacing needs {ndim} values")
+    return ndim, shape, (None if shape is None else (1,) * (3 - ndim) + shape), sp
+
+
+def _frame_array(a, shape, what, owner, dtype=None, dtype_error=TypeError):
+    """A frame a stage handle uploads: of the handle's shape, C-contiguous, in `dtype` or (None) in its own dtype, which the
+    library must know."""
+    a = np.asarray(a)
+    if a.shape != shape:
+        raise ValueError(f"{what} shape {a.shape} does not match the {owner}'s {shape}")
+    if dtype is None and a.dtype not in DTYPE_CODES:
+        raise dtype_error(f"unsupported {what} dtype {a.dtype}")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _kernel_ms(handle, name) -> float:
+    ms = _f32(0)
+    handle._call(name, C.byref(ms))
+    return float(ms.value)
+
+
+class Context(_Handle):
+    """One device context = one (device, local slab shape) pair (include/nellie_amd.h nl_ctx)."""
+
+    _destroy, _noun = "nl_ctx_destroy", "context"
+
+    def __init__(self, shape, device=0, gz0=0, gnz=None, own=None):
+        nz, ny, nx = (int(s) for s in shape)
+        self.shape = (nz, ny, nx)
+        self.gz0 = int(gz0)
+        self.gnz = int(gnz) if gnz is not None else nz
+        self.own = (0, nz) if own is None else (int(own[0]), int(own[1]))
+        self.device = int(device)
+        self._create("nl_ctx_create", self.device, nz, ny, nx, self.gz0, self.gnz, self.own[0], self.own[1])
 
     def sync(self):
         self._call("nl_sync")
@@ -1084,58 +1132,26 @@ class Context:
         return float(ms.value), int(k.value)
 
 
-class Tracker:
+class Tracker(_Handle):
     """Device state of Hu-moment tracking for one T stack (include/nellie_amd.h nl_track_*): the features of the last two
     frames stay on the device, so matching a frame against the one before uploads nothing."""
 
+    _destroy, _noun = "nl_track_destroy", "tracker"
+
     def __init__(self, shape, spacing, device=0):
-        self.lib = load()
-        self.ndim = len(shape)
-        if self.ndim not in (2, 3):
-            raise ValueError(f"tracking frames are 2-D or 3-D, got shape {tuple(shape)}")
-        self.shape = tuple(int(s) for s in shape)
+        self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("tracking frames", spacing, shape=shape)
         self.nh = 6 if self.ndim == 2 else 18
-        nz, ny, nx = (1,) + self.shape if self.ndim == 2 else self.shape
-        sp = np.ascontiguousarray(spacing, dtype=np.float64)
-        if sp.size != self.ndim:
-            raise ValueError(f"spacing needs {self.ndim} values")
-        h = _p()
-        self.lib.call("nl_track_create", C.byref(h), int(device), self.ndim, nz, ny, nx, _ptr(sp))
-        self._h = h
+        self._create("nl_track_create", int(device), self.ndim, nz, ny, nx, _ptr(sp))
         self.n = [0, 0]                                   # markers of the last frame, of the one before
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.cdll.nl_track_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _call(self, name, *args):
-        if not self._h:
-            raise NellieHipError(NL_ESTATE, "tracker is closed")
-        self.lib.call(name, self._h, *args)
-
     def frame(self, intensity, frangi, distance, marker) -> int:
-        arrs = []
-        for a, dt in ((intensity, None), (frangi, np.float32), (distance, np.float32), (marker, np.uint8)):
-            a = np.asarray(a)
-            if a.shape != self.shape:
-                raise ValueError(f"frame shape {a.shape} does not match the tracker's {self.shape}")
-            if dt is not None and a.dtype != dt:
-                a = (a > 0).astype(np.uint8) if dt == np.uint8 else a.astype(dt)
-            arrs.append(np.ascontiguousarray(a))
-        code = DTYPE_CODES.get(arrs[0].dtype)
-        if code is None:
-            raise ValueError(f"unsupported intensity dtype {arrs[0].dtype}")
+        marker = np.asarray(marker)
+        if marker.dtype != np.uint8:
+            marker = marker > 0
+        i, f, d, m = (_frame_array(a, self.shape, "frame", "tracker", dt, ValueError)
+                      for a, dt in ((intensity, None), (frangi, np.float32), (distance, np.float32), (marker, np.uint8)))
         n = _i64(0)
-        self._call("nl_track_frame", _ptr(arrs[0]), code, _ptr(arrs[1]), _ptr(arrs[2]), _ptr(arrs[3]), C.byref(n))
+        self._call("nl_track_frame", _ptr(i), DTYPE_CODES[i.dtype], _ptr(f), _ptr(d), _ptr(m), C.byref(n))
         self.n = [int(n.value), self.n[0]]
         return self.n[0]
 
@@ -1153,45 +1169,20 @@ class Tracker:
         ri, rc = np.full(n_post, -1, np.int32), np.full(n_post, np.inf, np.float32)
         ci, cc = np.full(n_pre, -1, np.int32), np.full(n_pre, np.inf, np.float32)
         m = np.full((n_post, n_pre), np.inf, np.float16) if full else None
-        self._call("nl_track_match", 0 if mode == "dense" else 1, float(max_distance), _ptr(ri), _ptr(rc), _ptr(ci), _ptr(cc),
-                   None if m is None else _ptr(m))
+        self._call("nl_track_match", 0 if mode == "dense" else 1, float(max_distance), _ptr(ri), _ptr(rc), _ptr(ci), _ptr(cc), _opt(m))
         return (ri, rc, ci, cc, m) if full else (ri, rc, ci, cc)
 
 
-class FlowField:
+class FlowField(_Handle):
     """Device state of flow-vector interpolation (include/nellie_amd.h nl_flow_*): the flow rows of one time point and direction,
     binned into a grid of cells of edge r, stay on the device until the next load()."""
 
+    _destroy, _noun = "nl_flow_destroy", "flow field"
+
     def __init__(self, ndim, spacing, r, device=0):
-        self.lib = load()
-        self.ndim = int(ndim)
-        if self.ndim not in (2, 3):
-            raise ValueError(f"flow fields are 2-D or 3-D, got ndim {ndim}")
-        sp = np.ascontiguousarray(spacing, dtype=np.float64)
-        if sp.size != self.ndim:
-            raise ValueError(f"spacing needs {self.ndim} values")
-        h = _p()
-        self.lib.call("nl_flow_create", C.byref(h), int(device), self.ndim, _ptr(sp), float(r))
-        self._h = h
+        self.ndim, _, _, sp = _frame_geometry("flow fields", spacing, ndim=ndim)
+        self._create("nl_flow_create", int(device), self.ndim, _ptr(sp), float(r))
         self.n_rows = 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.cdll.nl_flow_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _call(self, name, *args):
-        if not self._h:
-            raise NellieHipError(NL_ESTATE, "flow field is closed")
-        self.lib.call(name, self._h, *args)
 
     def load(self, coords, vectors, costs):
         """check coordinates (n, ndim), vectors (n, ndim) and costs (n) of one time point and direction"""
@@ -1212,59 +1203,26 @@ class FlowField:
         return out, int(found.value)
 
     def kernel_ms(self) -> float:
-        ms = _f32(0)
-        self._call("nl_flow_kernel_ms", C.byref(ms))
-        return float(ms.value)
+        return _kernel_ms(self, "nl_flow_kernel_ms")
 
 
-class Reassigner:
+class Reassigner(_Handle):
     """Device state of voxel reassignment for one label stack (include/nellie_amd.h nl_reassign_*): the last two frames stay on
     the device -- mask, labelled voxels, labels and reassigned labels -- so a frame is uploaded once and only the reassigned
     labels of the labelled voxels (and the best pairs, when asked for) come back."""
 
+    _destroy, _noun = "nl_reassign_destroy", "reassigner"
+
     def __init__(self, shape, spacing, r, device=0):
-        self.lib = load()
-        self.ndim = len(shape)
-        if self.ndim not in (2, 3):
-            raise ValueError(f"label frames are 2-D or 3-D, got shape {tuple(shape)}")
-        self.shape = tuple(int(s) for s in shape)
-        nz, ny, nx = (1,) + self.shape if self.ndim == 2 else self.shape
-        sp = np.ascontiguousarray(spacing, dtype=np.float64)
-        if sp.size != self.ndim:
-            raise ValueError(f"spacing needs {self.ndim} values")
-        h = _p()
-        self.lib.call("nl_reassign_create", C.byref(h), int(device), self.ndim, nz, ny, nx, _ptr(sp), float(r))
-        self._h = h
+        self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("label frames", spacing, shape=shape)
+        self._create("nl_reassign_create", int(device), self.ndim, nz, ny, nx, _ptr(sp), float(r))
         self.n = [0, 0]                                   # labelled voxels of the last frame, of the one before
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.cdll.nl_reassign_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _call(self, name, *args):
-        if not self._h:
-            raise NellieHipError(NL_ESTATE, "reassigner is closed")
-        self.lib.call(name, self._h, *args)
 
     def frame(self, branch, obj, seed=False) -> int:
         """uploads the next frame's labels; returns its number of labelled voxels (branch > 0 | obj > 0)"""
-        arrs = []
-        for a in (branch, obj):
-            a = np.asarray(a)
-            if a.shape != self.shape:
-                raise ValueError(f"frame shape {a.shape} does not match the reassigner's {self.shape}")
-            arrs.append(np.ascontiguousarray(a, dtype=np.int32))
+        b, o = (_frame_array(a, self.shape, "frame", "reassigner", np.int32) for a in (branch, obj))
         n = _i64(0)
-        self._call("nl_reassign_frame", _ptr(arrs[0]), _ptr(arrs[1]), 1 if seed else 0, C.byref(n))
+        self._call("nl_reassign_frame", _ptr(b), _ptr(o), 1 if seed else 0, C.byref(n))
         self.n = [int(n.value), self.n[0]]
         return self.n[0]
 
@@ -1284,17 +1242,14 @@ class Reassigner:
         rb = np.empty(n, np.int32) if labels else None
         ro = np.empty(n, np.int32) if labels else None
         bs = np.empty(n, np.int32) if best else None
-        opt = lambda a: None if a is None else _ptr(a)   # noqa: E731
-        self._call("nl_reassign_fetch", int(which), opt(vox), opt(rb), opt(ro), opt(bs))
+        self._call("nl_reassign_fetch", int(which), _opt(vox), _opt(rb), _opt(ro), _opt(bs))
         return vox, rb, ro, bs
 
     def kernel_ms(self) -> float:
-        ms = _f32(0)
-        self._call("nl_reassign_kernel_ms", C.byref(ms))
-        return float(ms.value)
+        return _kernel_ms(self, "nl_reassign_kernel_ms")
 
 
-class VoxelFeatures:
+class VoxelFeatures(_Handle):
     """Device state of the voxel level of the hierarchy for one stack (include/nellie_amd.h nl_voxfeat_*): one frame stays on
     the device -- mask, labelled voxels and their values -- while its flow vectors, pivots, motility features and node lists are
     computed; only per-voxel results, the two CSR lists and the node limits come back."""
@@ -1303,48 +1258,17 @@ class VoxelFeatures:
     MOTILITY = ("vec01", "vec12", "linear_vel_vector", "linear_vel", "angular_vel_vector", "angular_vel", "linear_acc", "angular_acc",
                 "rel_linear_vel", "rel_angular_vel", "rel_linear_acc", "rel_angular_acc", "rel_directionality")
 
+    _destroy, _noun = "nl_voxfeat_destroy", "voxel-feature object"
+
     def __init__(self, shape, spacing, dt, device=0):
-        self.lib = load()
-        self.ndim = len(shape)
-        if self.ndim not in (2, 3):
-            raise ValueError(f"frames are 2-D or 3-D, got shape {tuple(shape)}")
-        self.shape = tuple(int(s) for s in shape)
-        nz, ny, nx = (1,) + self.shape if self.ndim == 2 else self.shape
-        sp = np.ascontiguousarray(spacing, dtype=np.float64)
-        if sp.size != self.ndim:
-            raise ValueError(f"spacing needs {self.ndim} values")
-        h = _p()
-        self.lib.call("nl_voxfeat_create", C.byref(h), int(device), self.ndim, nz, ny, nx, _ptr(sp), float(dt))
-        self._h = h
+        self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("frames", spacing, shape=shape)
+        self._create("nl_voxfeat_create", int(device), self.ndim, nz, ny, nx, _ptr(sp), float(dt))
         self.n = 0                                        # labelled voxels of the loaded frame
         self.n_nodes = self.n_pairs = 0
         self._dtypes = (np.dtype(np.uint8), np.dtype(np.uint8))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.cdll.nl_voxfeat_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _call(self, name, *args):
-        if not self._h:
-            raise NellieHipError(NL_ESTATE, "voxel-feature object is closed")
-        self.lib.call(name, self._h, *args)
-
     def _frame_array(self, a, what, dtype=None):
-        a = np.asarray(a)
-        if a.shape != self.shape:
-            raise ValueError(f"{what} shape {a.shape} does not match the object's {self.shape}")
-        if dtype is None and a.dtype not in DTYPE_CODES:
-            raise TypeError(f"unsupported {what} dtype {a.dtype}")
-        return np.ascontiguousarray(a, dtype=dtype)
+        return _frame_array(a, self.shape, what, "object", dtype)
 
     def frame(self, comp, branch, raw, structure) -> int:
         """uploads a frame; returns the number of voxels with component label > 0"""
