@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from nellie_amd.utils import adaptive_run
+from nellie_amd.stage import frame_count, require_gpu, resolve_device, spacing_of
 from nellie_amd.utils.base_logger import logger
 
 
@@ -148,8 +148,7 @@ class Voxels:
         h = self.hierarchy
         if h.num_t is None:
             h.num_t = 1
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
+        require_gpu()
         self.kernel_ms = []
         try:
             fw, bw = self._interpolators()
@@ -171,22 +170,14 @@ class VoxelFeatures:
 
     def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
         self.im_info = im_info
-        dev = str(device or "auto").lower()
-        if dev not in ("auto", "cpu", "gpu", "cuda", "hip"):
-            raise ValueError(f"Unsupported device '{device}'. Use 'auto', 'cpu', or 'gpu'.")
-        if dev == "cpu":
-            raise RuntimeError("nellie_amd provides the MI355X HIP backend only: device='cpu' is not available "
-                               "(no CPU fallback exists in this package; use the reference implementation on CPU)")
+        resolve_device(device)
         self.device = device or "auto"
         self.device_index = int(device_index)
         self.skip_nodes = skip_nodes
         self.enable_motility = enable_motility
         self.viewer = viewer
-        self.num_t = 1 if im_info.no_t else im_info.shape[im_info.axes.index("T")]
-        if im_info.no_z:
-            self.spacing = (im_info.dim_res["Y"], im_info.dim_res["X"])
-        else:
-            self.spacing = (im_info.dim_res["Z"], im_info.dim_res["Y"], im_info.dim_res["X"])
+        self.num_t = frame_count(im_info)
+        self.spacing = spacing_of(im_info)
         self.im_raw = self.im_struct = self.im_distance = self.im_skel = self.im_pixel_class = self.im_border_mask = None
         self.label_components = self.label_branches = None
         self.flow_interpolator_fw = self.flow_interpolator_bw = None
@@ -220,8 +211,7 @@ class VoxelFeatures:
 
     def run(self):
         from nellie_amd.tracking.flow_interpolation import FlowInterpolator
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
+        require_gpu()
         logger.info("Running voxel feature extraction (HIP).")
         self._allocate_memory()
         try:

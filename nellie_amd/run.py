@@ -13,6 +13,7 @@ import time
 
 from nellie_amd.segmentation.filtering import Filter
 from nellie_amd.segmentation.labelling import Label
+from nellie_amd.stage import env_shard, flush, open_outputs, resolve_shard
 
 
 def _wait_for(path, timeout_s=600.0):
@@ -27,9 +28,9 @@ def _build_im_info(file_info, shard):
     """ImInfo(file_info) as run.py:49 -- in a multi-process launch (shard="env") rank 0 first, so that the canonical copy of the
     input (verifier.py:620-695) is written once; the other ranks then find it complete (ome_tiff.create moves files into place
     atomically) and reuse it instead of re-creating it under readers."""
-    from nellie_amd.engine import ShardSpec
     from nellie_amd.im_info.verifier import ImInfo
-    spec = ShardSpec.from_env() if shard == "env" or (shard is None and os.environ.get("NELLIE_SHARD") == "env") else None
+    # only "env" makes the ranks take turns here; whatever else `shard` or NELLIE_SHARD holds is for the stages to judge
+    spec = resolve_shard("env") if (env_shard() if shard is None else shard) == "env" else None
     if spec is None or spec.world <= 1:
         return ImInfo(file_info)
     import tempfile
@@ -60,12 +61,11 @@ def run_streamed(im_info, viewer=None, device_index=0, devices=None, shard=None)
                      RANK, RANK + WORLD_SIZE, ... on GPU LOCAL_RANK; rank 0 creates the two files, the others map them.
     No data crosses between the GPUs; the files are the ones a single GPU writes.
     """
-    from nellie_amd.engine import ShardSpec
     from nellie_amd.pipeline import FilterParams
     from nellie_amd.streaming import StreamedSegmenter
     if im_info.no_z:
         raise NotImplementedError("streaming covers 3-D frames")
-    spec = ShardSpec.from_env() if shard == "env" else shard
+    spec = resolve_shard(shard, use_env=False)               # (NELLIE_SHARD is for the Z-slab stages: frames are dealt out on request only)
     rank, world = (spec.rank, spec.world) if spec is not None else (0, 1)
     fr_path, lab_path = im_info.pipeline_paths["im_preprocessed"], im_info.pipeline_paths["im_instance_label"]
     # a multi-process run meets through files that carry this launch's nonce (nellie_amd/rendezvous.py): the markers of a launch
@@ -75,14 +75,9 @@ def run_streamed(im_info, viewer=None, device_index=0, devices=None, shard=None)
         from nellie_amd.rendezvous import rendezvous_for
         rdv = rendezvous_for(spec, os.path.dirname(lab_path))
     im = im_info.get_memmap(im_info.im_path)
-    if rank == 0:
-        fr = im_info.allocate_memory(fr_path, dtype="float32", description="frangi filtered im", return_memmap=True)
-        lab = im_info.allocate_memory(lab_path, dtype="int32", description="instance segmentation", return_memmap=True)
-        if rdv:
-            rdv.publish("streamed_files_ready")
-    else:
-        rdv.wait("streamed_files_ready")
-        fr, lab = im_info.get_memmap(fr_path), im_info.get_memmap(lab_path)
+    fr, lab = open_outputs(
+        im_info, [(fr_path, "float32", "frangi filtered im"), (lab_path, "int32", "instance segmentation")], creator=rank == 0,
+        announce=rdv and (lambda: rdv.publish("streamed_files_ready")), wait=rdv and (lambda: rdv.wait("streamed_files_ready")))
     devs = [spec.device] if spec is not None else ([int(d) for d in devices] if devices else [int(device_index)])
     params = FilterParams(dim_res=im_info.dim_res)
     num_t = im.shape[0]
@@ -119,7 +114,7 @@ def run_streamed(im_info, viewer=None, device_index=0, devices=None, shard=None)
             t.join()
         if errs:
             raise errs[0]
-    fr.flush(); lab.flush()
+    flush(fr, lab)
     if rdv:                                                    # EVERY rank returns only when every rank has flushed its frames
         rdv.barrier("streamed_done")
         if rank == 0:

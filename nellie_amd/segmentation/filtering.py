@@ -20,11 +20,12 @@ import os
 import numpy as np
 
 from nellie_amd.pipeline import FilterParams, FramePipeline, default_sigmas, sample_strides
+from nellie_amd.stage import FrameCounted, Held, frame_count, open_outputs, require_gpu, resolve_device, resolve_shard, shape_key
 from nellie_amd.utils import adaptive_run
 from nellie_amd.utils.base_logger import logger
 
 
-class Filter:
+class Filter(FrameCounted):
     def __init__(
         self,
         im_info,
@@ -53,19 +54,18 @@ class Filter:
         A frame too large for one context (>= 2^31 voxels) is cut into slabs on its own; results never depend on the layout."""
         self.im_info = im_info
         self.device = device
-        self.device_type = self._resolve_backend(device)
+        self.device_type = resolve_device(device)
+        require_gpu()
         self.device_index = int(device_index)
         self.devices = list(devices) if devices else None
         self.shard = shard
-        self._engine = None
+        self._held_pipeline, self._held_engine = Held(), Held()
         self.truncate = 3.0
         if not self.im_info.no_z:
             z_res = self.im_info.dim_res.get("Z") or self.im_info.dim_res.get("X") or 1.0
             x_res = self.im_info.dim_res.get("X") or 1.0
             self.z_ratio = float(z_res) / float(x_res)
-        self.num_t = num_t
-        if num_t is None and not self.im_info.no_t:
-            self.num_t = im_info.shape[im_info.axes.index("T")]
+        self.num_t = num_t if self.im_info.no_t else frame_count(im_info, num_t)      # without T the reference counts in run()
         self.remove_edges = remove_edges
         self.min_radius_um = min_radius_um
         self.max_radius_um = max_radius_um
@@ -89,22 +89,8 @@ class Filter:
         self.work_dtype = "float32"
         self.out_dtype = "float32"
         self.halo = None
-        self._pipeline = None
 
     # ------------------------------------------------------------------ backend
-    def _resolve_backend(self, device):
-        """filtering.py:117-159 with HIP in the role of CuPy."""
-        device = (device or "auto").lower()
-        if device not in ("auto", "cpu", "gpu", "cuda", "hip"):          # "hip": what INTEGRATION.md's dispatch forwards; same engine as "gpu"
-            raise ValueError(f"Unsupported device '{device}'. Use 'auto', 'cpu', or 'gpu'.")
-        if device == "cpu":
-            raise RuntimeError(
-                "nellie_amd provides the MI355X HIP backend only: device='cpu' is not available "
-                "(no CPU fallback exists in this package; use the reference implementation on CPU)")
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
-        return "hip"
-
     def _params(self) -> FilterParams:
         return FilterParams(
             dim_res=self.im_info.dim_res, min_radius_um=self.min_radius_um, max_radius_um=self.max_radius_um,
@@ -113,50 +99,24 @@ class Filter:
             max_threshold_samples=self.max_threshold_samples, sigmas=self.sigmas)
 
     def _get_pipeline(self, shape) -> FramePipeline:
-        key = tuple(int(s) for s in shape)
-        if self._pipeline is None or self._pipeline_key != key:
-            if self._pipeline is not None:
-                self._pipeline.close()
-            self._pipeline = FramePipeline(key, device=self.device_index)     # (Z, Y, X), or (Y, X) for no_z images
-            self._pipeline_key = key
-        return self._pipeline
+        key = shape_key(shape)                                                # (Z, Y, X), or (Y, X) for no_z images
+        return self._held_pipeline.get(key, lambda: FramePipeline(key, device=self.device_index))
 
     def _shard_spec(self):
-        from nellie_amd.engine import ShardSpec
-        shard = self.shard if self.shard is not None else (os.environ.get("NELLIE_SHARD") or None)
-        if isinstance(shard, str):
-            if shard != "env":
-                raise ValueError("shard must be 'env' or an engine.ShardSpec")
-            shard = ShardSpec.from_env(rendezvous_dir=os.path.dirname(self.im_info.pipeline_paths["im_preprocessed"]))
-        return shard
+        return resolve_shard(self.shard, rendezvous_dir=os.path.dirname(self.im_info.pipeline_paths["im_preprocessed"]))
 
     def _get_engine(self, shape):
         """The engine of a frame of this shape (nellie_amd/engine.py): one context, Z slabs in this process, or this rank's slab."""
         from nellie_amd.engine import make_engine
-        key = tuple(int(s) for s in shape)
-        if self._engine is None or self._engine_key != key:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = make_engine(key, self._params(), device_index=self.device_index, devices=self.devices, shard=self._shard_spec())
-            self._engine_key = key
-        return self._engine
+        key = shape_key(shape)
+        return self._held_engine.get(key, lambda: make_engine(key, self._params(), device_index=self.device_index, devices=self.devices,
+                                                         shard=self._shard_spec()))
 
     def close(self):
-        if self._pipeline is not None:
-            self._pipeline.close()
-            self._pipeline = None
-        if self._engine is not None:
-            self._engine.close()
-            self._engine = None
+        self._held_pipeline.close()
+        self._held_engine.close()
 
     # ------------------------------------------------------------------ setup (filtering.py:201-323)
-    def _get_t(self):
-        if self.num_t is None:
-            if self.im_info.no_t:
-                self.num_t = 1
-            else:
-                self.num_t = self.im_info.shape[self.im_info.axes.index("T")]
-
     def _allocate_memory(self, engine=None):
         """filtering.py:201-216.  In a multi-process run rank 0 creates the file, the other ranks map it once it exists
         (every rank writes its own planes of every frame)."""
@@ -164,15 +124,10 @@ class Filter:
         if self.im_memmap is None:
             self.im_memmap = self.im_info.get_memmap(self.im_info.im_path)
         self.shape = self.im_memmap.shape
-        im_frangi_path = self.im_info.pipeline_paths["im_preprocessed"]
-        multi = engine is not None and engine.kind == "rank-slab"
-        if not multi or engine.spec.rank == 0:
-            self.frangi_memmap = self.im_info.allocate_memory(
-                im_frangi_path, dtype=self.out_dtype, description="frangi filtered im", return_memmap=True)
-        if multi:
-            engine.barrier()
-            if engine.spec.rank != 0:
-                self.frangi_memmap = self.im_info.get_memmap(im_frangi_path)
+        barrier = engine.barrier if engine is not None and engine.kind == "rank-slab" else None
+        self.frangi_memmap, = open_outputs(
+            self.im_info, [(self.im_info.pipeline_paths["im_preprocessed"], self.out_dtype, "frangi filtered im")],
+            creator=barrier is None or engine.spec.rank == 0, announce=barrier, wait=barrier)
 
     def _get_sigma_vec(self, sigma: float):
         if self.im_info.no_z:
@@ -281,8 +236,8 @@ class Filter:
                 engine.filter(frame_view, self._params(), mask=mask, remove_edges=bool(self.remove_edges))
                 engine.download_frangi(out=self.frangi_memmap[t, ...])
             self.frangi_memmap.flush()
-        if self._engine is not None:
-            self._engine.barrier()
+        if self._held_engine.obj is not None:
+            self._held_engine.obj.barrier()
 
     def run(self, mask=True):
         """filtering.py:1033-1076.  The ladder has GPU rungs only; OOM re-raises as MemoryError."""

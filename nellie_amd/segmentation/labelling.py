@@ -19,6 +19,7 @@ import os
 import numpy as np
 
 from nellie_amd.pipeline import FramePipeline, min_area_pixels_of
+from nellie_amd.stage import FrameCounted, Held, frame_count, open_outputs, require_gpu, resolve_device, resolve_shard, shape_key
 from nellie_amd.utils import adaptive_run
 from nellie_amd.utils.base_logger import logger
 from nellie_amd.utils.gpu_functions import otsu_threshold
@@ -26,7 +27,7 @@ from nellie_amd.utils.gpu_functions import otsu_threshold
 _UNSET = object()
 
 
-class Label:
+class Label(FrameCounted):
     def __init__(self, im_info,
                  num_t=None,
                  threshold=None,
@@ -47,14 +48,13 @@ class Label:
         (nellie_amd/segmentation/filtering.py, nellie_amd/engine.py)."""
         self.im_info = im_info
         self.device = device
-        self.device_type = self._resolve_backend(device)
+        self.device_type = resolve_device(device)
+        require_gpu()
         self.device_index = int(device_index)
         self.devices = list(devices) if devices else None
         self.shard = shard
-        self._engine = None
-        self.num_t = num_t
-        if num_t is None and not self.im_info.no_t:
-            self.num_t = im_info.shape[im_info.axes.index('T')]
+        self._held_pipeline, self._held_engine = Held(), Held()
+        self.num_t = num_t if self.im_info.no_t else frame_count(im_info, num_t)      # without T the reference counts in run()
         self.threshold = threshold
         self.otsu_thresh_intensity = otsu_thresh_intensity
         self.im_memmap = None
@@ -80,40 +80,17 @@ class Label:
         self.max_chunk_voxels = int(max_chunk_voxels)
         self.ndim = 2 if self.im_info.no_z else 3
         self.min_area_pixels = self._compute_min_area_pixels()
-        self._pipeline = None
-
-    def _resolve_backend(self, device):
-        """labelling.py:115-154 with HIP in the role of CuPy."""
-        device = (device or "auto").lower()
-        if device not in ("auto", "cpu", "gpu", "cuda", "hip"):          # "hip": what INTEGRATION.md's dispatch forwards; same engine as "gpu"
-            raise ValueError(f"Unsupported device '{device}'. Use 'auto', 'cpu', or 'gpu'.")
-        if device == "cpu":
-            raise RuntimeError(
-                "nellie_amd provides the MI355X HIP backend only: device='cpu' is not available "
-                "(no CPU fallback exists in this package; use the reference implementation on CPU)")
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
-        return "hip"
 
     def _compute_min_area_pixels(self):
         """labelling.py:209-219 (min_radius_um already clamped to >= X resolution, :95-97)."""
         return min_area_pixels_of(self.im_info.dim_res, self.min_radius_um, no_z=self.im_info.no_z)
 
     def _get_pipeline(self, shape3) -> FramePipeline:
-        if self._pipeline is None or self._pipeline.shape != tuple(shape3):
-            if self._pipeline is not None:
-                self._pipeline.close()
-            self._pipeline = FramePipeline(shape3, device=self.device_index)
-        return self._pipeline
+        key = shape_key(shape3)
+        return self._held_pipeline.get(key, lambda: FramePipeline(key, device=self.device_index))
 
     def _shard_spec(self):
-        from nellie_amd.engine import ShardSpec
-        shard = self.shard if self.shard is not None else (os.environ.get("NELLIE_SHARD") or None)
-        if isinstance(shard, str):
-            if shard != "env":
-                raise ValueError("shard must be 'env' or an engine.ShardSpec")
-            shard = ShardSpec.from_env(rendezvous_dir=os.path.dirname(self.im_info.pipeline_paths["im_instance_label"]))
-        return shard
+        return resolve_shard(self.shard, rendezvous_dir=os.path.dirname(self.im_info.pipeline_paths["im_instance_label"]))
 
     def _engine_params(self):
         from nellie_amd.pipeline import FilterParams
@@ -122,29 +99,13 @@ class Label:
     def _get_engine(self, shape3):
         """Z slabs of a frame of this shape (nellie_amd/engine.py; one ghost plane per side is all Label needs)."""
         from nellie_amd.engine import make_engine
-        key = tuple(int(s) for s in shape3)
-        if self._engine is None or self._engine_key != key:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = make_engine(key, self._engine_params(), device_index=self.device_index, devices=self.devices,
-                                       shard=self._shard_spec(), label_only=True)
-            self._engine_key = key
-        return self._engine
+        key = shape_key(shape3)
+        return self._held_engine.get(key, lambda: make_engine(key, self._engine_params(), device_index=self.device_index,
+                                                              devices=self.devices, shard=self._shard_spec(), label_only=True))
 
     def close(self):
-        if self._pipeline is not None:
-            self._pipeline.close()
-            self._pipeline = None
-        if self._engine is not None:
-            self._engine.close()
-            self._engine = None
-
-    def _get_t(self):
-        if self.num_t is None:
-            if self.im_info.no_t:
-                self.num_t = 1
-            else:
-                self.num_t = self.im_info.shape[self.im_info.axes.index('T')]
+        self._held_pipeline.close()
+        self._held_engine.close()
 
     def _allocate_memory(self, engine=None):
         """labelling.py:337-353.  Multi-process runs: rank 0 creates the label file, the others map it once it exists."""
@@ -152,15 +113,10 @@ class Label:
         self.im_memmap = self.im_info.get_memmap(self.im_info.im_path)
         self.frangi_memmap = self.im_info.get_memmap(self.im_info.pipeline_paths['im_preprocessed'])
         self.shape = self.frangi_memmap.shape
-        path = self.im_info.pipeline_paths['im_instance_label']
-        multi = engine is not None and engine.kind == "rank-slab"
-        if not multi or engine.spec.rank == 0:
-            self.instance_label_memmap = self.im_info.allocate_memory(
-                path, dtype='int32', description='instance segmentation', return_memmap=True)
-        if multi:
-            engine.barrier()
-            if engine.spec.rank != 0:
-                self.instance_label_memmap = self.im_info.get_memmap(path)
+        barrier = engine.barrier if engine is not None and engine.kind == "rank-slab" else None
+        self.instance_label_memmap, = open_outputs(
+            self.im_info, [(self.im_info.pipeline_paths['im_instance_label'], 'int32', 'instance segmentation')],
+            creator=barrier is None or engine.spec.rank == 0, announce=barrier, wait=barrier)
 
     def _get_frame_views(self, t):
         return self.im_memmap[t, ...], self.frangi_memmap[t, ...]
@@ -289,8 +245,8 @@ class Label:
             if (t + 1) % self.flush_interval == 0:
                 self.instance_label_memmap.flush()
         self.instance_label_memmap.flush()
-        if self._engine is not None:
-            self._engine.barrier()
+        if self._held_engine.obj is not None:
+            self._held_engine.obj.barrier()
 
     def run(self):
         """labelling.py:736-778."""

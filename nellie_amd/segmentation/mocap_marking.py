@@ -13,14 +13,16 @@ chunked path gives the same results as its full-frame path); there is no CPU eng
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from nellie_amd.pipeline import FramePipeline, marker_sigmas
-from nellie_amd.utils import adaptive_run
+from nellie_amd.stage import FrameCounted, Held, flush, frame_count, open_outputs, require_gpu, resolve_device, resolve_shard, shape_key
 from nellie_amd.utils.base_logger import logger
 
 
-class Markers:
+class Markers(FrameCounted):
     def __init__(self, im_info, num_t=None, min_radius_um=0.20, max_radius_um=1, use_im="distance", num_sigma=5,
                  viewer=None, prefer_gpu=True, peak_min_distance=2, device="auto", low_memory=False,
                  max_chunk_voxels=int(1e6), device_index: int = 0, devices=None, shard=None):
@@ -33,11 +35,7 @@ class Markers:
         self.im_info = im_info
         self.devices = list(devices) if devices else None
         self.shard = shard
-        self.num_t = num_t
-        if self.im_info.no_t:
-            self.num_t = 1
-        elif num_t is None:
-            self.num_t = im_info.shape[im_info.axes.index("T")]
+        self.num_t = 1 if self.im_info.no_t else frame_count(im_info, num_t)
         x_res = self.im_info.dim_res.get("X") or 1.0
         z_res = self.im_info.dim_res.get("Z") or x_res
         self.z_ratio = float(z_res) / float(x_res) if not self.im_info.no_z else 1.0
@@ -53,33 +51,21 @@ class Markers:
         self.im_marker_memmap = self.im_distance_memmap = self.im_border_memmap = None
         self.debug = None
         self.viewer = viewer
-        dev = str(device or "auto").lower()
-        if dev not in ("auto", "cpu", "gpu", "cuda", "hip"):
-            raise ValueError(f"Unsupported device '{device}'. Use 'auto', 'cpu', or 'gpu'.")
-        if dev == "cpu" or (dev == "auto" and not prefer_gpu):
-            raise RuntimeError("nellie_amd provides the MI355X HIP backend only: device='cpu' is not available "
-                               "(no CPU fallback exists in this package; use the reference implementation on CPU)")
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
+        self.device_type = resolve_device(device, prefer_gpu)
+        require_gpu()
         self.device = device or "auto"
-        self.device_type = "hip"
         self.device_index = int(device_index)
         self.use_gpu = True
         self.peak_min_distance = peak_min_distance
         self.low_memory = bool(low_memory)
         self.max_chunk_voxels = int(max_chunk_voxels)
         self.truncate = 4.0
-        self._pipeline = None
-        self._pipeline_key = None
+        self._held_pipeline = Held()
 
     # ------------------------------------------------------------------ setup (mocap_marking.py:329-417)
     def _set_default_sigmas(self):
         logger.debug("Setting sigma values.")
         self.sigmas, _ = marker_sigmas(self.im_info.dim_res, self.min_radius_um, self.max_radius_um, self.num_sigma)
-
-    def _get_t(self):
-        if self.num_t is None:
-            self.num_t = 1 if self.im_info.no_t else self.im_info.shape[self.im_info.axes.index("T")]
 
     def _allocate_memory(self):
         logger.debug("Allocating memory for mocap marking.")
@@ -95,31 +81,21 @@ class Markers:
         if spec is not None and spec.world > 1:                # a multi-process run meets through this launch's file rendezvous
             from nellie_amd.rendezvous import rendezvous_for
             self._rdv = rendezvous_for(spec, os.path.dirname(paths["im_border"]))
-        if spec is not None and spec.rank != 0:                # rank 0 creates the files, the others map them
-            self._rdv.wait("markers_files_ready")
-            self.im_marker_memmap = self.im_info.get_memmap(paths["im_marker"])
-            self.im_distance_memmap = self.im_info.get_memmap(paths["im_distance"])
-            self.im_border_memmap = self.im_info.get_memmap(paths["im_border"])
-            return
-        alloc = self.im_info.allocate_memory
-        self.im_marker_memmap = alloc(paths["im_marker"], dtype="uint8", description="mocap marker image", return_memmap=True)
-        self.im_distance_memmap = alloc(paths["im_distance"], dtype="float32", description="distance transform image", return_memmap=True)
-        self.im_border_memmap = alloc(paths["im_border"], dtype="uint8", description="border image", return_memmap=True)
-        if self._rdv is not None:
-            self._rdv.publish("markers_files_ready")
+        rdv = self._rdv
+        self.im_marker_memmap, self.im_distance_memmap, self.im_border_memmap = open_outputs(
+            self.im_info, [(paths["im_marker"], "uint8", "mocap marker image"), (paths["im_distance"], "float32", "distance transform image"),
+                           (paths["im_border"], "uint8", "border image")],
+            creator=spec is None or spec.rank == 0,
+            announce=rdv and (lambda: rdv.publish("markers_files_ready")), wait=rdv and (lambda: rdv.wait("markers_files_ready")))
 
     def _get_pipeline(self, shape) -> FramePipeline:
-        key = tuple(int(s) for s in shape)
-        if self._pipeline is None or self._pipeline_key != key:
-            self.close()
-            self._pipeline = FramePipeline(key, device=self.device_index)
-            self._pipeline_key = key
-        return self._pipeline
+        key = shape_key(shape)
+        if self._held_pipeline.key != key:
+            self.close()                                       # (a subclass's close sees the change of shape)
+        return self._held_pipeline.get(key, lambda: FramePipeline(key, device=self.device_index))
 
     def close(self):
-        if self._pipeline is not None:
-            self._pipeline.close()
-            self._pipeline = None
+        self._held_pipeline.close()
 
     # ------------------------------------------------------------------ frames (mocap_marking.py:648-703)
     def _run_frame_impl(self, t, low_memory=False, chunk_voxels=None):
@@ -153,10 +129,8 @@ class Markers:
 
     def _slab_plan(self, shape3):
         """(slab count, this process's (rank, world) or None) for a frame of this shape."""
-        import os
-        from nellie_amd.engine import ShardSpec, slabs_needed
-        shard = self.shard if self.shard is not None else (os.environ.get("NELLIE_SHARD") or None)
-        spec = ShardSpec.from_env() if shard == "env" else shard
+        from nellie_amd.engine import slabs_needed
+        spec = resolve_shard(self.shard)
         if self.im_info.no_z:
             return 1, None
         if spec is not None and spec.world > 1:
@@ -237,9 +211,7 @@ class Markers:
             n_slabs, spec = self._slab_plan(self.label_memmap.shape[1:]) if self.label_memmap.ndim == 4 else (1, None)
             if n_slabs > 1:
                 self._run_frame_as_slabs(t, n_slabs, spec)
-                for mm in (self.im_marker_memmap, self.im_distance_memmap, self.im_border_memmap):
-                    if hasattr(mm, "flush"):
-                        mm.flush()
+                flush(self.im_marker_memmap, self.im_distance_memmap, self.im_border_memmap)
                 continue
             marker, distance, border = self._run_frame(t)
             if self.im_info.no_t or self.num_t == 1 and self.im_marker_memmap.ndim == marker.ndim:
@@ -250,9 +222,7 @@ class Markers:
                 self.im_marker_memmap[t] = marker
                 self.im_distance_memmap[t] = distance
                 self.im_border_memmap[t] = border
-            for mm in (self.im_marker_memmap, self.im_distance_memmap, self.im_border_memmap):
-                if hasattr(mm, "flush"):
-                    mm.flush()
+            flush(self.im_marker_memmap, self.im_distance_memmap, self.im_border_memmap)
 
     def run(self):
         logger.info("Running Markers (HIP).")

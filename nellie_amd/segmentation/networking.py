@@ -22,7 +22,7 @@ import zlib
 import numpy as np
 
 from nellie_amd import hipnative
-from nellie_amd.utils import adaptive_run
+from nellie_amd.stage import Held, require_gpu
 
 
 def _ctx_shape(shape):
@@ -37,25 +37,21 @@ def _ctx_shape(shape):
 class HipNetworkKernels:
     """Mixin / helper holding one HIP context per frame shape."""
 
-    _hip_ctx = None
-    _hip_ctx_key = None
+    _held_ctx = None                      # a Held of this object's own from the first context on (a mixin has no constructor)
     device_index = 0
 
     def _hip_context(self, shape):
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
+        require_gpu()
         key = (_ctx_shape(shape), int(getattr(self, "device_index", 0) or 0))
-        if self._hip_ctx is None or self._hip_ctx_key != key:
+        if self._held_ctx is None:
+            self._held_ctx = Held()
+        if self._held_ctx.key != key:
             self.close()
-            self._hip_ctx = hipnative.Context(key[0], device=key[1])
-            self._hip_ctx_key = key
-        return self._hip_ctx
+        return self._held_ctx.get(key, lambda: hipnative.Context(key[0], device=key[1]))
 
     def close(self):
-        if self._hip_ctx is not None:
-            self._hip_ctx.close()
-        self._hip_ctx = None
-        self._hip_ctx_key = None
+        if self._held_ctx is not None:
+            self._held_ctx.close()
 
     @staticmethod
     def _no_cpu(force_cpu):

@@ -14,26 +14,18 @@ from __future__ import annotations
 
 import numpy as np
 
-from nellie_amd.utils import adaptive_run
+from nellie_amd.stage import FrameCounted, frame_count, require_gpu, scaled_max_distance, spacing_of
 from nellie_amd.utils.base_logger import logger
 
 
-class FlowInterpolator:
+class FlowInterpolator(FrameCounted):
     def __init__(self, im_info, num_t=None, max_distance_um=0.5, forward=True, device_index: int = 0):
         self.im_info = im_info
         if self.im_info.no_t:
             return
-        self.num_t = num_t
-        if num_t is None:
-            self.num_t = im_info.shape[im_info.axes.index("T")]
-        if self.im_info.no_z:
-            self.scaling = (im_info.dim_res["Y"], im_info.dim_res["X"])
-        else:
-            self.scaling = (im_info.dim_res["Z"], im_info.dim_res["Y"], im_info.dim_res["X"])
-        dt = self.im_info.dim_res.get("T") or 1.0
-        if self.im_info.dim_res.get("T") is None:
-            logger.warning("Time resolution missing; assuming 1.0s for max_distance_um scaling.")
-        self.max_distance_um = np.max(np.array([max_distance_um * dt, 0.5]))
+        self.num_t = frame_count(im_info, num_t)
+        self.scaling = spacing_of(im_info)
+        self.max_distance_um = np.float64(scaled_max_distance(im_info, max_distance_um))     # (the reference's is numpy's)
         self.forward = forward
         self.device_index = int(device_index)
         self.shape = ()
@@ -45,8 +37,7 @@ class FlowInterpolator:
         self.check_coords = None
         self.debug = None
         self._field = None
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
+        require_gpu()
         self._initialize()
 
     def _allocate_memory(self):
@@ -54,10 +45,6 @@ class FlowInterpolator:
         self.im_memmap = self.im_info.get_memmap(self.im_info.im_path)
         self.shape = self.im_memmap.shape
         self.flow_vector_array = np.load(self.im_info.pipeline_paths["flow_vector_array"])
-
-    def _get_t(self):
-        if self.num_t is None:
-            self.num_t = 1 if self.im_info.no_t else self.im_info.shape[self.im_info.axes.index("T")]
 
     def _initialize(self):
         if self.im_info.no_t:

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from nellie_amd.utils import adaptive_run
+from nellie_amd.stage import frame_count, require_gpu, resolve_device, scaled_max_distance, spacing_of
 from nellie_amd.utils.base_logger import logger
 
 
@@ -45,16 +45,10 @@ class HuMomentTracking:
                  max_dense_pairs=int(1e7), max_dense_roi_voxels_cpu=int(5e7), max_dense_roi_voxels_gpu=int(2e7),
                  low_memory=False, device_index: int = 0):
         self.im_info = im_info
-        dev = str(device or "auto").lower()
-        if dev not in ("auto", "cpu", "gpu", "cuda", "hip"):
-            raise ValueError(f"Unsupported device '{device}'. Use 'auto', 'cpu', or 'gpu'.")
-        if dev == "cpu":
-            raise RuntimeError("nellie_amd provides the MI355X HIP backend only: device='cpu' is not available "
-                               "(no CPU fallback exists in this package; use the reference implementation on CPU)")
+        self.device_type = resolve_device(device)
         if mode not in ("auto", "dense", "sparse"):
             raise ValueError(f"Unsupported mode '{mode}'. Use 'auto', 'dense' or 'sparse'.")
         self.device = device or "auto"
-        self.device_type = "hip"
         self.device_index = int(device_index)
         self.viewer = viewer
         self.mode = mode
@@ -66,18 +60,10 @@ class HuMomentTracking:
         self.flow_vector_array_path = None
         if self.im_info.no_t:
             return
-        if num_t is None:
-            self.num_t = im_info.shape[im_info.axes.index("T")]
-        if self.im_info.no_z:
-            self.scaling = (im_info.dim_res["Y"], im_info.dim_res["X"])
-        else:
-            self.scaling = (im_info.dim_res["Z"], im_info.dim_res["Y"], im_info.dim_res["X"])
-        dt = self.im_info.dim_res.get("T") or 1.0
-        if self.im_info.dim_res.get("T") is None:
-            logger.warning("Time resolution missing; assuming 1.0s for max_distance_um scaling.")
-        self.max_distance_um = max(max_distance_um * dt, 0.5)
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
+        self.num_t = frame_count(im_info, num_t)
+        self.scaling = spacing_of(im_info)
+        self.max_distance_um = scaled_max_distance(im_info, max_distance_um)
+        require_gpu()
 
     def _allocate_memory(self):
         paths = self.im_info.pipeline_paths

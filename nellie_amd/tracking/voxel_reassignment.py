@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from nellie_amd.utils import adaptive_run
+from nellie_amd.stage import FrameCounted, flush, frame_count, require_gpu, resolve_device
 from nellie_amd.utils.base_logger import logger
 
 
@@ -30,19 +30,13 @@ def select_match_coord_dtype(spatial_shape):
     return np.uint64
 
 
-class VoxelReassigner:
+class VoxelReassigner(FrameCounted):
     def __init__(self, im_info, num_t=None, viewer=None, store_running_matches: bool = True, max_refine_iterations: int = 3,
                  device: str = "auto", low_memory: bool = False, max_query_points: int = int(1e6),
                  max_bruteforce_pairs: int = int(1e7), device_index: int = 0):
         self.im_info = im_info
-        dev = str(device or "auto").lower()
-        if dev not in ("auto", "cpu", "gpu", "cuda", "hip"):
-            raise ValueError(f"Unsupported device '{device}'. Use 'auto', 'cpu', or 'gpu'.")
-        if dev == "cpu":
-            raise RuntimeError("nellie_amd provides the MI355X HIP backend only: device='cpu' is not available "
-                               "(no CPU fallback exists in this package; use the reference implementation on CPU)")
+        self.device_type = resolve_device(device)
         self.device = device or "auto"
-        self.device_type = "hip"
         self.device_index = int(device_index)
         self.low_memory = bool(low_memory)                       # accepted, ignored (module docstring)
         self.max_query_points = max(1, int(max_query_points))
@@ -64,19 +58,10 @@ class VoxelReassigner:
         self.match_coord_dtype = None
         self.kernel_ms = []                                      # device time per frame pair of the last run
         self._reassigner = None
-        if self.im_info.no_t:
-            self.num_t = 1
-            return
-        self.num_t = num_t
-        if num_t is None:
-            self.num_t = im_info.shape[im_info.axes.index("T")]
+        self.num_t = 1 if self.im_info.no_t else frame_count(im_info, num_t)
 
     def _select_match_coord_dtype(self):
         return select_match_coord_dtype(self.spatial_shape)
-
-    def _get_t(self):
-        if self.num_t is None:
-            self.num_t = 1 if self.im_info.no_t else self.im_info.shape[self.im_info.axes.index("T")]
 
     def _allocate_memory(self):
         """voxel_reassignment.py:859-887"""
@@ -145,9 +130,7 @@ class VoxelReassigner:
                 self.running_matches.append([best_prev.astype(match_dtype, copy=False), best_next.astype(match_dtype, copy=False)])
             self._write_frame(t + 1, vox_next, re_b, re_o)
             vox_prev, n_prev = vox_next, n_next
-        for memmap in (self.reassigned_branch_memmap, self.reassigned_obj_memmap):
-            if hasattr(memmap, "flush"):
-                memmap.flush()
+        flush(self.reassigned_branch_memmap, self.reassigned_obj_memmap)
         if self.store_running_matches and self.voxel_matches_path is not None:
             np.save(self.voxel_matches_path, np.array(self.running_matches, dtype=object))
 
@@ -155,8 +138,7 @@ class VoxelReassigner:
         if self.im_info.no_t:
             logger.info("Skipping voxel reassignment for non-temporal dataset.")
             return
-        if not adaptive_run.gpu_available():
-            raise RuntimeError("GPU backend requested but no HIP device / libnellie_hip.so is available.")
+        require_gpu()
         logger.info("Running voxel reassignment (HIP).")
         try:
             self._run_reassignment()

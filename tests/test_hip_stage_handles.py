@@ -1,6 +1,7 @@
 """GPU tests of what the four stage handles share (csrc/nl_stage.h, csrc/rank_scan.inc, hipnative._Handle): the lifecycle of every
 class in 2-D and 3-D, and the shared mask / scan / compaction and query-coordinate kernels at the smallest frames whose scan
-crosses a workgroup boundary.  Every expectation comes from numpy."""
+crosses a workgroup boundary; and the one device object per frame shape the stage classes hold (nellie_amd/stage.py).  Every
+expectation comes from numpy or from a fresh object of the same library."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -175,3 +176,71 @@ def test_query_coordinates_match_unravel_index(hip, frame):
         for seed in (True, False):
             r.frame(comp, comp, seed=seed)
         assert r.pair(field, None) == want
+
+
+# ---- one device object per frame shape -----------------------------------------------------------------------------------------------
+def test_filter_holds_one_pipeline_per_shape(hip):
+    """Asked for another shape, a stage closes the pipeline it has (its context with it) and builds the next; the new one computes
+    what a pipeline of its own computes, bit for bit; after close() the stage starts over."""
+    from fakes import ArrayImInfo
+    from nellie_amd.pipeline import FramePipeline
+    from nellie_amd.segmentation.filtering import Filter
+    from nellie_amd.synthetic import make_volume
+    vol = make_volume((8, 16, 24), 5)
+    f = Filter(ArrayImInfo(vol[None], {"X": 0.1, "Y": 0.1, "Z": 0.1, "T": 1.0}))
+    zeros = np.zeros((8, 16, 16), np.float32)
+    try:
+        first = f._get_pipeline((8, 16, 16))
+        first.upload_frangi(zeros)
+        second = f._get_pipeline((8, 16, 24))
+        assert second is not first and f._get_pipeline((8, 16, 24)) is second
+        with pytest.raises(NellieHipError, match="context is closed") as e:
+            first.upload_frangi(zeros)
+        assert e.value.code == NL_ESTATE
+        second.filter(vol, f._params())
+        got = second.download_frangi()
+        fresh = FramePipeline((8, 16, 24))
+        try:
+            fresh.filter(vol, f._params())
+            want = fresh.download_frangi()
+        finally:
+            fresh.close()
+        assert got.dtype == np.float32 and got.shape == vol.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+        f.close()
+        with pytest.raises(NellieHipError, match="context is closed"):
+            second.download_frangi()
+        third = f._get_pipeline((8, 16, 24))
+        assert third is not second
+        third.upload_frangi(want)
+    finally:
+        f.close()
+        f.close()
+
+
+def test_network_kernels_hold_one_context_per_shape(hip):
+    from nellie_amd.segmentation.networking import HipNetworkKernels
+    rng = np.random.default_rng(16)
+    skel2 = (rng.random((16, 16)) < 0.3).astype(np.int32)
+    skel3 = (rng.random((4, 16, 16)) < 0.2).astype(np.int32)
+    k = HipNetworkKernels()
+    try:
+        first = k._hip_context(skel2.shape)
+        assert first.shape == (1, 16, 16) and k._get_pixel_class(skel2).shape == skel2.shape and k._hip_context((16, 16)) is first
+        second = k._hip_context(skel3.shape)
+        assert second is not first and k._hip_context((4, 16, 16)) is second
+        with pytest.raises(NellieHipError, match="context is closed") as e:
+            first.skel_pixel_class(skel2)
+        assert e.value.code == NL_ESTATE
+        got = k._get_pixel_class(skel3)
+        assert k._hip_context(skel3.shape) is second
+        with hip.Context((4, 16, 16)) as fresh:
+            want, n = fresh.skel_pixel_class(skel3)
+        assert n == int(skel3.sum()) == k.n_skeleton_voxels and got.dtype == np.uint8 and np.array_equal(got, want)
+        k.close()
+        with pytest.raises(NellieHipError, match="context is closed"):
+            second.skel_pixel_class(skel3)
+        third = k._hip_context(skel3.shape)
+        assert third is not second and np.array_equal(third.skel_pixel_class(skel3)[0], want)
+    finally:
+        k.close()
+        k.close()
