@@ -624,6 +624,9 @@ majority_bits_kernel(const unsigned long long *__restrict__ in, unsigned long lo
 // and the zero stores back to back 1.12 / 0.51; the volume cleared by a fill (6.4 TB/s) and only rows with runs touched 0.66 + 0.40 /
 // 0.32 + 0.16; the same with a wave looking at 64 rows and painting those with runs in turn 0.66 + 0.39 / 0.32 + 0.31 -- most rows of
 // these frames hold runs, and a 4 B/voxel write stream wants many short waves.)
+// SPARSE: `out` is already all zero on these rows (a fill beside the last scale's walk: nl_gauss_step) -- only the voxels inside the
+// runs are stored, a row without runs costs its two offsets.
+template <bool SPARSE>
 __global__ void __launch_bounds__(256)
 rl_paint_kernel(const unsigned long long *__restrict__ bits, const unsigned int *__restrict__ row_off, const int *__restrict__ parent,
                 const int *__restrict__ newid, int *__restrict__ out, i64 row0, i64 row1, int wpr, int nx) {
@@ -637,6 +640,7 @@ rl_paint_kernel(const unsigned long long *__restrict__ bits, const unsigned int 
         // them voxel by voxel inside the word loop would expose that latency once per non-empty word
         int *orow = out + (row - row0) * nx;
         const bool vec = ((nx & 3) == 0) && ((reinterpret_cast<size_t>(orow) & 15) == 0);
+        if (SPARSE && nr == 0u) continue;
         if (nr == 0u && vec) {                  // a row without runs (most rows): zeros, without looking at the mask
             for (int q = lane; q < nx / 4; q += 64) reinterpret_cast<int4 *>(orow)[q] = make_int4(0, 0, 0, 0);
             continue;
@@ -645,11 +649,13 @@ rl_paint_kernel(const unsigned long long *__restrict__ bits, const unsigned int 
         if (vec) {
             // a row with runs: zeros first, in four wide stores like an empty row, then only the words that hold voxels are
             // visited -- a row has a handful of runs, not 16 words' worth
+            if (!SPARSE) {
             for (int q = lane; q < nx / 4; q += 64) reinterpret_cast<int4 *>(orow)[q] = make_int4(0, 0, 0, 0);
             // the label stores below hit addresses the zero stores also wrote, from other lanes: wait until the zeros have been
             // acknowledged instead of relying on the order in which two stores of one wave reach L2 (the lookups of this row's
             // labels above are in flight meanwhile, other waves fill the time)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
             unsigned long long carry = 0;
             int prev_w = -2;                     // last visited word: a run continues from it only if it is the word before
             for (int wb = 0; wb < wpr; wb += 64) {
@@ -692,7 +698,7 @@ rl_paint_kernel(const unsigned long long *__restrict__ bits, const unsigned int 
                 const unsigned int rl = set ? (seen - seen0) + (unsigned int)__builtin_popcountll(below) - 1u : 0u;
                 int lab = __shfl(lab_mine, (int)(rl & 63u), 64);
                 if (set && rl >= 64u) lab = newid[parent[seen0 + rl]];
-                if (x < nx) orow[x] = set ? lab : 0;
+                if (x < nx && (set || !SPARSE)) orow[x] = set ? lab : 0;
                 seen += (unsigned int)__builtin_popcountll(starts);
                 carry = v >> 63;
             }

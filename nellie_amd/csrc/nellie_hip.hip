@@ -479,6 +479,7 @@ extern "C" int nl_filter_load(nl_ctx *c, const void *host, int dtype, int64_t z0
     NL_JOIN_SIDE(c);
     if (!host || z0 < 0 || z1 > c->nzl || z0 >= z1) return nl_fail(err, errlen, NL_EINVAL, "bad plane range [%lld,%lld)", (i64)z0, (i64)z1);
     c->i_gauss = 0; c->i_vmax = 3; c->i_labels = -1; c->frangi_ready = 0;
+    c->pz_on = 0; c->prezero_used = 0;
     c->gauss_ext = nullptr;
     // a frame abandoned between nl_gauss_step_ahead and nl_gauss_commit (an exception in the host's scale loop) leaves a cascade step on the
     // side stream that still writes the ping-pong volumes: this frame's first kernels come after it
@@ -519,6 +520,7 @@ extern "C" int nl_filter_begin(nl_ctx *c, char *err, size_t errlen) {
     NL_JOIN_SIDE(c);
     if (!c->d_input) return nl_fail(err, errlen, NL_ESTATE, "nl_filter_begin before nl_input_load");
     c->i_gauss = 0; c->i_vmax = 3; c->i_labels = -1; c->frangi_ready = 0;
+    c->pz_on = 0; c->prezero_used = 0;
     c->mask_slots_used = 0;
     c->gauss_ext = nullptr;
     // a frame abandoned between nl_gauss_step_ahead and nl_gauss_commit (an exception in the host's scale loop) leaves a cascade step on the
@@ -608,9 +610,15 @@ extern "C" int nl_gauss_step(nl_ctx *c, const double *wz, int rz, const double *
         static int zero_in_passing = -1;
         if (zero_in_passing < 0) { const char *e = getenv("NELLIE_ZERO_IN_GAUSS"); zero_in_passing = (e && !atoi(e)) ? 0 : 1; }
         const bool zero = zero_in_passing && c->mask_slots_used == 0 && c->vmax_zero_hi == 0 && c->stream != c->side;
-        (void)gl_zyx(c, rz, ry, srcp, c->f[dst], v, z0, z1, gauss_ws_of(gw), gauss_ws_of(gy), zero ? c->f[c->i_vmax] : nullptr);
+        // ... and the chain's last step the volume Label will paint into: the third ping-pong volume, dead since the step before and
+        // for the rest of the frame (nl_chain_begin: pz_on).  A step running ahead is enqueued one nl_chain_scale earlier.
+        const bool ahead = c->stream == c->side;
+        const bool prezero = !zero && c->pz_on && c->chain_n > 0 && c->chain_k == c->chain_n - (ahead ? 2 : 1) && z0 == 0 && z1 == c->nzl;
+        float *third = c->f[(src + 2) % 3];
+        (void)gl_zyx(c, rz, ry, srcp, c->f[dst], v, z0, z1, gauss_ws_of(gw), gauss_ws_of(gy), zero ? c->f[c->i_vmax] : (prezero ? third : nullptr));
         if (zero) { c->vmax_zero_lo = z0; c->vmax_zero_hi = z1; }
         NL_CHECK_LAUNCH();
+        if (prezero) pz_set(c, third);
         src = dst; srcp = c->f[dst];
         fused_yx = true;
         wz = nullptr;
@@ -693,7 +701,7 @@ extern "C" int nl_gauss_step_ahead(nl_ctx *c, const double *wz, int rz, const do
 }
 
 extern "C" int nl_gauss_commit(nl_ctx *c, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     if (!c->ahead_pending) return nl_fail(err, errlen, NL_ESTATE, "nl_gauss_commit without nl_gauss_step_ahead");
     NL_HIP(hipStreamWaitEvent(c->stream, c->ev_ahead, 0));
     c->i_gauss = c->ahead_gauss;
@@ -1561,13 +1569,17 @@ extern "C" int nl_chain_begin(nl_ctx *c, int n_scales, char *err, size_t errlen)
     NL_CHECK_LAUNCH();
     c->chain_n = n_scales; c->chain_k = 0; c->chain_copy_pending = 0;
     c->def_resolve = 0;
+    // NELLIE_PREZERO=0: the frame's outputs are written densely, as before (read per frame: one process can run both ways).  A whole
+    // 3-D volume on one context only: slabs, images and everything outside the chain keep the dense kernels.
+    const char *e_pz = getenv("NELLIE_PREZERO");
+    c->pz_on = (e_pz ? atoi(e_pz) != 0 : NL_PREZERO_DEFAULT) && !c->two_d && !c->comm && c->own_lo == 0 && c->own_hi == c->nzl && c->nzl == c->gnz;
     return NL_OK;
 }
 
 // One scale of the frame, enqueued without a single wait: see chain.inc.  The Gaussian of the scale is current (nl_gauss_step).
 extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, int64_t sy, int64_t sx, double alpha_sq, double beta_sq,
                               double division, double margin, double test_scale, int64_t z0, int64_t z1, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);          // (the threshold kernels, the walk and the resolve kernel use no free volume)
     if (!c->d_chain || c->chain_k >= c->chain_n) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_scale outside nl_chain_begin .. nl_chain_finish");
     if (!(division != 0.0)) return nl_fail(err, errlen, NL_EINVAL, "the chain needs a non-zero threshold division");
     int rc;
@@ -1677,7 +1689,7 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
 // of the frame's percentile threshold) runs on the device while nl_chain_finish waits for the records only and repeats the
 // decisions on the host.
 extern "C" int nl_chain_flush(nl_ctx *c, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     if (!c->d_chain || c->chain_k < 1) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_flush without scales");
     { int rcd = resolve_deferred_launch(c, false, err, errlen); if (rcd) return rcd; }       // the last scale's: nothing left to run beside
     NL_JOIN_SIDE(c);
@@ -1690,7 +1702,7 @@ extern "C" int nl_chain_flush(nl_ctx *c, char *err, size_t errlen) {
 // The one wait of the frame: per scale flags (0 = the chain's result stands), gamma, max |H|, the Frobenius threshold and this
 // context's h_mask count.  Any non-zero flag: redo the frame the synchronous way.
 extern "C" int nl_chain_finish(nl_ctx *c, int *flags, double *gamma, double *max_abs, double *thr, int64_t *mask_count, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     if (!c->d_chain || c->chain_k < 1) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_finish without scales");
     const int n = c->chain_k;
     if (!c->chain_copy_pending) { int rcd = resolve_deferred_launch(c, false, err, errlen); if (rcd) return rcd; }
@@ -1711,7 +1723,7 @@ extern "C" int nl_chain_finish(nl_ctx *c, int *flags, double *gamma, double *max
         if (thr) thr[k] = (double)h[k].thr;
         if (mask_count) mask_count[k] = (int64_t)(h[k].cnt_walk + h[k].cnt_resolve);
     }
-    c->chain_n = 0;
+    c->chain_n = 0; c->pz_on = 0;
     return NL_OK;
 }
 
@@ -1977,7 +1989,9 @@ extern "C" int nl_mask_volume(nl_ctx *c, float thr, char *err, size_t errlen) {
 // Writes the masked frame into the free volume *dst_out; the caller commits it (swap with i_vmax) or not.
 static int mask_volume_fused_enqueue(nl_ctx *c, float thr, const float *thr_dev, unsigned long long *d_cnt, int *dst_out, char *err, size_t errlen) {
     int dst = -1;
-    for (int k = 0; k < 3; ++k) if (k != c->i_gauss) { dst = k; break; }
+    for (int k = 0; k < 3; ++k) if (k != c->i_gauss && !pz_is(c, c->f[k])) { dst = k; break; }      // (not the pre-zeroed label volume)
+    if (dst < 0) for (int k = 0; k < 3; ++k) if (k != c->i_gauss) { dst = k; break; }
+    pz_touch(c, c->f[dst]);
     *dst_out = dst;
     NL_HIP(zero_small(d_cnt, 8, c->stream));
     ProfScope ps(c, "mask_volume");
@@ -2017,7 +2031,7 @@ static void mask_volume_fused_commit(nl_ctx *c, int dst) {
 }
 
 extern "C" int nl_mask_volume_fused(nl_ctx *c, float thr, int64_t *n_positive, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     if (c->mask_slots_used == 0) return nl_fail(err, errlen, NL_ESTATE, "nl_mask_volume_fused before any scale was evaluated");
     NL_JOIN_SIDE(c);
     unsigned long long *d_cnt = (unsigned long long *)c->d_small;
@@ -2064,7 +2078,7 @@ static int pct_enqueue(nl_ctx *c, const float *samples, const unsigned int *d_n,
    (strides sz, sy, sx), their q-th percentile (numpy's float32 'linear' rule, selected on the device), the percentile mask, its
    opening and the product.  Nothing is committed yet: nl_tail_finish waits, reports and (commit != 0) makes the result the frame. */
 extern "C" int nl_tail_enqueue(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx, double q, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     if (c->mask_slots_used == 0) return nl_fail(err, errlen, NL_ESTATE, "nl_tail_enqueue before any scale was evaluated");
     if (c->two_d) return nl_fail(err, errlen, NL_EINVAL, "nl_tail_enqueue is the 3-D epilogue");
     int rc;
@@ -2076,6 +2090,9 @@ extern "C" int nl_tail_enqueue(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx, do
     if (total > c->n) return nl_fail(err, errlen, NL_EINVAL, "lattice larger than the volume");
     float *stage = c->f[(c->i_gauss + 1) % 3];
     if (stage == c->f[c->i_vmax]) return nl_fail(err, errlen, NL_ESTATE, "no free volume for the samples");
+    // the pre-zeroed label volume is that very volume (the one after the current Gaussian): the samples borrow its first `total` words,
+    // which are zeroed again once the percentile is selected (a few MB)
+    const bool stage_pz = pz_is(c, stage);
     unsigned int *d_n = (unsigned int *)((char *)c->d_pct + 64);
     unsigned long long *d_cnt = (unsigned long long *)((char *)c->d_pct + 72);
     NL_HIP(zero_small(d_n, 4, c->stream));
@@ -2085,6 +2102,7 @@ extern "C" int nl_tail_enqueue(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx, do
         NL_CHECK_LAUNCH();
     }
     if ((rc = pct_enqueue(c, stage, d_n, total, (float)q, err, errlen))) return rc;
+    if (stage_pz && total > 0) NL_HIP(hipMemsetAsync(stage, 0, (size_t)total * 4, c->stream));
     // the samples sit in a volume the epilogue may write (dst): the selection above is complete before it does (stream order)
     int dst;
     if ((rc = mask_volume_fused_enqueue(c, 0.0f, &((PctRec *)c->d_pct)->thr, d_cnt, &dst, err, errlen))) return rc;
@@ -2095,7 +2113,7 @@ extern "C" int nl_tail_enqueue(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx, do
 
 extern "C" int nl_tail_finish(nl_ctx *c, int commit, int64_t *n_samples, float *a, float *b, float *gamma, float *thr, int64_t *n_positive,
                               char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     if (!c->tail_pending) return nl_fail(err, errlen, NL_ESTATE, "nl_tail_finish without nl_tail_enqueue");
     NL_HIP(hipStreamSynchronize(c->stream));
     c->tail_pending = 0;
@@ -2184,7 +2202,7 @@ int store_planes(nl_ctx *c, const void *dev_base, void *host, size_t elem, int64
 }
 
 extern "C" int nl_filter_store(nl_ctx *c, float *host, int64_t z0, int64_t z1, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     NL_KEEP_LABBITS(c);
     NL_KEEP_SUPPORT(c);
     return store_planes(c, c->f[c->i_vmax], host, 4, z0, z1, err, errlen);
@@ -2545,7 +2563,7 @@ extern "C" int nl_allgather_var(nl_ctx *c, const void *send, int64_t nbytes, voi
 // ---- Label's threshold sampling (flat strided samples of the Frangi volume, labelling.py:426-433) ----
 extern "C" int nl_flat_sample_gather(nl_ctx *c, int field, int64_t offset, int64_t step, float *out, int64_t cap, int64_t *n,
                                      char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     NL_KEEP_SUPPORT(c);
     if (step < 1 || offset < 0) return nl_fail(err, errlen, NL_EINVAL, "bad offset/step");
     if (field != NL_FIELD_FRANGI && field != NL_FIELD_GAUSS) return nl_fail(err, errlen, NL_EINVAL, "flat sampling supports GAUSS/FRANGI");
@@ -2560,8 +2578,10 @@ extern "C" int nl_flat_sample_gather(nl_ctx *c, int field, int64_t offset, int64
     if (count == 0 || (!out && cap == 0)) return NL_OK;   // size query
     if (!out || cap < count) return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld < %lld samples", (i64)cap, count);
     const float *src = (field == NL_FIELD_FRANGI) ? c->f[c->i_vmax] : gauss_cur(c);
-    float *stage = nullptr;
-    for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src) { stage = c->f[k]; break; }
+    float *stage = nullptr;                                  // a free volume, not the pre-zeroed one while there is another
+    for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src && !pz_is(c, c->f[k])) { stage = c->f[k]; break; }
+    if (!stage) for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src) { stage = c->f[k]; break; }
+    pz_touch(c, stage);
     {
         ProfScope ps(c, "sample");
         // local flat index = global - gz0*plane
@@ -2577,7 +2597,7 @@ extern "C" int nl_flat_sample_gather(nl_ctx *c, int field, int64_t offset, int64
 // values[values > 0]); order unspecified.  cap >= the count nl_flat_sample_gather reports.
 extern "C" int nl_flat_sample_gather_positive(nl_ctx *c, int field, int64_t offset, int64_t step, float *out, int64_t cap,
                                               int64_t *n, char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
     NL_KEEP_SUPPORT(c);
     if (step < 1 || offset < 0) return nl_fail(err, errlen, NL_EINVAL, "bad offset/step");
     if (field != NL_FIELD_FRANGI && field != NL_FIELD_GAUSS) return nl_fail(err, errlen, NL_EINVAL, "flat sampling supports GAUSS/FRANGI");
@@ -2591,8 +2611,10 @@ extern "C" int nl_flat_sample_gather_positive(nl_ctx *c, int field, int64_t offs
     if (count == 0) return NL_OK;
     if (!out || cap < count) return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld < %lld samples", (i64)cap, count);
     const float *src = (field == NL_FIELD_FRANGI) ? c->f[c->i_vmax] : gauss_cur(c);
-    float *stage = nullptr;
-    for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src) { stage = c->f[k]; break; }
+    float *stage = nullptr;                                  // a free volume, not the pre-zeroed one while there is another
+    for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src && !pz_is(c, c->f[k])) { stage = c->f[k]; break; }
+    if (!stage) for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src) { stage = c->f[k]; break; }
+    pz_touch(c, stage);
     unsigned int *d_n = (unsigned int *)c->d_small;
     NL_HIP(zero_small(d_n, 4, c->stream));
     {
@@ -2615,6 +2637,7 @@ extern "C" int nl_ctx_info(nl_ctx *c, const char *key, double *value) {
     else if (!strcmp(key, "last_fsq_min")) *value = c->last_fsq_min;
     else if (!strcmp(key, "last_spec_overflow")) *value = c->last_spec_overflow;
     else if (!strcmp(key, "last_label_sparse")) *value = c->last_label_sparse;
+    else if (!strcmp(key, "prezero_used")) *value = c->prezero_used;        // bit 1: the last frame's labels were painted into a pre-zeroed volume (bit 0, the Frangi volume: never)
     else if (!strcmp(key, "device_bytes")) *value = (double)nl_ctx_bytes(c->nzl, c->ny, c->nx);
     else if (!strcmp(key, "gauss_yx_max_r")) *value = getenv("NELLIE_NO_FUSED_YX") ? 0 : GM_MAX_R;   // largest in-plane radius whose Y and X passes share a kernel
     else if (!strcmp(key, "queue_entries")) {

@@ -11,7 +11,7 @@ extern "C" int nl_label_load_frangi(nl_ctx *c, const float *host, int64_t z0, in
     NL_ENTER(c);
     if (!host || z0 < 0 || z1 > c->nzl || z0 >= z1) return nl_fail(err, errlen, NL_EINVAL, "bad plane range [%lld,%lld)", (i64)z0, (i64)z1);
     const i64 plane = c->ny * c->nx;
-    c->i_vmax = 3; c->i_gauss = 0; c->i_labels = -1;
+    c->i_vmax = 3; c->i_gauss = 0; c->i_labels = -1; c->prezero_used = 0;
     NL_HIP(hipMemcpyAsync(c->f[c->i_vmax] + z0 * plane, host, (size_t)(z1 - z0) * plane * 4, hipMemcpyHostToDevice, c->stream));
     NL_HIP(hipStreamSynchronize(c->stream));
     c->frangi_ready = 1;
@@ -170,6 +170,7 @@ struct LabelGeo {
     i64 gz0 = 0, gnz = 0;         // placement of plane 0 of the run set in the global volume (boundary rules)
     bool rank_independent_bands = false;   // Z slab: the row bands of the in-LDS union level are a function of ny alone (build_components)
     bool whole_frame_paint = false;        // nl_label_run on a whole local volume: paint_out holds the frame's labels (the pack may follow, number_and_paint)
+    bool prezeroed = false;                // paint_out is all zero (NELLIE_PREZERO): the pair filter's slots are zeroed again after use, the paint is sparse
 };
 static void label_geo_whole(LabelGeo &g) { g.zf_lo = 0; g.zf_hi = (int)g.nz - 1; g.gz0 = 0; g.gnz = g.nz; }
 
@@ -251,10 +252,20 @@ static int build_components(nl_ctx *c, const LabelGeo &g, const unsigned long lo
     NL_CHECK_LAUNCH();
     ccl_flatten_kernel<<<gr, 256, 0, c->stream>>>(rs.parent, rs.nruns, rn.p, cap);
     NL_CHECK_LAUNCH();
+    if (lvl2 && g.prezeroed) {        // the pair filter borrowed one word per run of the pre-zeroed label volume
+        rl_fill_u32_kernel<<<gr, 256, 0, c->stream>>>((unsigned int *)link, 0u, rn);
+        NL_CHECK_LAUNCH();
+    }
     return NL_OK;
 }
 
 static int pack_enqueue_fwd(nl_ctx *c, int with_labels, const float *frangi, const int *labels, char *err, size_t errlen);
+// The three volumes Label works in, the label volume (`out`, one of them) last: [runs, parent + aux, labels].
+static void label_volumes(const nl_ctx *c, const int *out, int idx[3]) {
+    int nf = 0, io = -1;
+    for (int k = 0; k < 4; ++k) if (k != c->i_vmax) { if ((const int *)c->f[k] == out && io < 0) io = k; else idx[nf++] = k; }
+    idx[2] = io >= 0 ? io : idx[2];
+}
 // ids 1..K in raster order of each component's first voxel (scipy.ndimage.label numbering), painted as int32
 static int number_and_paint(nl_ctx *c, const LabelGeo &g, const RunSet &rs, int *aux, int64_t *n_labels, char *err, size_t errlen,
                             bool *overflow = nullptr) {
@@ -274,8 +285,12 @@ static int number_and_paint(nl_ctx *c, const LabelGeo &g, const RunSet &rs, int 
         NL_HIP(hipMemcpyAsync(c->h_small, d_total, 8, hipMemcpyDeviceToHost, c->stream));
         NL_HIP(hipMemcpyAsync((char *)c->h_small + 8, (unsigned int *)c->d_small + 60, 4, hipMemcpyDeviceToHost, c->stream));   // the overflow flag
     }
-    rl_paint_kernel<<<grid1d((g.paint_row1 - g.paint_row0) * 64, 256, (i64)1 << 22), 256, 0, c->stream>>>(
-        g.bitsA, rs.row_off, rs.parent, aux, g.paint_out, g.paint_row0, g.paint_row1, g.wpr, (int)g.nx);
+    if (g.prezeroed)
+        rl_paint_kernel<true><<<grid1d((g.paint_row1 - g.paint_row0) * 64, 256, (i64)1 << 22), 256, 0, c->stream>>>(
+            g.bitsA, rs.row_off, rs.parent, aux, g.paint_out, g.paint_row0, g.paint_row1, g.wpr, (int)g.nx);
+    else
+        rl_paint_kernel<false><<<grid1d((g.paint_row1 - g.paint_row0) * 64, 256, (i64)1 << 22), 256, 0, c->stream>>>(
+            g.bitsA, rs.row_off, rs.parent, aux, g.paint_out, g.paint_row0, g.paint_row1, g.wpr, (int)g.nx);
     NL_CHECK_LAUNCH();
     // a streamed stack packs every frame right behind its labels: enqueue that now, under this wait (nl_outputs_pack_with_label)
     bool packed = false;
@@ -295,8 +310,8 @@ static int number_and_paint(nl_ctx *c, const LabelGeo &g, const RunSet &rs, int 
 // labelling.py:484-509 on a bit-packed mask (bitsA holds `frame > thr` on entry).  *overflow: more runs than scratch.
 static int label_core(nl_ctx *c, const LabelGeo &g, int64_t min_area, int fill_holes, int64_t *n_labels, bool *overflow,
                       char *err, size_t errlen) {
-    int free_idx[3], nf = 0;
-    for (int k = 0; k < 4; ++k) if (k != c->i_vmax) free_idx[nf++] = k;
+    int free_idx[3];
+    label_volumes(c, g.paint_out, free_idx);
     const i64 cap = c->n / 2;                                 // runs that fit the scratch volumes
     RunSet rs;
     rs.runs = (RunRec *)c->f[free_idx[0]];                    // 8 B x cap  = 4N bytes
@@ -355,12 +370,17 @@ static int label_core(nl_ctx *c, const LabelGeo &g, int64_t min_area, int fill_h
 static int label_out_index(const nl_ctx *c) {
     int last = -1;
     for (int k = 0; k < 4; ++k) if (k != c->i_vmax) last = k;
+    for (int k = 0; k < 4; ++k) if (k != c->i_vmax && pz_is(c, c->f[k])) last = k;      // the pre-zeroed one, if any
     return last;
 }
 
 extern "C" int nl_label_run(nl_ctx *c, int has_thr, float thr, int64_t min_area, int fill_holes, int64_t *n_labels,
                             char *err, size_t errlen) {
-    NL_ENTER(c);
+    NL_ENTER_KEEP_PZ(c);
+    c->prezero_used &= ~2;
+    const int out_idx = label_out_index(c);                  // (reads the flag)
+    const bool pz = pz_is(c, c->f[out_idx]) && c->nzl == c->gnz && !(getenv("NELLIE_LABEL_VOXEL") && atoi(getenv("NELLIE_LABEL_VOXEL"))) && c->nx <= 65535;
+    c->pz_buf = nullptr;                                     // Label writes every free volume: none is pre-zeroed after it
     if (!c->frangi_ready) return nl_fail(err, errlen, NL_ESTATE, "nl_label_run before a Frangi volume exists");
     if (c->nzl != c->gnz) return nl_fail(err, errlen, NL_EINVAL, "nl_label_run works on a whole volume (Z-slabs: nl_label_pack / nl_label_run_global)");
     static int force_voxel = -1;
@@ -371,8 +391,9 @@ extern "C" int nl_label_run(nl_ctx *c, int has_thr, float thr, int64_t min_area,
     g.nrows = c->nzl * c->ny; g.wpr = (int)((c->nx + 63) / 64); g.nwords = g.nrows * g.wpr;
     g.rows = c->d_rows;
     g.bitsA = (unsigned long long *)c->m[1]; g.bitsB = (unsigned long long *)c->m[2];
-    g.paint_row0 = 0; g.paint_row1 = g.nrows; g.paint_out = (int *)c->f[label_out_index(c)];
+    g.paint_row0 = 0; g.paint_row1 = g.nrows; g.paint_out = (int *)c->f[out_idx];
     g.link_scratch = g.paint_out;                 // the whole label volume (4N bytes) is idle until the paint
+    g.prezeroed = pz;
     label_geo_whole(g);
     g.whole_frame_paint = true;
     c->pack_pending = 0;
@@ -387,6 +408,7 @@ extern "C" int nl_label_run(nl_ctx *c, int has_thr, float thr, int64_t min_area,
     int rc = label_core(c, g, min_area, fill_holes, n_labels, &overflow, err, errlen);
     if (rc) return rc;
     if (overflow) return label_run_voxels(c, has_thr, thr, min_area, fill_holes, n_labels, err, errlen);
+    if (pz) c->prezero_used |= 2;
     c->labbits_epoch = c->epoch.load();           // m[1] = the mask the labels were painted from (labels > 0, bit for bit)
     return NL_OK;
 }
@@ -803,7 +825,7 @@ extern "C" int nl_slab_paint(nl_ctx *c, int64_t base, int64_t n, const int32_t *
         }
         NL_CHECK_LAUNCH();
     }
-    rl_paint_kernel<<<grid1d((g.paint_row1 - g.paint_row0) * 64, 256, (i64)1 << 22), 256, 0, c->stream>>>(
+    rl_paint_kernel<false><<<grid1d((g.paint_row1 - g.paint_row0) * 64, 256, (i64)1 << 22), 256, 0, c->stream>>>(
         g.bitsA, rs.row_off, rs.parent, sg.aux, g.paint_out, g.paint_row0, g.paint_row1, g.wpr, (int)g.nx);
     NL_CHECK_LAUNCH();
     NL_HIP(hipStreamSynchronize(c->stream));

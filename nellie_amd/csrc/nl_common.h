@@ -61,6 +61,14 @@ struct nl_ctx {
     unsigned long long labbits_epoch = ~0ull - 8;   // epoch at which m[1] held the bits `labels > 0` of the label volume (nl_label_run's last
                                                     // mask: what it painted from); Markers then skips re-deriving them from 4 B/voxel of labels
     int last_label_sparse = 0;
+    // Pre-zeroed label volume (NELLIE_PREZERO, nl_host.h: NL_ENTER_KEEP_PZ): the buffer -- by address, the epilogue swaps f[] entries --
+    // that the frame's last fused cascade step zeroed in passing (its dead third ping-pong volume) and that nl_label_run then paints
+    // sparsely.  Valid while pz_epoch == epoch at an entry point that carried it forward: every entry point that is not on that short
+    // list drops it.
+    float *pz_buf = nullptr;
+    unsigned long long pz_epoch = ~0ull - 8;
+    int pz_on = 0;                       // this frame's chain may pre-zero (nl_chain_begin reads NELLIE_PREZERO)
+    int prezero_used = 0;                // bit 0: the last frame's Frangi volume (never: see DESIGN.md), bit 1: its labels were written sparsely
     unsigned char *mk_act = nullptr; size_t mk_act_cap = 0;   // Markers, sparse LoG (markers.inc): [tile list (int32) | tile bytes | Z-march map]
     int mk_act_valid = 0;         // the tile list describes the current mask ...
     int mk_ntiles = 0;            // ... and holds this many active 16 x 64 tiles

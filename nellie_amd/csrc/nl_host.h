@@ -13,6 +13,7 @@
 
 #define NL_MASK_SLOTS 2      // cumulative h_mask bit planes (ping-pong between consecutive scales)
 #define NL_VERSION "nellie_amd-hip 0.1.0 (gfx950)"
+#define NL_PREZERO_DEFAULT 1 // NELLIE_PREZERO when unset (nl_chain_begin)
 #define SCAN_CHUNK 4096      // elements per workgroup of the exclusive scans (label_voxels.inc)
 
 // What the entry points call: RCCL's names, dispatched per communicator -- a communicator created from a loopback id
@@ -89,6 +90,18 @@ static size_t dtype_size(int dt) {
     if (!(c)) return nl_fail(err, errlen, NL_EINVAL, "ctx is NULL");   \
     ++(c)->epoch;                                                      \
     NL_HIP(hipSetDevice((c)->device));
+
+// The entry points between the frame's last cascade step and nl_label_run that leave the pre-zeroed volume alone (or say so: pz_touch):
+// they carry its flag forward.  After any other entry point the volume counts as pre-zeroed no longer.
+#define NL_ENTER_KEEP_PZ(c)                                            \
+    NL_ENTER(c)                                                        \
+    if ((c)->pz_epoch + 1 == (c)->epoch.load()) (c)->pz_epoch = (c)->epoch.load();
+
+static inline bool pz_valid(const nl_ctx *c) { return c->pz_buf && c->pz_epoch == c->epoch.load(); }
+static inline bool pz_is(const nl_ctx *c, const float *p) { return pz_valid(c) && p == c->pz_buf; }
+static inline void pz_set(nl_ctx *c, float *p) { c->pz_buf = p; c->pz_epoch = c->epoch.load(); }
+// `p` is about to be written by an entry point that carries the flag
+static inline void pz_touch(nl_ctx *c, const float *p) { if (p == c->pz_buf) c->pz_buf = nullptr; }
 
 // Entry points of the copy threads of nellie_amd/streaming.py (nl_input_load_async, nl_outputs_fetch_async, nl_outputs_wait):
 // they run CONCURRENTLY with the compute thread's calls on the same context, touch only the copy streams, the input slots
