@@ -1,4 +1,4 @@
-// Part of libnellie_hip.so (gfx950): included by nellie_hip.hip after thresholds.inc.
+// Part of libnellie_hip.so (gfx950): included by nellie_hip.hip after thresholds.inc; the records it logs are filled by nellie_sample.hip.
 // =================================================================================================
 // Device-resident threshold chain of a scale (filtering.py:365-380, 421-444, 555-566, 839-851)
 // =================================================================================================
@@ -20,13 +20,14 @@
 #define NL_CHAIN_BINS 256
 #define NL_CHAIN_MAX_SCALES 16
 
-struct ChainHist {                        // the record range_hist_enqueue fills (same layout as its scratch slots)
+struct ChainHist {                        // the record the sampling rounds fill: hist_layout (nl_host.h) at NL_CHAIN_BINS
     unsigned long long counts[NL_CHAIN_BINS];
     float edges[NL_CHAIN_BINS + 1];
     float pad_[3];
     unsigned int res[8];                  // [0] min bits, [1] max bits, [2..3] count, [4] flag (0 none, 1 ok, 2 not finite)
 };
-static_assert(sizeof(ChainHist) == NL_CHAIN_BINS * 8 + (((NL_CHAIN_BINS + 1) * 4 + 15) & ~15) + 32, "layout of range_hist_enqueue");
+static_assert(sizeof(ChainHist) == hist_layout(NL_CHAIN_BINS).bytes && offsetof(ChainHist, edges) == hist_layout(NL_CHAIN_BINS).off_edges &&
+              offsetof(ChainHist, res) == hist_layout(NL_CHAIN_BINS).off_res, "ChainHist is hist_layout");
 
 enum {
     NL_CF_GAUSS_HIST = 1, NL_CF_RAW_HIST = 2, NL_CF_TRIANGLE = 4, NL_CF_BRACKET = 8, NL_CF_INF = 16, NL_CF_OVERFLOW = 32,

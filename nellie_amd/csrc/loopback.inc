@@ -1,4 +1,4 @@
-// Part of libnellie_hip.so: included by nellie_hip.hip (host code + one small kernel).
+// Part of libnellie_hip.so: included by nellie_comm.hip (host code + one small kernel).
 // =================================================================================================
 // Loopback transport: the nccl* subset this library uses, between contexts of ONE process
 // =================================================================================================

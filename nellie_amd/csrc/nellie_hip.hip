@@ -1,109 +1,9 @@
-// libnellie_hip.so -- hand-written HIP for gfx950 (MI355X): Nellie's Filter -> Label hot path.
-// C-ABI in include/nellie_amd.h.  Compile with -ffp-contract=off: every float operation
+// libnellie_hip.so -- hand-written HIP for gfx950 (MI355X): Nellie's Filter -> Label hot path.  This unit: context lifetime, the
+// Gaussian cascade, the Hessian walk's launchers, the device chain and the epilogue (sampling: nellie_sample.hip, collectives:
+// nellie_comm.hip).  C-ABI in include/nellie_amd.h.  Compile with -ffp-contract=off: every float operation
 // below is meant to round exactly where numpy/scipy round.
 #include "nl_host.h"
 
-// RCCL is loaded on first use (dlopen) instead of being linked: librccl.so is ~570 MB and would be paged in by every
-// single-GPU process that merely loads this library.
-struct RcclApi {
-    void *handle = nullptr;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclSend) Send = nullptr;
-    decltype(&ncclRecv) Recv = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr;
-    decltype(&ncclBroadcast) Broadcast = nullptr;
-    decltype(&ncclAllGather) AllGather = nullptr;
-    bool ok = false;
-};
-static RcclApi &rccl_real() {
-    static RcclApi api;
-    if (!api.handle) {
-        // The installed ROCm's copy BY PATH first: a bare "librccl.so.1" is answered with whatever object of that SONAME the process
-        // already holds -- e.g. the RCCL a PyTorch wheel bundles (built against another HIP runtime: ncclCommInitRank then fails with
-        // "unhandled cuda error"; found when a test imported torch into the pytest process, round 5).
-        std::string rp;
-        if (const char *e = getenv("ROCM_PATH")) rp = std::string(e) + "/lib/librccl.so.1";
-        const char *names[] = {rp.c_str(), "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so", "librccl.so.1", "librccl.so"};
-        for (const char *n : names) { if (!*n) continue; api.handle = dlopen(n, RTLD_NOW | RTLD_GLOBAL); if (api.handle) break; }
-        if (api.handle) {
-#define NL_SYM(F) api.F = (decltype(api.F))dlsym(api.handle, "nccl" #F)
-            NL_SYM(GetUniqueId); NL_SYM(CommInitRank); NL_SYM(CommDestroy); NL_SYM(GetErrorString); NL_SYM(GroupStart);
-            NL_SYM(GroupEnd); NL_SYM(Send); NL_SYM(Recv); NL_SYM(AllReduce); NL_SYM(Broadcast); NL_SYM(AllGather);
-#undef NL_SYM
-            api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.GetErrorString && api.GroupStart &&
-                     api.GroupEnd && api.Send && api.Recv && api.AllReduce && api.Broadcast && api.AllGather;
-        }
-    }
-    return api;
-}
-
-#include "loopback.inc"
-
-// What the entry points call: the same names, dispatched per communicator -- a communicator created from a loopback id
-// (nl_comm_loopback_id) lives in loopback.inc, every other one is RCCL's.  librccl.so is only loaded when a real id is asked
-// for or used.
-static ncclResult_t comm_missing() { return (ncclResult_t)lb::kMissing; }
-ncclResult_t CommApi::GetUniqueId(ncclUniqueId *id) { return rccl_real().ok ? rccl_real().GetUniqueId(id) : comm_missing(); }
-ncclResult_t CommApi::CommInitRank(ncclComm_t *comm, int world, ncclUniqueId id, int rank) {
-    if (lb::is_loopback_id(id.internal)) return lb::comm_init(comm, world, id.internal, rank);
-    if (!rccl_real().ok) return comm_missing();
-    const ncclResult_t r = rccl_real().CommInitRank(comm, world, id, rank);
-    if (r == ncclSuccess) ++n_real;
-    return r;
-}
-ncclResult_t CommApi::CommDestroy(ncclComm_t comm) {
-    if (lb::is_ours(comm)) return lb::comm_destroy(comm);
-    if (!rccl_real().ok) return comm_missing();
-    --n_real;
-    return rccl_real().CommDestroy(comm);
-}
-const char *CommApi::GetErrorString(ncclResult_t r) {
-    if ((int)r == lb::kMissing) return "librccl.so could not be loaded";
-    if (rccl_real().handle && rccl_real().ok) return rccl_real().GetErrorString(r);
-    switch (r) {
-        case ncclInvalidArgument: return "invalid argument (loopback transport)";
-        case ncclSystemError: return "rendezvous timed out or a peer failed (loopback transport)";
-        case ncclUnhandledCudaError: return "HIP error (loopback transport)";
-        default: return "error (loopback transport)";
-    }
-}
-ncclResult_t CommApi::GroupStart() {
-    lb::group_start();
-    return n_real.load() > 0 ? rccl_real().GroupStart() : ncclSuccess;
-}
-ncclResult_t CommApi::GroupEnd() {
-    const ncclResult_t r = lb::group_end();
-    const ncclResult_t q = n_real.load() > 0 ? rccl_real().GroupEnd() : ncclSuccess;
-    return r != ncclSuccess ? r : q;
-}
-ncclResult_t CommApi::Send(const void *buf, size_t count, ncclDataType_t dt, int peer, ncclComm_t comm, hipStream_t st) {
-    if (lb::is_ours(comm)) return lb::submit(lb::Op{0, buf, nullptr, count, dt, ncclSum, peer, (lb::Comm *)comm, st});
-    return rccl_real().Send(buf, count, dt, peer, comm, st);
-}
-ncclResult_t CommApi::Recv(void *buf, size_t count, ncclDataType_t dt, int peer, ncclComm_t comm, hipStream_t st) {
-    if (lb::is_ours(comm)) return lb::submit(lb::Op{1, nullptr, buf, count, dt, ncclSum, peer, (lb::Comm *)comm, st});
-    return rccl_real().Recv(buf, count, dt, peer, comm, st);
-}
-ncclResult_t CommApi::AllReduce(const void *src, void *dst, size_t count, ncclDataType_t dt, ncclRedOp_t op, ncclComm_t comm, hipStream_t st) {
-    if (lb::is_ours(comm)) return lb::submit(lb::Op{2, src, dst, count, dt, op, -1, (lb::Comm *)comm, st});
-    return rccl_real().AllReduce(src, dst, count, dt, op, comm, st);
-}
-ncclResult_t CommApi::AllGather(const void *src, void *dst, size_t count, ncclDataType_t dt, ncclComm_t comm, hipStream_t st) {
-    if (lb::is_ours(comm)) return lb::submit(lb::Op{3, src, dst, count, dt, ncclSum, -1, (lb::Comm *)comm, st});
-    return rccl_real().AllGather(src, dst, count, dt, comm, st);
-}
-ncclResult_t CommApi::Broadcast(const void *src, void *dst, size_t count, ncclDataType_t dt, int root, ncclComm_t comm, hipStream_t st) {
-    if (lb::is_ours(comm)) return lb::submit(lb::Op{4, src, dst, count, dt, ncclSum, root, (lb::Comm *)comm, st});
-    return rccl_real().Broadcast(src, dst, count, dt, root, comm, st);
-}
-CommApi &rccl() { static CommApi api; return api; }
-
-#include "sampling.inc"
 #include "hessian.inc"
 #include "hessian_pair.inc"
 #include "hv_launch.h"
@@ -115,19 +15,6 @@ CommApi &rccl() { static CommApi api; return api; }
 // =================================================================================================
 // host side: context, launch helpers, C-ABI
 // =================================================================================================
-// workgroups of the lattice reductions (range, histogram): every workgroup ends with atomics on the same few words, which
-// retire ~10 ns apart -- 1024 workgroups spent 10-30 us on that alone (a 1e6-point gather is not longer); NELLIE_SAMPLE_GRID
-// NELLIE_CHAIN_UNFUSED_SAMPLING=1: the chain's first round as two separate range + histogram sequences (A/B, tests)
-static bool chain_unfused_sampling() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("NELLIE_CHAIN_UNFUSED_SAMPLING"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-static i64 sample_grid_cap() {
-    static i64 v = 0;
-    if (!v) { const char *e = getenv("NELLIE_SAMPLE_GRID"); v = (e && atoll(e) > 0) ? atoll(e) : 256; }
-    return v;
-}
 
 // fused Y+X Gaussian: tiled / register-blocked X pass (default) or the row-at-a-time kernel (NELLIE_GYX_TILE=0)
 bool gyx_tiled() {
@@ -158,7 +45,6 @@ static int hv_rs_env() {
 }
 // the pair kernel addresses the planes of a Z chunk through one buffer resource (32-bit byte offsets)
 static int hv_rs(const nl_ctx *c) { return ((i64)(HM_ZCHUNK + 4) * c->ny * c->nx * 4 < ((i64)1 << 32)) ? hv_rs_env() : 0; }
-static HessP hessp(const nl_ctx *c);
 static HessDv<1> hessdv_fast(const nl_ctx *c) { return hessdv_fast(hessp(c)); }      // (dv_* and the HessP forms: hv_launch.h)
 static HessDv<0> hessdv_exact(const nl_ctx *c) { return hessdv_exact(hessp(c)); }
 // the pair walk (its own translation unit, hv_launch.h): division variant as proven for this context's divisors
@@ -221,7 +107,6 @@ static int check_fast_div(nl_ctx *c, char *err, size_t errlen) {
     if (e && atoi(e) == 3) c->fast_div2 = 0;
     return NL_OK;
 }
-static HessP hessp(const nl_ctx *c) { return HessP{c->hz, c->hy, c->hx, c->hz2, c->hy2, c->hx2}; }
 
 
 extern "C" const char *nl_version(void) { return NL_VERSION; }
@@ -294,7 +179,6 @@ extern "C" int64_t nl_ctx_bytes(int64_t nz_local, int64_t ny, int64_t nx) {
     return n * (4 * 4 + 3) + qe * 32 + vq_alloc_regions(nz_local, ny, nx) * 4 + (1 << 16) + ((n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1) * 4;
 }
 
-static void comm_release(nl_ctx *c, void *comm, int role);      // RCCL communicators go back to a per-process pool (see nl_comm_init)
 extern "C" int nl_ctx_destroy(nl_ctx *c) {
     if (!c) return NL_OK;
     hipSetDevice(c->device);
@@ -711,442 +595,6 @@ extern "C" int nl_gauss_commit(nl_ctx *c, char *err, size_t errlen) {
     return NL_OK;
 }
 
-static int make_lattice(const nl_ctx *c, i64 sz, i64 sy, i64 sx, Lattice &L, char *err, size_t errlen) {
-    if (sz < 1 || sy < 1 || sx < 1) return nl_fail(err, errlen, NL_EINVAL, "strides must be >= 1");
-    L.sz = sz; L.sy = sy; L.sx = sx;
-    // owned global planes [g_lo, g_hi): lattice planes are global z = k*sz
-    const i64 g_lo = c->gz0 + c->own_lo, g_hi = c->gz0 + c->own_hi;
-    const i64 k_lo = (g_lo + sz - 1) / sz, k_hi = (g_hi + sz - 1) / sz;   // k in [k_lo, k_hi)
-    L.cz = k_hi > k_lo ? k_hi - k_lo : 0;
-    L.zfirst = k_lo * sz - c->gz0;
-    L.cy = (c->ny + sy - 1) / sy;
-    L.cx = (c->nx + sx - 1) / sx;
-    return NL_OK;
-}
-
-static int make_field(nl_ctx *c, int field, FieldSrc &fs, char *err, size_t errlen) {
-    fs.field = field; fs.hp = hessp(c); fs.max_abs = c->frob_max_abs; fs.max_finite = c->frob_max_finite;
-    fs.two_d = c->two_d; fs.bits = nullptr; fs.wpr = 0; fs.fsq_cache = nullptr; fs.norm_dev = nullptr;
-    if (field == NL_FIELD_GAUSS) fs.p = gauss_cur(c);
-    else if (field == NL_FIELD_FROB) {
-        if (!c->have_spacing) return nl_fail(err, errlen, NL_ESTATE, "NL_FIELD_FROB before nl_hessian_stats");
-        fs.p = gauss_cur(c);
-    } else if (field == NL_FIELD_FRANGI) fs.p = c->f[c->i_vmax];
-    else if (field == NL_FIELD_VESSELNESS) {
-        if (c->mask_slots_used == 0) return nl_fail(err, errlen, NL_ESTATE, "NL_FIELD_VESSELNESS before any scale was evaluated");
-        NL_JOIN_SIDE(c);
-        fs.p = c->f[c->i_vmax];
-        fs.wpr = (int)((c->nx + 63) / 64);
-        fs.bits = (const unsigned long long *)c->m[0] + (i64)((c->mask_slots_used - 1) & 1) * (c->nzl * c->ny * fs.wpr);
-    } else return nl_fail(err, errlen, NL_EINVAL, "unknown field %d", field);
-    return NL_OK;
-}
-
-// NL_FIELD_FROB is sampled up to four times per scale (threshold bracket and exact threshold, min/max and histogram
-// each) with different normalisations of the same frob_sq: evaluate the Hessian at the lattice points once.
-static int use_fsq_cache(nl_ctx *c, FieldSrc &fs, const Lattice &L, char *err, size_t errlen) {
-    if (fs.field != NL_FIELD_FROB) return NL_OK;
-    const i64 total = L.cz * L.cy * L.cx;
-    if (total == 0) return NL_OK;
-    if (!(c->fsq_cache_valid && c->fsq_cache_key[0] == L.sz && c->fsq_cache_key[1] == L.sy && c->fsq_cache_key[2] == L.sx)) {
-        if (total > c->fsq_cache_cap) {
-            if (c->d_fsq_cache) NL_HIP(hipFree(c->d_fsq_cache));
-            c->d_fsq_cache = nullptr; c->fsq_cache_cap = 0;
-            NL_HIP(hipMalloc((void **)&c->d_fsq_cache, (size_t)total * 4));
-            c->fsq_cache_cap = total;
-        }
-        ProfScope ps(c, "sample");
-        sample_fsq_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(fs, geom(c), L, c->d_fsq_cache);
-        NL_CHECK_LAUNCH();
-        c->fsq_cache_key[0] = L.sz; c->fsq_cache_key[1] = L.sy; c->fsq_cache_key[2] = L.sx;
-        c->fsq_cache_valid = 1;
-    }
-    fs.fsq_cache = c->d_fsq_cache;
-    return NL_OK;
-}
-
-extern "C" int nl_sample_gather(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, float *out, int64_t cap,
-                                int64_t *n, char *err, size_t errlen) {
-    NL_ENTER(c);
-    Lattice L; FieldSrc fs; int rc;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, field, fs, err, errlen))) return rc;
-    if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-    const i64 total = L.cz * L.cy * L.cx;
-    if (n) *n = total;
-    if (total == 0 || (!out && cap == 0)) return NL_OK;   // size query
-    if (!out || cap < total) return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld < %lld samples", (i64)cap, total);
-    // a free float volume as staging: whichever of f[0..2] is not the current gauss
-    float *stage = c->f[(c->i_gauss + 1) % 3];
-    if (total > c->n) return nl_fail(err, errlen, NL_EINVAL, "lattice larger than the volume");
-    {
-        ProfScope ps(c, "sample");
-        sample_gather_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(fs, geom(c), L, stage);
-        NL_CHECK_LAUNCH();
-    }
-    NL_HIP(hipMemcpyAsync(out, stage, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    return NL_OK;
-}
-
-// The positive samples of the same lattice, compacted on the device: only they cross PCIe (the consumers take
-// arr[arr > 0] first anyway: filtering.py:357, 957-959).  Order unspecified.  cap >= number of lattice points.
-// A positive gather leaves its samples in `stage` and their number in *d_n.  Fetching them used to be two round trips (the count,
-// then that many samples); the count and the first NL_PREFIX samples now travel together into pinned memory, and only a longer
-// list costs a second transfer.  *n = the count; out[0 .. n) = the samples.
-#define NL_PREFIX 32768
-int fetch_counted(nl_ctx *c, const float *stage, const unsigned int *d_n, i64 max_count, float *out, i64 cap, int64_t *n, char *err, size_t errlen) {
-    if (!c->h_prefix) NL_HIP(hipHostMalloc(&c->h_prefix, (size_t)NL_PREFIX * 4 + 64, hipHostMallocDefault));
-    unsigned int *h_n = (unsigned int *)c->h_prefix;
-    float *h_s = (float *)((char *)c->h_prefix + 64);
-    const i64 first = max_count < NL_PREFIX ? max_count : NL_PREFIX;
-    NL_HIP(hipMemcpyAsync(h_n, d_n, 4, hipMemcpyDeviceToHost, c->stream));
-    if (first > 0) NL_HIP(hipMemcpyAsync(h_s, stage, (size_t)first * 4, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    const i64 k = (i64)*h_n;
-    if (n) *n = 0;
-    if (k > cap || (k && !out)) return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld < %lld positive samples", (i64)cap, k);
-    if (k > max_count) return nl_fail(err, errlen, NL_ESTATE, "positive gather counted %lld of at most %lld samples", k, max_count);
-    if (k) memcpy(out, h_s, (size_t)(k < first ? k : first) * 4);
-    if (k > first) {
-        NL_HIP(hipMemcpyAsync(out + first, stage + first, (size_t)(k - first) * 4, hipMemcpyDeviceToHost, c->stream));
-        NL_HIP(hipStreamSynchronize(c->stream));
-    }
-    if (n) *n = k;
-    return NL_OK;
-}
-
-// The positive lattice samples in two halves, so that the host can do other work (nl_chain_finish: wait for the chain's
-// records, repeat its decisions) while the kernel runs: _begin enqueues the kernel and the download of the count, _end waits and
-// fetches the samples.  No other call on this context in between except nl_chain_finish / nl_chain_log.
-extern "C" int nl_sample_gather_positive_begin(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, int64_t *n_lattice, char *err, size_t errlen) {
-    NL_ENTER(c);
-    Lattice L; FieldSrc fs; int rc;
-    c->gp_total = -1;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, field, fs, err, errlen))) return rc;
-    if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-    const i64 total = L.cz * L.cy * L.cx;
-    if (n_lattice) *n_lattice = total;
-    c->gp_total = total;
-    if (total == 0) return NL_OK;
-    if (total > c->n) { c->gp_total = -1; return nl_fail(err, errlen, NL_EINVAL, "lattice larger than the volume"); }
-    c->gp_stage = c->f[(c->i_gauss + 1) % 3];
-    unsigned int *d_n = (unsigned int *)c->d_small;
-    NL_HIP(zero_small(d_n, 4, c->stream));
-    {
-        ProfScope ps(c, "sample");
-        sample_gather_pos_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(fs, geom(c), L, c->gp_stage, d_n);
-        NL_CHECK_LAUNCH();
-    }
-    return NL_OK;
-}
-extern "C" int nl_sample_gather_positive_end(nl_ctx *c, float *out, int64_t cap, int64_t *n, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (c->gp_total < 0) return nl_fail(err, errlen, NL_ESTATE, "nl_sample_gather_positive_end without _begin");
-    const i64 total = c->gp_total;
-    c->gp_total = -1;
-    if (n) *n = 0;
-    if (total == 0) return NL_OK;
-    return fetch_counted(c, c->gp_stage, (const unsigned int *)c->d_small, total, out, cap, n, err, errlen);
-}
-extern "C" int nl_sample_gather_positive(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, float *out, int64_t cap,
-                                         int64_t *n, char *err, size_t errlen) {
-    int64_t total = 0;
-    if (n) *n = 0;
-    int rc = nl_sample_gather_positive_begin(c, field, sz, sy, sx, &total, err, errlen);
-    if (rc) return rc;
-    if (total > 0 && (!out || cap < total)) { c->gp_total = -1; return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld < %lld lattice points", (i64)cap, (i64)total); }
-    return nl_sample_gather_positive_end(c, out, cap, n, err, errlen);
-}
-
-// res = [min bits, max bits, count lo, count hi] of positive float32 samples: unsigned order = float order
-static int reduce_range(nl_ctx *c, unsigned int *res, char *err, size_t errlen) {
-    NL_NCCL(rccl().GroupStart());
-    NL_NCCL(rccl().AllReduce(res, res, 1, ncclUint32, ncclMin, (ncclComm_t)c->comm, c->stream));
-    NL_NCCL(rccl().AllReduce(res + 1, res + 1, 1, ncclUint32, ncclMax, (ncclComm_t)c->comm, c->stream));
-    NL_NCCL(rccl().AllReduce(res + 2, res + 2, 1, ncclUint64, ncclSum, (ncclComm_t)c->comm, c->stream));
-    NL_NCCL(rccl().GroupEnd());
-    return NL_OK;
-}
-static int reduce_u64_sum(nl_ctx *c, unsigned long long *v, size_t n, char *err, size_t errlen) {
-    NL_NCCL(rccl().AllReduce(v, v, n, ncclUint64, ncclSum, (ncclComm_t)c->comm, c->stream));
-    return NL_OK;
-}
-static int reduce_u32_max(nl_ctx *c, unsigned int *v, size_t n, char *err, size_t errlen) {
-    NL_NCCL(rccl().AllReduce(v, v, n, ncclUint32, ncclMax, (ncclComm_t)c->comm, c->stream));
-    return NL_OK;
-}
-
-extern "C" int nl_sample_minmax(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, float *mn, float *mx,
-                                int64_t *npos, char *err, size_t errlen) {
-    NL_ENTER(c);
-    Lattice L; FieldSrc fs; int rc;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, field, fs, err, errlen))) return rc;
-    if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-    const i64 total = L.cz * L.cy * L.cx;
-    unsigned int *res = (unsigned int *)c->d_small;
-    unsigned int *h = (unsigned int *)c->h_small;
-    h[0] = 0xffffffffu; h[1] = 0; h[2] = 0; h[3] = 0;
-    NL_HIP(hipMemcpyAsync(res, h, 16, hipMemcpyHostToDevice, c->stream));
-    if (total > 0) {
-        ProfScope ps(c, "sample");
-        sample_minmax_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, 0, c->stream>>>(fs, geom(c), L, res);
-        NL_CHECK_LAUNCH();
-    }
-    if (fused(c) && (rc = reduce_range(c, res, err, errlen))) return rc;
-    NL_HIP(hipMemcpyAsync(h, res, 16, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    const unsigned long long cnt = *(unsigned long long *)(h + 2);
-    if (npos) *npos = (int64_t)cnt;
-    if (cnt) {
-        if (mn) memcpy(mn, &h[0], 4);
-        if (mx) memcpy(mx, &h[1], 4);
-    }
-    return NL_OK;
-}
-
-extern "C" int nl_sample_hist(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, const float *edges, int nbins,
-                              int64_t *counts, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!edges || !counts || nbins < 1 || nbins > 4096) return nl_fail(err, errlen, NL_EINVAL, "bad histogram arguments (nbins=%d)", nbins);
-    Lattice L; FieldSrc fs; int rc;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, field, fs, err, errlen))) return rc;
-    if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-    const i64 total = L.cz * L.cy * L.cx;
-    // d_small layout: [0, 32K) counts (u64 x nbins), [32K, 64K) edges (f32 x nbins+1)
-    unsigned long long *d_counts = (unsigned long long *)c->d_small;
-    float *d_edges = (float *)((char *)c->d_small + (1 << 15));
-    NL_HIP(zero_small(d_counts, (size_t)nbins * 8, c->stream));
-    memcpy((char *)c->h_small + (1 << 15), edges, (size_t)(nbins + 1) * 4);
-    NL_HIP(hipMemcpyAsync(d_edges, (char *)c->h_small + (1 << 15), (size_t)(nbins + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (total > 0) {
-        ProfScope ps(c, "sample");
-        const size_t sh = (size_t)(nbins + 2) * 4 + (size_t)nbins * 4;
-        sample_hist_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, sh, c->stream>>>(fs, geom(c), L, d_edges, nbins, d_counts, nullptr);
-        NL_CHECK_LAUNCH();
-    }
-    if (fused(c) && (rc = reduce_u64_sum(c, d_counts, (size_t)nbins, err, errlen))) return rc;
-    NL_HIP(hipMemcpyAsync(c->h_small, d_counts, (size_t)nbins * 8, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    memcpy(counts, c->h_small, (size_t)nbins * 8);
-    return NL_OK;
-}
-
-// nl_sample_minmax + nl_sample_hist in one go: the bin edges numpy would build from the range are formed on the
-// device, so the two passes need no host round trip in between.  *valid: 0 no positive sample, 1 ok, 2 range not finite
-// (the caller raises numpy's ValueError then).  edges (may be NULL) receives the nbins + 1 device-built edges.
-// the kernels of one range + edges + histogram chain, working in the `slot`-th half of the small scratch (device and pinned)
-#define NL_RH_SLOT 32768
-static int range_hist_enqueue_at(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, int nbins, char *d0, char *h0, char *err, size_t errlen);
-static int range_hist_enqueue(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, int nbins, int slot, char *err, size_t errlen) {
-    return range_hist_enqueue_at(c, field, sz, sy, sx, nbins, (char *)c->d_small + (size_t)slot * NL_RH_SLOT, (char *)c->h_small + (size_t)slot * NL_RH_SLOT, err, errlen);
-}
-// d0: the record in device memory; h0: its pinned mirror (the initial state of the range words is uploaded from there), or NULL
-// when the record was initialised by the caller (chain_init_kernel)
-static int range_hist_enqueue_at(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, int nbins, char *d0, char *h0, char *err, size_t errlen) {
-    Lattice L; FieldSrc fs; int rc;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, field, fs, err, errlen))) return rc;
-    if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-    const i64 total = L.cz * L.cy * L.cx;
-    // layout (contiguous, one transfer back): counts (u64 x nbins) | edges (f32 x nbins+1, padded) | range, count, flag
-    const size_t off_edges = (size_t)nbins * 8, off_res = off_edges + (((size_t)(nbins + 1) * 4 + 15) & ~(size_t)15);
-    unsigned long long *d_counts = (unsigned long long *)d0;
-    float *d_edges = (float *)(d0 + off_edges);
-    unsigned int *res = (unsigned int *)(d0 + off_res);
-    if (h0) {
-        unsigned int *h = (unsigned int *)(h0 + off_res);
-        h[0] = 0xffffffffu; h[1] = 0; h[2] = 0; h[3] = 0; h[4] = 0;
-        NL_HIP(hipMemcpyAsync(res, h, 20, hipMemcpyHostToDevice, c->stream));
-        NL_HIP(zero_small(d_counts, (size_t)nbins * 8, c->stream));
-    }
-    if (total > 0 || fused(c)) {
-        // fused: a rank without lattice points of its own still takes part in the collectives and builds the same edges
-        ProfScope ps(c, "sample");
-        if (total > 0) sample_minmax_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, 0, c->stream>>>(fs, geom(c), L, res);
-        if (fused(c) && (rc = reduce_range(c, res, err, errlen))) return rc;
-        sample_edges_kernel<<<1, 64, 0, c->stream>>>(res, nbins, d_edges, res + 4);
-        const size_t sh = (size_t)(nbins + 2) * 4 + (size_t)nbins * 4;
-        if (total > 0) sample_hist_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, sh, c->stream>>>(fs, geom(c), L, d_edges, nbins, d_counts, res + 4);
-        NL_CHECK_LAUNCH();
-        if (fused(c) && (rc = reduce_u64_sum(c, d_counts, (size_t)nbins, err, errlen))) return rc;
-    }
-    return NL_OK;
-}
-// The Gaussian and the raw-Frobenius records of one scale in three launches instead of seven: one pass fills the frob_sq
-// cache and both ranges, one builds both edge arrays, one bins both.  With fused reductions: two grouped collectives instead of
-// four.  hG / hF: pinned mirrors the initial state is uploaded from, or NULL when the caller initialised the records (chain.inc).
-static int range_hist_pair_enqueue(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx, int nbins, char *dG, char *dF, char *hG, char *hF,
-                                   char *err, size_t errlen) {
-    Lattice L; FieldSrc fsG, fsF; int rc;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, NL_FIELD_GAUSS, fsG, err, errlen))) return rc;
-    if ((rc = make_field(c, NL_FIELD_FROB, fsF, err, errlen))) return rc;
-    const i64 total = L.cz * L.cy * L.cx;
-    const size_t off_edges = (size_t)nbins * 8, off_res = off_edges + (((size_t)(nbins + 1) * 4 + 15) & ~(size_t)15);
-    unsigned int *resG = (unsigned int *)(dG + off_res), *resF = (unsigned int *)(dF + off_res);
-    float *edgesG = (float *)(dG + off_edges), *edgesF = (float *)(dF + off_edges);
-    for (int k = 0; k < 2; ++k) {
-        char *h0 = k ? hF : hG, *d0 = k ? dF : dG;
-        if (!h0) continue;
-        unsigned int *h = (unsigned int *)(h0 + off_res);
-        h[0] = 0xffffffffu; h[1] = 0; h[2] = 0; h[3] = 0; h[4] = 0;
-        NL_HIP(hipMemcpyAsync(d0 + off_res, h, 20, hipMemcpyHostToDevice, c->stream));
-        NL_HIP(zero_small(d0, (size_t)nbins * 8, c->stream));
-    }
-    if (total > c->fsq_cache_cap) {
-        if (c->d_fsq_cache) NL_HIP(hipFree(c->d_fsq_cache));
-        c->d_fsq_cache = nullptr; c->fsq_cache_cap = 0;
-        NL_HIP(hipMalloc((void **)&c->d_fsq_cache, (size_t)total * 4));
-        c->fsq_cache_cap = total;
-    }
-    if (total == 0 && !fused(c)) return NL_OK;
-    ProfScope ps(c, "sample");
-    if (total > 0) {
-        sample_minmax2_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, 0, c->stream>>>(fsG, fsF, geom(c), L, resG, resF, c->d_fsq_cache);
-        c->fsq_cache_key[0] = L.sz; c->fsq_cache_key[1] = L.sy; c->fsq_cache_key[2] = L.sx;
-        c->fsq_cache_valid = 1;
-        fsF.fsq_cache = c->d_fsq_cache;
-    }
-    if (fused(c)) {
-        NL_NCCL(rccl().GroupStart());
-        for (unsigned int *res : {resG, resF}) {
-            NL_NCCL(rccl().AllReduce(res, res, 1, ncclUint32, ncclMin, (ncclComm_t)c->comm, c->stream));
-            NL_NCCL(rccl().AllReduce(res + 1, res + 1, 1, ncclUint32, ncclMax, (ncclComm_t)c->comm, c->stream));
-            NL_NCCL(rccl().AllReduce(res + 2, res + 2, 1, ncclUint64, ncclSum, (ncclComm_t)c->comm, c->stream));
-        }
-        NL_NCCL(rccl().GroupEnd());
-    }
-    sample_edges2_kernel<<<2, 64, 0, c->stream>>>(resG, edgesG, resG + 4, resF, edgesF, resF + 4, nbins);
-    const size_t sh = 2 * ((size_t)(nbins + 2) * 4 + (size_t)nbins * 4);
-    if (total > 0)
-        sample_hist2_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, sh, c->stream>>>(fsG, fsF, geom(c), L, nbins, edgesG, (unsigned long long *)dG, resG + 4,
-                                                                                         edgesF, (unsigned long long *)dF, resF + 4);
-    NL_CHECK_LAUNCH();
-    if (fused(c)) {
-        NL_NCCL(rccl().GroupStart());
-        NL_NCCL(rccl().AllReduce(dG, dG, (size_t)nbins, ncclUint64, ncclSum, (ncclComm_t)c->comm, c->stream));
-        NL_NCCL(rccl().AllReduce(dF, dF, (size_t)nbins, ncclUint64, ncclSum, (ncclComm_t)c->comm, c->stream));
-        NL_NCCL(rccl().GroupEnd());
-    }
-    return NL_OK;
-}
-static void range_hist_read(const nl_ctx *c, int nbins, int slot, float *mn, float *mx, int64_t *npos, int64_t *counts, float *edges, int *valid) {
-    const size_t off_edges = (size_t)nbins * 8, off_res = off_edges + (((size_t)(nbins + 1) * 4 + 15) & ~(size_t)15);
-    const char *h0 = (const char *)c->h_small + (size_t)slot * NL_RH_SLOT;
-    const unsigned int *hr = (const unsigned int *)(h0 + off_res);
-    const unsigned long long cnt = *(const unsigned long long *)(hr + 2);
-    if (npos) *npos = (int64_t)cnt;
-    *valid = (int)hr[4];
-    if (cnt) {
-        if (mn) memcpy(mn, &hr[0], 4);
-        if (mx) memcpy(mx, &hr[1], 4);
-    }
-    memcpy(counts, h0, (size_t)nbins * 8);
-    if (edges) memcpy(edges, h0 + off_edges, (size_t)(nbins + 1) * 4);
-}
-
-extern "C" int nl_sample_range_hist(nl_ctx *c, int field, int64_t sz, int64_t sy, int64_t sx, int nbins, float *mn, float *mx,
-                                    int64_t *npos, int64_t *counts, float *edges, int *valid, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!counts || !valid || nbins < 1 || nbins > 2048) return nl_fail(err, errlen, NL_EINVAL, "bad histogram arguments (nbins=%d)", nbins);
-    int rc = range_hist_enqueue(c, field, sz, sy, sx, nbins, 0, err, errlen);
-    if (rc) return rc;
-    const size_t bytes = (size_t)nbins * 8 + (((size_t)(nbins + 1) * 4 + 15) & ~(size_t)15) + 32;
-    NL_HIP(hipMemcpyAsync(c->h_small, c->d_small, bytes, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    range_hist_read(c, nbins, 0, mn, mx, npos, counts, edges, valid);
-    return NL_OK;
-}
-
-// Two independent fields in one round trip (the gamma samples of the Gaussian and the raw Frobenius samples of a scale:
-// filtering.py:365-380 and 421-444 need nothing from each other).  Arrays of two: [0] = field_a, [1] = field_b.
-extern "C" int nl_sample_range_hist2(nl_ctx *c, int field_a, int field_b, int64_t sz, int64_t sy, int64_t sx, int nbins, float *mn, float *mx,
-                                     int64_t *npos, int64_t *counts, float *edges, int *valid, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!counts || !valid || !mn || !mx || !npos || nbins < 1 || nbins > 2048) return nl_fail(err, errlen, NL_EINVAL, "bad histogram arguments (nbins=%d)", nbins);
-    int rc;
-    const bool fresh_cache = !(c->fsq_cache_valid && c->fsq_cache_key[0] == sz && c->fsq_cache_key[1] == sy && c->fsq_cache_key[2] == sx);
-    if (field_a == NL_FIELD_GAUSS && field_b == NL_FIELD_FROB && fresh_cache && nbins <= 1024 && !chain_unfused_sampling()) {
-        // the pair of a scale's first round (filtering.py:365-380, 421-444): one pass over the lattice
-        if ((rc = range_hist_pair_enqueue(c, sz, sy, sx, nbins, (char *)c->d_small, (char *)c->d_small + NL_RH_SLOT, (char *)c->h_small,
-                                          (char *)c->h_small + NL_RH_SLOT, err, errlen))) return rc;
-    } else {
-        if ((rc = range_hist_enqueue(c, field_a, sz, sy, sx, nbins, 0, err, errlen))) return rc;
-        if ((rc = range_hist_enqueue(c, field_b, sz, sy, sx, nbins, 1, err, errlen))) return rc;
-    }
-    const size_t bytes = (size_t)nbins * 8 + (((size_t)(nbins + 1) * 4 + 15) & ~(size_t)15) + 32;
-    for (int k = 0; k < 2; ++k)
-        NL_HIP(hipMemcpyAsync((char *)c->h_small + (size_t)k * NL_RH_SLOT, (char *)c->d_small + (size_t)k * NL_RH_SLOT, bytes, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 2; ++k)
-        range_hist_read(c, nbins, k, mn + k, mx + k, npos + k, counts + (size_t)k * nbins, edges ? edges + (size_t)k * (nbins + 1) : nullptr, valid + k);
-    return NL_OK;
-}
-
-extern "C" int nl_hist_thresholds(const int64_t *counts, const float *edges, int nbins, double *triangle, double *otsu, int *status,
-                                  char *err, size_t errlen) {
-    if (!counts || !edges || !triangle || !otsu || !status || nbins < 1 || nbins > (1 << 20))
-        return nl_fail(err, errlen, NL_EINVAL, "bad histogram arguments (nbins=%d)", nbins);
-    hist_thresholds_host<float>(counts, edges, nbins, triangle, otsu, status);
-    return NL_OK;
-}
-
-static void host_edges(float first, float last, int nbins, float *edges);
-// np.histogram(values, bins=nbins, range=(min, max)) of float32 host data + the two thresholds of that histogram, in one call
-// (labelling.py:448-455 after the log10: the samples are a few 10^4 values, numpy spends ~0.2-0.6 ms on them while the GPU
-// waits).  Same float32 arithmetic as sample_edges_kernel / sample_hist_kernel, which are pinned against numpy.  *status: 0 ok,
-// 1 degenerate triangle (numpy's ValueError), 2 range not finite (numpy's ValueError).  counts / edges: optional copies.
-extern "C" int nl_host_hist_thresholds_f32(const float *values, int64_t n, int nbins, double *triangle, double *otsu, int *status,
-                                           int64_t *counts_out, float *edges_out, char *err, size_t errlen) {
-    if (!values || n < 1 || !triangle || !otsu || !status || nbins < 1 || nbins > (1 << 20))
-        return nl_fail(err, errlen, NL_EINVAL, "bad histogram arguments (n=%lld, nbins=%d)", (long long)n, nbins);
-    float mn = values[0], mx = values[0];
-    bool nan = false;
-    for (int64_t i = 0; i < n; ++i) {
-        const float a = values[i];
-        if (a != a) nan = true;
-        if (a < mn) mn = a;
-        if (a > mx) mx = a;
-    }
-    *status = 0; *triangle = 0.0; *otsu = 0.0;
-    if (nan || !(fabsf(mn) <= 3.402823466e38f) || !(fabsf(mx) <= 3.402823466e38f)) { *status = 2; return NL_OK; }
-    std::vector<float> edges((size_t)nbins + 1);
-    std::vector<int64_t> counts((size_t)nbins, 0);
-    host_edges(mn, mx, nbins, edges.data());
-    volatile float first = mn, last = mx;
-    if (mn == mx) { first = mn - 0.5f; last = mx + 0.5f; }
-    const float f0 = first, f1 = last;
-    volatile float denom = f1 - f0;
-    const float dn = denom, nb = (float)nbins;
-    for (int64_t i = 0; i < n; ++i) {
-        const float a = values[i];
-        if (!(a >= f0 && a <= f1)) continue;
-        const float t = ((a - f0) / dn) * nb;          // float32 throughout (x86-64 SSE, -ffp-contract=off): numpy's expression
-        int idx = (int)t;
-        if (idx == nbins) idx -= 1;
-        if (a < edges[idx]) idx -= 1;
-        if (a >= edges[idx + 1] && idx != nbins - 1) idx += 1;
-        counts[idx] += 1;
-    }
-    hist_thresholds_host<float>(counts.data(), edges.data(), nbins, triangle, otsu, status, nullptr);
-    if (counts_out) memcpy(counts_out, counts.data(), (size_t)nbins * 8);
-    if (edges_out) memcpy(edges_out, edges.data(), ((size_t)nbins + 1) * 4);
-    return NL_OK;
-}
-
-extern "C" int nl_hist_thresholds_ex(const int64_t *counts, const void *edges, int edges_f64, int nbins, double *triangle, double *otsu,
-                                     double *otsu_var, int *status, char *err, size_t errlen) {
-    if (!counts || !edges || !triangle || !otsu || !status || nbins < 1 || nbins > (1 << 20))
-        return nl_fail(err, errlen, NL_EINVAL, "bad histogram arguments (nbins=%d)", nbins);
-    if (edges_f64) hist_thresholds_host<double>(counts, (const double *)edges, nbins, triangle, otsu, status, otsu_var);
-    else hist_thresholds_host<float>(counts, (const float *)edges, nbins, triangle, otsu, status, otsu_var);
-    return NL_OK;
-}
-
 static int set_spacing(nl_ctx *c, const double spacing[3], char *err, size_t errlen) {
     if (!spacing) return nl_fail(err, errlen, NL_EINVAL, "spacing is NULL");
     if ((!c->two_d && c->gnz < 2) || c->ny < 2 || c->nx < 2)
@@ -1494,18 +942,6 @@ extern "C" int nl_vesselness_resolve(nl_ctx *c, float gamma_sq, float alpha_sq, 
 
 
 // ---- device-resident threshold chain (chain.inc) -----------------------------------------------------------------------------
-static void host_edges(float first, float last, int nbins, float *edges) {       // sample_edges_kernel on the host (verification)
-    if (first == last) { first = first - 0.5f; last = last + 0.5f; }
-    volatile float delta = last - first;
-    const float div = (float)nbins;
-    volatile float step = delta / div;
-    for (int i = 0; i <= nbins; ++i) {
-        volatile float y = (float)i;
-        if (step == 0.0f) { y = y / div; y = y * delta; } else y = y * step;
-        y = y + first;
-        edges[i] = (i == nbins) ? last : y;
-    }
-}
 static inline unsigned int f2u(float x) { unsigned int u; memcpy(&u, &x, 4); return u; }
 static inline float u2f(unsigned int u) { float x; memcpy(&x, &u, 4); return x; }
 static inline float py_min_f(float a, float b) { return b < a ? b : a; }       // python's min(a, b)
@@ -1595,12 +1031,7 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
         // raw round only measures the sample range the exact round's edges are derived from (its "bracket" decides nothing: the caller passes
         // a margin of 1), the statistics kernel stands where the walk stands, and the vesselness kernel reads gamma_sq / fsq_min / m_inf
         // from the record as the resolve kernel does.  ~20 host round trips of a 2048^2 frame gone.
-        if (!chain_unfused_sampling()) {
-            if ((rc = range_hist_pair_enqueue(c, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, (char *)&cs->h_raw, nullptr, nullptr, err, errlen))) return rc;
-        } else {
-            if ((rc = range_hist_enqueue_at(c, NL_FIELD_GAUSS, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, nullptr, err, errlen))) return rc;
-            if ((rc = range_hist_enqueue_at(c, NL_FIELD_FROB, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_raw, nullptr, err, errlen))) return rc;
-        }
+        if ((rc = sample_first_round(c, NL_FIELD_GAUSS, NL_FIELD_FROB, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, (char *)&cs->h_raw, nullptr, nullptr, true, err, errlen))) return rc;
         chain_thr1_kernel<<<2, 64, 0, c->stream>>>(cs, division, margin, test_scale);
         {
             ProfScope ps(c, "hessian_stats");
@@ -1608,19 +1039,8 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
         }
         chain_post_kernel<<<1, 64, 0, c->stream>>>(cs);
         NL_CHECK_LAUNCH();
-        {
-            Lattice L; FieldSrc fs;
-            if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-            if ((rc = make_field(c, NL_FIELD_FROB, fs, err, errlen))) return rc;
-            if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-            fs.norm_dev = cs->norm;
-            const i64 total = L.cz * L.cy * L.cx;
-            ProfScope ps(c, "sample");
-            sample_edges_kernel<<<1, 64, 0, c->stream>>>(cs->h_exact.res, NL_CHAIN_BINS, cs->h_exact.edges, cs->h_exact.res + 4);
-            const size_t sh = (size_t)(NL_CHAIN_BINS + 2) * 4 + (size_t)NL_CHAIN_BINS * 4;
-            if (total > 0) sample_hist_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, sh, c->stream>>>(fs, geom(c), L, cs->h_exact.edges, NL_CHAIN_BINS, cs->h_exact.counts, cs->h_exact.res + 4);
-            NL_CHECK_LAUNCH();
-        }
+        // the exact round (an image lives on one context: no reduction)
+        if ((rc = sample_exact_round(c, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_exact, cs->norm, c->stream, false, err, errlen))) return rc;
         chain_thr2_kernel<<<1, 64, 0, c->stream>>>(cs, division);
         NL_CHECK_LAUNCH();
         VessP vp{};
@@ -1643,34 +1063,17 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
         NL_CHECK_LAUNCH();
         return NL_OK;
     }
-    if (!chain_unfused_sampling()) {
-        if ((rc = range_hist_pair_enqueue(c, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, (char *)&cs->h_raw, nullptr, nullptr, err, errlen))) return rc;
-    } else {
-        if ((rc = range_hist_enqueue_at(c, NL_FIELD_GAUSS, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, nullptr, err, errlen))) return rc;
-        if ((rc = range_hist_enqueue_at(c, NL_FIELD_FROB, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_raw, nullptr, err, errlen))) return rc;
-    }
+    if ((rc = sample_first_round(c, NL_FIELD_GAUSS, NL_FIELD_FROB, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, (char *)&cs->h_raw, nullptr, nullptr, true, err, errlen))) return rc;
     chain_thr1_kernel<<<2, 64, 0, c->stream>>>(cs, division, margin, test_scale);
     NL_CHECK_LAUNCH();
     if ((rc = spec_enqueue(c, spacing, 0.0f, 0.0f, z0, z1, cs->stats, &cs->cnt_walk, &cs->fsq_lo, err, errlen))) return rc;
     // (With the resolve kernel held back, the exact round of the scale on the side stream as well was measured: no gain, docs/HISTORY.md.)
-    const bool defer = resolve_defer_ok(c) && c->fsq_cache_valid;     // (the cache is this scale's: use_fsq_cache below launches nothing)
+    const bool defer = resolve_defer_ok(c) && c->fsq_cache_valid;     // (the cache is this scale's: the exact round below launches nothing to fill it)
     hipStream_t st = c->stream;
     chain_post_kernel<<<1, 64, 0, st>>>(cs);
     NL_CHECK_LAUNCH();
-    {   // the exact round: edges from the normalised range, histogram of the cached frob_sq under the device's normalisation
-        Lattice L; FieldSrc fs;
-        if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-        if ((rc = make_field(c, NL_FIELD_FROB, fs, err, errlen))) return rc;
-        if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-        fs.norm_dev = cs->norm;
-        const i64 total = L.cz * L.cy * L.cx;
-        ProfScope ps(c, "sample", st);
-        sample_edges_kernel<<<1, 64, 0, st>>>(cs->h_exact.res, NL_CHAIN_BINS, cs->h_exact.edges, cs->h_exact.res + 4);
-        const size_t sh = (size_t)(NL_CHAIN_BINS + 2) * 4 + (size_t)NL_CHAIN_BINS * 4;
-        if (total > 0) sample_hist_kernel<<<grid1d(total, 256, sample_grid_cap()), 256, sh, st>>>(fs, geom(c), L, cs->h_exact.edges, NL_CHAIN_BINS, cs->h_exact.counts, cs->h_exact.res + 4);
-        NL_CHECK_LAUNCH();
-        if (fused(c) && (rc = reduce_u64_sum(c, cs->h_exact.counts, NL_CHAIN_BINS, err, errlen))) return rc;
-    }
+    // the exact round: edges from the normalised range, histogram of the cached frob_sq under the device's normalisation
+    if ((rc = sample_exact_round(c, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_exact, cs->norm, st, true, err, errlen))) return rc;
     chain_thr2_kernel<<<1, 64, 0, st>>>(cs, division);
     NL_CHECK_LAUNCH();
     VessP vp{};
@@ -2017,7 +1420,7 @@ static int mask_volume_fused_enqueue(nl_ctx *c, float thr, const float *thr_dev,
         c->f[c->i_vmax], bD, c->f[dst], v, wpr, c->own_lo, c->own_hi);
     NL_CHECK_LAUNCH();
     // a fused communicator: the count comes back GLOBAL (one collective on the stream instead of a host-level all-reduce behind the call)
-    if (fused(c)) NL_NCCL(rccl().AllReduce(d_cnt, d_cnt, 1, ncclUint64, ncclSum, (ncclComm_t)c->comm, c->stream));
+    if (fused(c)) return reduce_u64_sum(c, d_cnt, 1, err, errlen);
     return NL_OK;
 }
 static void mask_volume_fused_commit(nl_ctx *c, int dst) {
@@ -2059,14 +1462,15 @@ static int pct_enqueue(nl_ctx *c, const float *samples, const unsigned int *d_n,
     unsigned int *hist = (unsigned int *)((char *)c->d_pct + 128);
     NL_HIP(hipMemcpyAsync(&rec->n, d_n, 4, hipMemcpyDeviceToDevice, c->stream));
     NL_HIP(hipMemcpyAsync(&rec->n_local, d_n, 4, hipMemcpyDeviceToDevice, c->stream));
-    if (fused(c)) NL_NCCL(rccl().AllReduce(&rec->n, &rec->n, 1, ncclUint32, ncclSum, (ncclComm_t)c->comm, c->stream));
+    int rc;
+    if (fused(c) && (rc = reduce_u32_sum(c, &rec->n, 1, err, errlen))) return rc;
     ProfScope ps(c, "sample");
     pct_begin_kernel<<<1, 64, 0, c->stream>>>(rec, q);
     const unsigned grid = grid1d(max_n > 0 ? max_n : 1, 256, 256 * 256);
 #define NL_PCT_LEVEL(L)                                                                                            \
     NL_HIP(hipMemsetAsync(hist, 0, (size_t)2 * PCT_BINS * 4, c->stream));                                           \
     pct_hist_kernel<L><<<grid, 256, 0, c->stream>>>(samples, d_n, rec, hist);                                       \
-    if (fused(c)) NL_NCCL(rccl().AllReduce(hist, hist, (size_t)2 * PCT_BINS, ncclUint32, ncclSum, (ncclComm_t)c->comm, c->stream)); \
+    if (fused(c) && (rc = reduce_u32_sum(c, hist, (size_t)2 * PCT_BINS, err, errlen))) return rc;                    \
     pct_select_kernel<L><<<1, 256, 0, c->stream>>>(rec, hist);
     NL_PCT_LEVEL(0) NL_PCT_LEVEL(1) NL_PCT_LEVEL(2)
 #undef NL_PCT_LEVEL
@@ -2083,11 +1487,6 @@ extern "C" int nl_tail_enqueue(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx, do
     if (c->two_d) return nl_fail(err, errlen, NL_EINVAL, "nl_tail_enqueue is the 3-D epilogue");
     int rc;
     if ((rc = pct_buffers(c, err, errlen))) return rc;
-    Lattice L; FieldSrc fs;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, NL_FIELD_VESSELNESS, fs, err, errlen))) return rc;       // (joins the side stream)
-    const i64 total = L.cz * L.cy * L.cx;
-    if (total > c->n) return nl_fail(err, errlen, NL_EINVAL, "lattice larger than the volume");
     float *stage = c->f[(c->i_gauss + 1) % 3];
     if (stage == c->f[c->i_vmax]) return nl_fail(err, errlen, NL_ESTATE, "no free volume for the samples");
     // the pre-zeroed label volume is that very volume (the one after the current Gaussian): the samples borrow its first `total` words,
@@ -2095,12 +1494,9 @@ extern "C" int nl_tail_enqueue(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx, do
     const bool stage_pz = pz_is(c, stage);
     unsigned int *d_n = (unsigned int *)((char *)c->d_pct + 64);
     unsigned long long *d_cnt = (unsigned long long *)((char *)c->d_pct + 72);
-    NL_HIP(zero_small(d_n, 4, c->stream));
-    if (total > 0) {
-        ProfScope ps(c, "sample");
-        sample_gather_pos_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(fs, geom(c), L, stage, d_n);
-        NL_CHECK_LAUNCH();
-    }
+    i64 total;
+    if ((rc = sample_gather_pos_enqueue(c, NL_FIELD_VESSELNESS, sz, sy, sx, stage, d_n, c->n, &total, err, errlen))) return rc;       // (joins the side stream)
+    if (total > c->n) return nl_fail(err, errlen, NL_EINVAL, "lattice larger than the volume");
     if ((rc = pct_enqueue(c, stage, d_n, total, (float)q, err, errlen))) return rc;
     if (stage_pz && total > 0) NL_HIP(hipMemsetAsync(stage, 0, (size_t)total * 4, c->stream));
     // the samples sit in a volume the epilogue may write (dst): the selection above is complete before it does (stream order)
@@ -2137,21 +1533,13 @@ extern "C" int nl_mask_volume_dev(nl_ctx *c, int64_t sz, int64_t sy, int64_t sx,
     NL_ENTER(c);
     int rc;
     if ((rc = pct_buffers(c, err, errlen))) return rc;
-    Lattice L; FieldSrc fs;
-    if ((rc = make_lattice(c, sz, sy, sx, L, err, errlen))) return rc;
-    if ((rc = make_field(c, NL_FIELD_FRANGI, fs, err, errlen))) return rc;
-    const i64 total = L.cz * L.cy * L.cx;
-    if (total > c->n) return nl_fail(err, errlen, NL_EINVAL, "lattice larger than the volume");
     float *stage = nullptr;                                  // a free volume: neither the frame nor the current Gaussian
     for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != c->f[c->i_vmax]) stage = c->f[k];
     if (!stage) return nl_fail(err, errlen, NL_ESTATE, "no free volume for the samples");
     unsigned int *d_n = (unsigned int *)((char *)c->d_pct + 64);
-    NL_HIP(zero_small(d_n, 4, c->stream));
-    if (total > 0) {
-        ProfScope ps(c, "sample");
-        sample_gather_pos_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(fs, geom(c), L, stage, d_n);
-        NL_CHECK_LAUNCH();
-    }
+    i64 total;
+    if ((rc = sample_gather_pos_enqueue(c, NL_FIELD_FRANGI, sz, sy, sx, stage, d_n, c->n, &total, err, errlen))) return rc;
+    if (total > c->n) return nl_fail(err, errlen, NL_EINVAL, "lattice larger than the volume");
     if ((rc = pct_enqueue(c, stage, d_n, total, (float)q, err, errlen))) return rc;
     int dst;
     if ((rc = mask_volume_enqueue(c, 0.0f, &((PctRec *)c->d_pct)->thr, &dst, err, errlen))) return rc;
@@ -2213,11 +1601,6 @@ extern "C" int nl_gauss_store(nl_ctx *c, float *host, int64_t z0, int64_t z1, ch
 }
 
 // ------------------------------------------------------------------------------ slab helpers ----
-static float *field_ptr(nl_ctx *c, int field) {
-    if (field == NL_FIELD_GAUSS) return gauss_cur(c);
-    if (field == NL_FIELD_FRANGI) return c->f[c->i_vmax];
-    return nullptr;
-}
 
 extern "C" int nl_planes_get(nl_ctx *c, int field, int64_t z0, int64_t z1, float *host, char *err, size_t errlen) {
     NL_ENTER(c);
@@ -2237,393 +1620,6 @@ extern "C" int nl_planes_put(nl_ctx *c, int field, int64_t z0, int64_t z1, const
     return NL_OK;
 }
 
-
-extern "C" int nl_comm_unique_id(char *id128, char *err, size_t errlen) {
-    if (!id128) return nl_fail(err, errlen, NL_EINVAL, "id buffer is NULL");
-    ncclUniqueId id;
-    {
-        (void)hipGetLastError();        // (see comm_acquire)
-        ncclResult_t r_ = rccl().GetUniqueId(&id);
-        if (r_ != ncclSuccess) return nl_fail(err, errlen, NL_ECOMM, "ncclGetUniqueId: %s", rccl().GetErrorString(r_));
-    }
-    static_assert(sizeof(id) == 128, "ncclUniqueId is 128 bytes");
-    memcpy(id128, &id, 128);
-    return NL_OK;
-}
-
-// An id of the loopback transport (loopback.inc): `world` contexts of THIS process, one host thread per rank, exchange
-// through device-to-device copies on the very streams, with the very offsets and counts RCCL would be given.
-extern "C" int nl_comm_loopback_id(char *id128, char *err, size_t errlen) {
-    if (!id128) return nl_fail(err, errlen, NL_EINVAL, "id buffer is NULL");
-    lb::get_unique_id(id128);
-    return NL_OK;
-}
-
-// RCCL communicators outlive their context: a context that closes hands its communicators to a per-process pool, and the next
-// context of the same (device, world, rank, role) takes them from there instead of creating new ones (every rank does the
-// same, so the pool's state is the same everywhere; the id the caller brings is then not used -- the CONSTRAINT: the ranks of a
-// job open and close their contexts in the same order, which the SPMD stage classes do; a rank that restarts alone, or a context
-// that failed in a collective (its communicators are destroyed instead, `comm_poisoned`), needs fresh ids on every rank).  Why: a process in which an RCCL
-// communicator has been destroyed -- or created beside an older one -- runs every later slab step 9-18 % slower (measured at
-// world 1 on a 128 x 2048 x 2048 slab: 29.9 -> 32.7 ms synchronous, 30.1 -> 35.3 ms with the device chain; with the earlier
-// communicators neither destroyed nor replaced: 30.1), and the stages of a run (Filter, then Label) each open a context.
-// Loopback communicators are plain host objects and are destroyed with their context.
-struct PooledComm { int device, world, rank, role; ncclComm_t comm; };
-static std::mutex g_comm_pool_mu;
-static std::vector<PooledComm> g_comm_pool;
-static ncclComm_t comm_pool_take(int device, int world, int rank, int role) {
-    std::lock_guard<std::mutex> lk(g_comm_pool_mu);
-    for (size_t i = 0; i < g_comm_pool.size(); ++i) {
-        const PooledComm &p = g_comm_pool[i];
-        if (p.device == device && p.world == world && p.rank == rank && p.role == role) {
-            ncclComm_t c = p.comm;
-            g_comm_pool.erase(g_comm_pool.begin() + (long)i);
-            return c;
-        }
-    }
-    return nullptr;
-}
-static void comm_release(nl_ctx *c, void *comm, int role) {
-    if (!comm) return;
-    // a communicator whose context saw a collective fail may be out of step with its peers: never hand it to a later context
-    if (lb::is_ours(comm) || c->comm_poisoned || getenv("NELLIE_DESTROY_COMMS")) { rccl().CommDestroy((ncclComm_t)comm); return; }
-    std::lock_guard<std::mutex> lk(g_comm_pool_mu);
-    g_comm_pool.push_back(PooledComm{c->device, c->world, c->rank, role, (ncclComm_t)comm});
-}
-static int comm_acquire(nl_ctx *c, int world, int rank, const char *id128, int role, ncclComm_t *out, char *err, size_t errlen) {
-    ncclUniqueId id;
-    memcpy(&id, id128, 128);
-    if (!lb::is_loopback_id(id128)) {
-        ncclComm_t pooled = comm_pool_take(c->device, world, rank, role);
-        if (pooled) { *out = pooled; return NL_OK; }
-    }
-    (void)hipGetLastError();        // RCCL checks the thread's last HIP error during init: it must not inherit one that was handled long ago
-    NL_NCCL(rccl().CommInitRank(out, world, id, rank));
-    return NL_OK;
-}
-
-extern "C" int nl_comm_init(nl_ctx *c, int world, int rank, const char *id128, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!id128 || world < 1 || rank < 0 || rank >= world) return nl_fail(err, errlen, NL_EINVAL, "bad communicator arguments");
-    if (c->comm) return nl_fail(err, errlen, NL_ESTATE, "the context already has a communicator");
-    ncclComm_t comm;
-    int rc = comm_acquire(c, world, rank, id128, 1, &comm, err, errlen);
-    if (rc) return rc;
-    c->comm = comm; c->world = world; c->rank = rank;
-    return NL_OK;
-}
-
-// Ghost-plane exchange with the Z neighbours over RCCL (xGMI).  The `depth` owned planes that start `offset` planes inside
-// this rank's boundary go to the neighbour's ghost planes at the same distance from the interface, and the neighbours'
-// come into ours: low side  send [own_lo + offset, +depth)  recv [own_lo - offset - depth, own_lo - offset),
-//                 high side send [own_hi - offset - depth, own_hi - offset)  recv [own_hi + offset, +depth).
-// offset 0 = the classic halo.  Asynchronous on the context stream; with `async` != 0 (and a second communicator,
-// nl_comm_init2) it runs on a stream and a communicator of its own, ordered after everything submitted so far, and the next
-// nl_gauss_step waits for it: the exchange for cascade step s+1 then travels while scale s is being evaluated.
-static int halo_exchange_impl(nl_ctx *c, int field, int64_t offset, int64_t depth, int async, char *err, size_t errlen) {
-    if (!c->comm) return nl_fail(err, errlen, NL_ESTATE, "nl_halo_exchange before nl_comm_init");
-    c->fsq_cache_valid = 0;
-    float *p = field_ptr(c, field);
-    if (!p) return nl_fail(err, errlen, NL_EINVAL, "nl_halo_exchange: field %d has no volume", field);
-    const i64 plane = c->ny * c->nx;
-    const bool has_lo = c->rank > 0, has_hi = c->rank + 1 < c->world;
-    if (depth < 1 || offset < 0 || offset + depth > c->own_hi - c->own_lo || (has_lo && offset + depth > c->own_lo) ||
-        (has_hi && offset + depth > c->nzl - c->own_hi))
-        return nl_fail(err, errlen, NL_EINVAL, "halo planes [%lld, %lld) from the interface do not fit the slab (own %lld, ghosts %lld/%lld)", (i64)offset,
-                       (i64)(offset + depth), (i64)(c->own_hi - c->own_lo), (i64)c->own_lo, (i64)(c->nzl - c->own_hi));
-    const bool side = async && c->comm2;
-    ncclComm_t comm = (ncclComm_t)(side ? c->comm2 : c->comm);
-    hipStream_t st = c->stream;
-    if (side) {
-        if (!c->xstream) {
-            NL_HIP(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
-            NL_HIP(hipEventCreateWithFlags(&c->ev_x_main, hipEventDisableTiming));
-            NL_HIP(hipEventCreateWithFlags(&c->ev_x_done, hipEventDisableTiming));
-        }
-        if (c->halo_pending) NL_HIP(hipStreamWaitEvent(c->stream, c->ev_x_done, 0));      // one exchange in flight at a time
-        NL_HIP(hipEventRecord(c->ev_x_main, c->stream));
-        NL_HIP(hipStreamWaitEvent(c->xstream, c->ev_x_main, 0));
-        st = c->xstream;
-    }
-    ProfScope ps(c, "halo", st);
-    NL_NCCL(rccl().GroupStart());
-    if (has_lo) {
-        NL_NCCL(rccl().Send(p + (c->own_lo + offset) * plane, (size_t)(depth * plane), ncclFloat, c->rank - 1, comm, st));
-        NL_NCCL(rccl().Recv(p + (c->own_lo - offset - depth) * plane, (size_t)(depth * plane), ncclFloat, c->rank - 1, comm, st));
-    }
-    if (has_hi) {
-        NL_NCCL(rccl().Send(p + (c->own_hi - offset - depth) * plane, (size_t)(depth * plane), ncclFloat, c->rank + 1, comm, st));
-        NL_NCCL(rccl().Recv(p + (c->own_hi + offset) * plane, (size_t)(depth * plane), ncclFloat, c->rank + 1, comm, st));
-    }
-    NL_NCCL(rccl().GroupEnd());
-    if (side) {
-        NL_HIP(hipEventRecord(c->ev_x_done, c->xstream));
-        c->halo_pending = 1;
-    }
-    return NL_OK;
-}
-extern "C" int nl_halo_exchange(nl_ctx *c, int field, int64_t depth, char *err, size_t errlen) {
-    NL_ENTER(c);
-    return halo_exchange_impl(c, field, 0, depth, 0, err, errlen);
-}
-extern "C" int nl_halo_exchange_at(nl_ctx *c, int field, int64_t offset, int64_t depth, int async, char *err, size_t errlen) {
-    NL_ENTER(c);
-    return halo_exchange_impl(c, field, offset, depth, async, err, errlen);
-}
-// second communicator (its own unique id): carries the asynchronous ghost-plane exchanges, so that they do not serialise
-// with the reductions of the first one
-extern "C" int nl_comm_init2(nl_ctx *c, int world, int rank, const char *id128, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!id128 || world != c->world || rank != c->rank || !c->comm) return nl_fail(err, errlen, NL_EINVAL, "nl_comm_init2 needs the world / rank of nl_comm_init");
-    if (c->comm2) return nl_fail(err, errlen, NL_ESTATE, "the context already has a second communicator");
-    ncclComm_t comm;
-    int rc = comm_acquire(c, world, rank, id128, 2, &comm, err, errlen);
-    if (rc) return rc;
-    c->comm2 = comm;
-    return NL_OK;
-}
-
-// Small all-reduce of host values through RCCL: dtype 0 = int64, 1 = float32; op 0 = sum, 1 = min, 2 = max.
-extern "C" int nl_allreduce(nl_ctx *c, void *host_inout, int64_t count, int dtype, int op, char *err, size_t errlen) {
-    NL_ENTER(c);
-    NL_KEEP_SUPPORT(c);
-    if (!c->comm) return nl_fail(err, errlen, NL_ESTATE, "nl_allreduce before nl_comm_init");
-    const size_t es = dtype == 0 ? 8 : 4;
-    if (!host_inout || count < 1 || (size_t)count * es > (1 << 15) || dtype < 0 || dtype > 1 || op < 0 || op > 2)
-        return nl_fail(err, errlen, NL_EINVAL, "bad all-reduce arguments");
-    memcpy(c->h_small, host_inout, (size_t)count * es);
-    NL_HIP(hipMemcpyAsync(c->d_small, c->h_small, (size_t)count * es, hipMemcpyHostToDevice, c->stream));
-    const ncclRedOp_t ops[3] = {ncclSum, ncclMin, ncclMax};
-    NL_NCCL(rccl().AllReduce(c->d_small, c->d_small, (size_t)count, dtype == 0 ? ncclInt64 : ncclFloat, ops[op], (ncclComm_t)c->comm, c->stream));
-    NL_HIP(hipMemcpyAsync(c->h_small, c->d_small, (size_t)count * es, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    memcpy(host_inout, c->h_small, (size_t)count * es);
-    return NL_OK;
-}
-
-extern "C" int nl_comm_fuse(nl_ctx *c, int on, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (on && !c->comm) return nl_fail(err, errlen, NL_ESTATE, "nl_comm_fuse before nl_comm_init");
-    c->fuse_reduce = on ? 1 : 0;
-    return NL_OK;
-}
-
-// The positive samples of ALL ranks in one call with one wait (round 4): every rank compacts its samples into a block
-// [count | samples ...] of block_items + 1 floats (block_items: a bound on any rank's sample points that the callers derive from
-// the global geometry, identical everywhere), the blocks are all-gathered over RCCL on the context stream and land in page-locked
-// memory.  mode 0: the lattice arr[::a, ::b, ::c] of `field` (filtering.py:348-363), mode 1: flat[a::b] (labelling.py:418-433).
-// out receives the samples rank by rank, counts[r] how many rank r contributed.  Before: a download, then nl_allgather_var's two
-// collectives with a wait each.
-extern "C" int nl_positive_samples_world(nl_ctx *c, int field, int mode, int64_t a, int64_t b, int64_t cc, int64_t block_items,
-                                         float *out, int64_t cap, int64_t *counts, char *err, size_t errlen) {
-    NL_ENTER(c);
-    NL_KEEP_SUPPORT(c);
-    if (!c->comm) return nl_fail(err, errlen, NL_ESTATE, "nl_positive_samples_world before nl_comm_init");
-    if (block_items < 0 || !counts || (mode != 0 && mode != 1)) return nl_fail(err, errlen, NL_EINVAL, "bad arguments");
-    const int W = c->world;
-    const size_t blk = (size_t)block_items + 1;                       // floats per rank
-    const size_t need = blk * (size_t)(W + 1) * 4;
-    if (need > c->ag_cap) {
-        if (c->d_ag) hipFree(c->d_ag);
-        c->d_ag = nullptr; c->ag_cap = 0;
-        NL_HIP(hipMalloc(&c->d_ag, need + need / 2));
-        c->ag_cap = need + need / 2;
-    }
-    if (blk * W * 4 > c->h_ag_cap) {
-        if (c->h_ag) hipHostFree(c->h_ag);
-        c->h_ag = nullptr; c->h_ag_cap = 0;
-        NL_HIP(hipHostMalloc(&c->h_ag, blk * W * 4 * 3 / 2, hipHostMallocDefault));
-        c->h_ag_cap = blk * W * 4 * 3 / 2;
-    }
-    float *d_send = (float *)c->d_ag, *d_recv = d_send + blk;
-    NL_HIP(zero_small(d_send, 4, c->stream));
-    int rc;
-    i64 points = 0;
-    if (mode == 0) {
-        Lattice L; FieldSrc fs;
-        if ((rc = make_lattice(c, a, b, cc, L, err, errlen))) return rc;
-        if ((rc = make_field(c, field, fs, err, errlen))) return rc;
-        if ((rc = use_fsq_cache(c, fs, L, err, errlen))) return rc;
-        points = L.cz * L.cy * L.cx;
-        if (points > block_items) return nl_fail(err, errlen, NL_EINVAL, "%lld lattice points in this slab, block of %lld", (long long)points, (long long)block_items);
-        if (points) {
-            ProfScope ps(c, "sample");
-            sample_gather_pos_kernel<<<(unsigned)((points + 255) / 256), 256, 0, c->stream>>>(fs, geom(c), L, d_send + 1, (unsigned int *)d_send);
-            NL_CHECK_LAUNCH();
-        }
-    } else {
-        if (b < 1 || a < 0) return nl_fail(err, errlen, NL_EINVAL, "bad offset/step");
-        if (field != NL_FIELD_FRANGI && field != NL_FIELD_GAUSS) return nl_fail(err, errlen, NL_EINVAL, "flat sampling supports GAUSS/FRANGI");
-        const i64 plane = c->ny * c->nx;
-        const i64 g_begin = (c->gz0 + c->own_lo) * plane, g_end = (c->gz0 + c->own_hi) * plane;
-        const i64 k0 = g_begin > a ? (g_begin - a + b - 1) / b : 0;
-        const i64 k1 = g_end > a ? (g_end - a + b - 1) / b : 0;
-        points = k1 > k0 ? k1 - k0 : 0;
-        if (points > block_items) return nl_fail(err, errlen, NL_EINVAL, "%lld sample points in this slab, block of %lld", (long long)points, (long long)block_items);
-        if (points) {
-            const float *src = (field == NL_FIELD_FRANGI) ? c->f[c->i_vmax] : gauss_cur(c);
-            ProfScope ps(c, "sample");
-            flat_gather_pos_kernel<<<(unsigned)((points + 255) / 256), 256, 0, c->stream>>>(src, -c->gz0 * plane, a + k0 * b, b, points, d_send + 1, (unsigned int *)d_send);
-            NL_CHECK_LAUNCH();
-        }
-    }
-    {
-        ProfScope ps(c, "halo");
-        NL_NCCL(rccl().AllGather(d_send, d_recv, blk, ncclFloat, (ncclComm_t)c->comm, c->stream));
-    }
-    NL_HIP(hipMemcpyAsync(c->h_ag, d_recv, blk * W * 4, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    i64 total = 0;
-    const float *h = (const float *)c->h_ag;
-    for (int r = 0; r < W; ++r) {
-        unsigned int k; memcpy(&k, h + (size_t)r * blk, 4);
-        if ((i64)k > block_items) return nl_fail(err, errlen, NL_ESTATE, "rank %d reports %u samples in a block of %lld", r, k, (long long)block_items);
-        counts[r] = (int64_t)k;
-        if (total + (i64)k > cap || (k && !out)) return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld too small", (long long)cap);
-        if (k) memcpy(out + total, h + (size_t)r * blk + 1, (size_t)k * 4);
-        total += (i64)k;
-    }
-    return NL_OK;
-}
-
-// Variable-size all-gather of host bytes (see include/nellie_amd.h).  Two collectives: the sizes, then the padded blocks.
-extern "C" int nl_allgather_bytes(nl_ctx *c, const void *send, int64_t nbytes, void *recv, int64_t max_bytes, int64_t *bytes_of,
-                                  char *err, size_t errlen) {
-    NL_ENTER(c);
-    NL_KEEP_SUPPORT(c);
-    if (!c->comm) return nl_fail(err, errlen, NL_ESTATE, "nl_allgather_bytes before nl_comm_init");
-    if (nbytes < 0 || max_bytes < 1 || nbytes > max_bytes || !recv || !bytes_of || (nbytes && !send))
-        return nl_fail(err, errlen, NL_EINVAL, "bad all-gather arguments");
-    const int W = c->world;
-    // sizes through the small scratch
-    long long *hs = (long long *)c->h_small;
-    hs[0] = nbytes;
-    NL_HIP(hipMemcpyAsync(c->d_small, hs, 8, hipMemcpyHostToDevice, c->stream));
-    NL_NCCL(rccl().AllGather(c->d_small, (char *)c->d_small + 64, 1, ncclInt64, (ncclComm_t)c->comm, c->stream));
-    NL_HIP(hipMemcpyAsync(hs, (char *)c->d_small + 64, (size_t)W * 8, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < W; ++r) { bytes_of[r] = hs[r]; if (hs[r] > max_bytes) return nl_fail(err, errlen, NL_EINVAL, "rank %d sends %lld bytes, more than max_bytes = %lld", r, hs[r], (long long)max_bytes); }
-    // blocks through a staging buffer that grows on demand
-    const size_t need = (size_t)max_bytes * (size_t)(W + 1);
-    if (need > c->ag_cap) {
-        if (c->d_ag) hipFree(c->d_ag);
-        c->d_ag = nullptr; c->ag_cap = 0;
-        NL_HIP(hipMalloc(&c->d_ag, need));
-        c->ag_cap = need;
-    }
-    char *d_send = (char *)c->d_ag, *d_recv = d_send + max_bytes;
-    if (nbytes) NL_HIP(hipMemcpyAsync(d_send, send, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
-    NL_NCCL(rccl().AllGather(d_send, d_recv, (size_t)max_bytes, ncclChar, (ncclComm_t)c->comm, c->stream));
-    NL_HIP(hipMemcpyAsync(recv, d_recv, (size_t)max_bytes * W, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    return NL_OK;
-}
-
-// The same without a size negotiated by the caller: the block size is the largest of the gathered sizes, and the blocks land
-// in a page-locked buffer the context owns (*recv, valid until the next call; rank r's block at r * *stride).
-extern "C" int nl_allgather_var(nl_ctx *c, const void *send, int64_t nbytes, void **recv, int64_t *stride, int64_t *bytes_of,
-                                char *err, size_t errlen) {
-    NL_ENTER(c);
-    NL_KEEP_SUPPORT(c);
-    if (!c->comm) return nl_fail(err, errlen, NL_ESTATE, "nl_allgather_var before nl_comm_init");
-    if (nbytes < 0 || !recv || !stride || !bytes_of || (nbytes && !send)) return nl_fail(err, errlen, NL_EINVAL, "bad all-gather arguments");
-    const int W = c->world;
-    long long *hs = (long long *)c->h_small;
-    hs[0] = nbytes;
-    NL_HIP(hipMemcpyAsync(c->d_small, hs, 8, hipMemcpyHostToDevice, c->stream));
-    NL_NCCL(rccl().AllGather(c->d_small, (char *)c->d_small + 64, 1, ncclInt64, (ncclComm_t)c->comm, c->stream));
-    NL_HIP(hipMemcpyAsync(hs, (char *)c->d_small + 64, (size_t)W * 8, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    long long mx = 16;
-    for (int r = 0; r < W; ++r) { bytes_of[r] = hs[r]; if (hs[r] > mx) mx = hs[r]; }
-    mx = (mx + 15) & ~15ll;
-    const size_t need = (size_t)mx * (size_t)(W + 1);
-    if (need > c->ag_cap) {
-        if (c->d_ag) hipFree(c->d_ag);
-        c->d_ag = nullptr; c->ag_cap = 0;
-        NL_HIP(hipMalloc(&c->d_ag, need + need / 2));          // head room: the tables of the next phase / frame differ a little
-        c->ag_cap = need + need / 2;
-    }
-    if ((size_t)mx * W > c->h_ag_cap) {
-        if (c->h_ag) hipHostFree(c->h_ag);
-        c->h_ag = nullptr; c->h_ag_cap = 0;
-        const size_t cap = (size_t)mx * W * 3 / 2;
-        NL_HIP(hipHostMalloc(&c->h_ag, cap, hipHostMallocDefault));
-        c->h_ag_cap = cap;
-    }
-    char *d_send = (char *)c->d_ag, *d_recv = d_send + mx;
-    if (nbytes) NL_HIP(hipMemcpyAsync(d_send, send, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
-    NL_NCCL(rccl().AllGather(d_send, d_recv, (size_t)mx, ncclChar, (ncclComm_t)c->comm, c->stream));
-    NL_HIP(hipMemcpyAsync(c->h_ag, d_recv, (size_t)mx * W, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    *recv = c->h_ag; *stride = mx;
-    return NL_OK;
-}
-
-// ---- Label's threshold sampling (flat strided samples of the Frangi volume, labelling.py:426-433) ----
-extern "C" int nl_flat_sample_gather(nl_ctx *c, int field, int64_t offset, int64_t step, float *out, int64_t cap, int64_t *n,
-                                     char *err, size_t errlen) {
-    NL_ENTER_KEEP_PZ(c);
-    NL_KEEP_SUPPORT(c);
-    if (step < 1 || offset < 0) return nl_fail(err, errlen, NL_EINVAL, "bad offset/step");
-    if (field != NL_FIELD_FRANGI && field != NL_FIELD_GAUSS) return nl_fail(err, errlen, NL_EINVAL, "flat sampling supports GAUSS/FRANGI");
-    // flat index runs over the GLOBAL volume; this rank contributes indices inside its owned planes
-    const i64 plane = c->ny * c->nx;
-    const i64 g_begin = (c->gz0 + c->own_lo) * plane, g_end = (c->gz0 + c->own_hi) * plane;
-    i64 k0 = 0;
-    if (g_begin > offset) k0 = (g_begin - offset + step - 1) / step;
-    i64 k1 = (g_end > offset) ? (g_end - offset + step - 1) / step : 0;    // k in [k0,k1)
-    const i64 count = k1 > k0 ? k1 - k0 : 0;
-    if (n) *n = count;
-    if (count == 0 || (!out && cap == 0)) return NL_OK;   // size query
-    if (!out || cap < count) return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld < %lld samples", (i64)cap, count);
-    const float *src = (field == NL_FIELD_FRANGI) ? c->f[c->i_vmax] : gauss_cur(c);
-    float *stage = nullptr;                                  // a free volume, not the pre-zeroed one while there is another
-    for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src && !pz_is(c, c->f[k])) { stage = c->f[k]; break; }
-    if (!stage) for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src) { stage = c->f[k]; break; }
-    pz_touch(c, stage);
-    {
-        ProfScope ps(c, "sample");
-        // local flat index = global - gz0*plane
-        flat_gather_kernel<<<(unsigned)((count + 255) / 256), 256, 0, c->stream>>>(src, -c->gz0 * plane, offset + k0 * step, step, count, stage);
-        NL_CHECK_LAUNCH();
-    }
-    NL_HIP(hipMemcpyAsync(out, stage, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    return NL_OK;
-}
-
-// nl_flat_sample_gather restricted to the positive samples, compacted on the device (labelling.py:426-433 takes
-// values[values > 0]); order unspecified.  cap >= the count nl_flat_sample_gather reports.
-extern "C" int nl_flat_sample_gather_positive(nl_ctx *c, int field, int64_t offset, int64_t step, float *out, int64_t cap,
-                                              int64_t *n, char *err, size_t errlen) {
-    NL_ENTER_KEEP_PZ(c);
-    NL_KEEP_SUPPORT(c);
-    if (step < 1 || offset < 0) return nl_fail(err, errlen, NL_EINVAL, "bad offset/step");
-    if (field != NL_FIELD_FRANGI && field != NL_FIELD_GAUSS) return nl_fail(err, errlen, NL_EINVAL, "flat sampling supports GAUSS/FRANGI");
-    const i64 plane = c->ny * c->nx;
-    const i64 g_begin = (c->gz0 + c->own_lo) * plane, g_end = (c->gz0 + c->own_hi) * plane;
-    i64 k0 = 0;
-    if (g_begin > offset) k0 = (g_begin - offset + step - 1) / step;
-    i64 k1 = (g_end > offset) ? (g_end - offset + step - 1) / step : 0;
-    const i64 count = k1 > k0 ? k1 - k0 : 0;
-    if (n) *n = 0;
-    if (count == 0) return NL_OK;
-    if (!out || cap < count) return nl_fail(err, errlen, NL_EINVAL, "output capacity %lld < %lld samples", (i64)cap, count);
-    const float *src = (field == NL_FIELD_FRANGI) ? c->f[c->i_vmax] : gauss_cur(c);
-    float *stage = nullptr;                                  // a free volume, not the pre-zeroed one while there is another
-    for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src && !pz_is(c, c->f[k])) { stage = c->f[k]; break; }
-    if (!stage) for (int k = 0; k < 3; ++k) if (k != c->i_gauss && c->f[k] != src) { stage = c->f[k]; break; }
-    pz_touch(c, stage);
-    unsigned int *d_n = (unsigned int *)c->d_small;
-    NL_HIP(zero_small(d_n, 4, c->stream));
-    {
-        ProfScope ps(c, "sample");
-        flat_gather_pos_kernel<<<(unsigned)((count + 255) / 256), 256, 0, c->stream>>>(src, -c->gz0 * plane, offset + k0 * step, step, count, stage, d_n);
-        NL_CHECK_LAUNCH();
-    }
-    return fetch_counted(c, stage, d_n, count, out, cap, n, err, errlen);
-}
 
 
 // ---------------------------------------------------------------------------------- debug -------

@@ -1,5 +1,12 @@
-// Internal: what the translation units of libnellie_hip.so (nellie_hip.hip, nellie_label.hip, nellie_markers.hip) share on the host
-// side -- the communicator dispatch, the entry-point macros and a few launch helpers.  gfx950 only.
+// Internal: what the translation units of libnellie_hip.so share on the host side -- the communicator dispatch, the entry-point macros,
+// a few launch helpers and the declarations of what one unit defines for the others (at the end of this file):
+//   nellie_hip.hip      Filter: context lifetime, cascade, Hessian walk, device chain, epilogue   -> upload_convert, store_planes, ...
+//   nellie_sample.hip   lattice / flat sampling, histogram records and thresholds               -> the sample_* rounds, fetch_counted, host_edges
+//   nellie_comm.hip     RCCL loader, loopback transport, communicator pool, collectives         -> rccl(), comm_release, reduce_*, ag_reserve, allgather_sizes
+//   nellie_label.hip    Label / Network / streaming                                             -> nl_launch_threshold_pack
+//   nellie_markers.hip  Markers                                                                 -> nl_launch_pack_labels
+//   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the four stage handles share nl_stage.h.
+// gfx950 only.
 #pragma once
 #include <stdarg.h>
 #include <stdlib.h>
@@ -17,7 +24,7 @@
 #define SCAN_CHUNK 4096      // elements per workgroup of the exclusive scans (label_voxels.inc)
 
 // What the entry points call: RCCL's names, dispatched per communicator -- a communicator created from a loopback id
-// (nl_comm_loopback_id) lives in loopback.inc, every other one is RCCL's (dlopen()ed on first use).  Defined in nellie_hip.hip.
+// (nl_comm_loopback_id) lives in loopback.inc, every other one is RCCL's (dlopen()ed on first use).  Defined in nellie_comm.hip.
 struct CommApi {
     std::atomic<int> n_real{0};
     ncclResult_t GetUniqueId(ncclUniqueId *id);
@@ -65,6 +72,12 @@ static inline hipError_t zero_small(void *p, size_t bytes, hipStream_t st) {
 }
 
 static float *gauss_cur(const nl_ctx *c) { return c->gauss_ext ? c->gauss_ext : c->f[c->i_gauss]; }
+static inline float *field_ptr(nl_ctx *c, int field) {      // the fields that are a volume of their own
+    if (field == NL_FIELD_GAUSS) return gauss_cur(c);
+    if (field == NL_FIELD_FRANGI) return c->f[c->i_vmax];
+    return nullptr;
+}
+static inline HessP hessp(const nl_ctx *c) { return HessP{c->hz, c->hy, c->hx, c->hz2, c->hy2, c->hx2}; }
 static VolGeom geom(const nl_ctx *c) {
     VolGeom v{c->nzl, c->ny, c->nx, c->gz0, c->gnz};
     // 128-element chunks read 128 + 2R elements for 128 outputs; 256 halves the excess (about 1 % of the Gaussian passes at 1024^3,
@@ -139,13 +152,47 @@ static inline void pz_touch(nl_ctx *c, const float *p) { if (p == c->pz_buf) c->
 // pass plus one per host-level all-reduce.  Every rank must make the same calls in the same order (they do: the path is SPMD).
 static inline bool fused(const nl_ctx *c) { return c->comm && c->fuse_reduce; }
 
-// defined in nellie_hip.hip, used by the other units
+// ---- defined in nellie_hip.hip ------------------------------------------------------------------------------------------
 int upload_convert(nl_ctx *c, const void *host, int dtype, float *dst, i64 count, char *err, size_t errlen);
-int fetch_counted(nl_ctx *c, const float *stage, const unsigned int *d_n, i64 max_count, float *out, i64 cap, int64_t *n, char *err, size_t errlen);
 int store_planes(nl_ctx *c, const void *dev_base, void *host, size_t elem, int64_t z0, int64_t z1, char *err, size_t errlen);
 int64_t vq_alloc_entries(int64_t nzl, int64_t ny, int64_t nx);
 bool gyx_tiled();
-// kernels of one unit launched from another
+
+// ---- defined in nellie_sample.hip ---------------------------------------------------------------------------------------
+// A histogram record, contiguous so that one transfer brings it back: counts (u64 x nbins) | edges (f32 x nbins + 1, padded to
+// 16 bytes) | res: [0] min bits, [1] max bits, [2..3] count, [4] flag (0 no positive sample, 1 ok, 2 range not finite), 32 bytes.
+// ChainHist (chain.inc) is this layout at NL_CHAIN_BINS.
+struct HistLayout { size_t off_edges, off_res, bytes; };
+constexpr size_t hist_off_res(int nbins) { return (size_t)nbins * 8 + (((size_t)(nbins + 1) * 4 + 15) & ~(size_t)15); }
+constexpr HistLayout hist_layout(int nbins) { return HistLayout{(size_t)nbins * 8, hist_off_res(nbins), hist_off_res(nbins) + 32}; }
+// The first round of a scale, enqueued: the records of field_a and field_b on the lattice (sz, sy, sx) into dA / dB.  The Gaussian /
+// raw-Frobenius pair takes one pass over the lattice where `pair_ok` and NELLIE_CHAIN_UNFUSED_SAMPLING allow, else two single
+// sequences.  hA / hB: pinned mirrors the initial state is uploaded from, or NULL when the caller initialised the records (chain.inc).
+int sample_first_round(nl_ctx *c, int field_a, int field_b, i64 sz, i64 sy, i64 sx, int nbins, char *dA, char *dB, char *hA, char *hB, bool pair_ok,
+                       char *err, size_t errlen);
+// The exact round of a scale on stream `st`: edges from the range already in the record, then the histogram of the cached frob_sq under
+// the normalisation at norm_dev (device memory); reduce: the counts are summed across a fused communicator.
+int sample_exact_round(nl_ctx *c, i64 sz, i64 sy, i64 sx, int nbins, char *rec, const float *norm_dev, hipStream_t st, bool reduce, char *err, size_t errlen);
+// The positive lattice samples of `field`, compacted into dst with their number in *d_n (zeroed here), enqueued.  *total = the lattice
+// points; a lattice of more than `cap` points enqueues nothing -- the caller reports that.
+int sample_gather_pos_enqueue(nl_ctx *c, int field, i64 sz, i64 sy, i64 sx, float *dst, unsigned int *d_n, i64 cap, i64 *total, char *err, size_t errlen);
+int fetch_counted(nl_ctx *c, const float *stage, const unsigned int *d_n, i64 max_count, float *out, i64 cap, int64_t *n, char *err, size_t errlen);
+void host_edges(float first, float last, int nbins, float *edges);       // sample_edges_kernel on the host
+
+// ---- defined in nellie_comm.hip -----------------------------------------------------------------------------------------
+void comm_release(nl_ctx *c, void *comm, int role);      // RCCL communicators go back to a per-process pool (see nl_comm_init)
+// small reductions across the ranks on the context stream, in place.  reduce_range: res = [min bits, max bits, count lo, count hi] of
+// positive float32 samples (unsigned order = float order); two records (res_b != NULL) travel in one group, as do two count arrays
+int reduce_range(nl_ctx *c, unsigned int *res, unsigned int *res_b, char *err, size_t errlen);
+int reduce_u64_sum(nl_ctx *c, unsigned long long *v, size_t n, char *err, size_t errlen, unsigned long long *v_b = nullptr);
+int reduce_u32_sum(nl_ctx *c, unsigned int *v, size_t n, char *err, size_t errlen);
+int reduce_u32_max(nl_ctx *c, unsigned int *v, size_t n, char *err, size_t errlen);
+// the all-gather staging of the context (d_ag on the device, h_ag page-locked) holds at least that many bytes afterwards
+int ag_reserve(nl_ctx *c, size_t device_bytes, size_t host_bytes, char *err, size_t errlen);
+// bytes_of[r] = rank r's nbytes (one collective and one wait, through the small scratch)
+int allgather_sizes(nl_ctx *c, int64_t nbytes, int64_t *bytes_of, char *err, size_t errlen);
+
+// ---- kernels of one unit launched from another ---------------------------------------------------------------------------
 void nl_launch_threshold_pack(unsigned int grid, hipStream_t st, const float *f, const unsigned long long *support, unsigned long long *bits,
                               int has_thr, float thr, int nx, i64 nrows, int wpr, const float *thr_dev);      // nellie_label.hip
 void nl_launch_pack_labels(unsigned int grid, hipStream_t st, const int *lab, unsigned long long *bits, int nx, i64 nrows, int wpr);   // nellie_markers.hip

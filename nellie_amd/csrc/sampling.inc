@@ -1,4 +1,4 @@
-// Part of libnellie_hip.so (gfx950): included by nellie_hip.hip, see include/nellie_amd.h for the C-ABI.
+// Part of libnellie_hip.so (gfx950): included by nellie_sample.hip (and by no other unit), see include/nellie_amd.h for the C-ABI.
 // =================================================================================================
 // kernels: lattice sampling (strided subsample for the thresholds)
 // =================================================================================================

@@ -1,4 +1,4 @@
-// Part of libnellie_hip.so: included by nellie_hip.hip (host code).
+// Part of libnellie_hip.so: included by nellie_sample.hip and nellie_hip.hip (host code).
 // =================================================================================================
 // Histogram thresholds of nellie/utils/gpu_functions.py:23-94 on a finished histogram
 // =================================================================================================

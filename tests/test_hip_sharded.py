@@ -234,6 +234,13 @@ def test_zslab_loopback_with_randomised_transfer_delays(hip, world, delay_us, se
         assert all(p_[1] == ref_thr and p_[2] == ref_counts and p_[4] == ref_n for p_ in parts)
 
 
+GROW_SIZES = (16, 70000, 16)
+
+
+def _payload(rank, size):
+    return ((np.arange(size) * (rank + 3) + rank) % 251).astype(np.uint8)
+
+
 def test_loopback_collectives_known_answers(hip):
     """The transport itself against numpy: all-reduce (sum / min / max, int64 and float32), variable all-gather with empty
     and unequal blocks, on 3 ranks."""
@@ -252,6 +259,9 @@ def test_loopback_collectives_known_answers(hip):
             res["maxf"] = ctx.allreduce(np.array([0.5 * rank, -1.0 - rank], np.float32), "max")
             res["gather"] = ctx.allgather_var(np.arange(rank * 1000, dtype=np.int32) + rank, world)
             res["gather_bytes"] = ctx.allgather_var(np.frombuffer(bytes([rank] * (rank + 1)), np.uint8).copy(), world)
+            # the staging buffers of both all-gathers grow, then serve a smaller payload again
+            res["grow"] = [(ctx.allgather_bytes(_payload(rank, size).tobytes(), size, world), ctx.allgather_var(_payload(rank, size), world))
+                           for size in GROW_SIZES]
             out[rank] = res
             ctx.close()
         except Exception as exc:  # noqa: BLE001
@@ -271,6 +281,8 @@ def test_loopback_collectives_known_answers(hip):
         for q in range(world):
             assert np.array_equal(r["gather"][q], np.arange(q * 1000, dtype=np.int32) + q)
             assert bytes(r["gather_bytes"][q]) == bytes([q] * (q + 1))
+            for size, (fixed, var) in zip(GROW_SIZES, r["grow"]):
+                assert fixed[q] == _payload(q, size).tobytes() and np.array_equal(var[q], _payload(q, size))
 
 
 @pytest.mark.parametrize("fused", [True, False])
