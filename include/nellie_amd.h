@@ -642,6 +642,43 @@ int nl_voxfeat_fetch_nodes(nl_voxfeat *voxfeat, int64_t *lims0, int64_t *lims1, 
                            int32_t *vox_start, int32_t *vox_val, char *err, size_t errlen);
 int nl_voxfeat_kernel_ms(nl_voxfeat *voxfeat, float *ms, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ node-level features -------- */
+/* Nodes and aggregate_stats_for_class of nellie/feature_extraction/hierarchical.py on the device.  The
+   object has its own stream and buffers.  It keeps one frame's node list and border mask (1 bit / voxel), and one set of groups:
+   lists of indices into value arrays, over which any number of value arrays are aggregated.  Every sum is numpy's pairwise sum
+   of a row padded to L, the longest group of the set.
+   nl_nodefeat_create  : ndim 2 or 3 (nz = 1 for 2), the frame's shape and spacing ((Z,) Y, X in um).  An object that only
+                         aggregates may have any shape.
+   nl_nodefeat_frame   : pixel class, component labels, branch labels and border mask, each in its own dtype (the dtype codes of
+                         nl_filter_load).  Nodes are the voxels with pixel class > 0 in raster order; their labels are gathered;
+                         their thickness is 2 * the distance in um to the nearest voxel with border != 0 (per axis node * s -
+                         border * s, squares added in axis order, sqrt of the minimum), NaN without a border voxel.
+   nl_nodefeat_fetch   : coordinates (n_nodes, D) int64, the two labels (n_nodes elements of the uploaded dtypes), thickness
+                         (n_nodes float64).  NULL pointers are skipped.
+   nl_nodefeat_groups  : group j = idx[offsets[j] .. offsets[j + 1]), in the order given, neither sorted nor disjoint; offsets has
+                         n_groups + 1 entries from 0.  At most 2^31 - 1 indices in all.  longest = L.
+   nl_nodefeat_aggregate : values (float32, float64 or integers of at most 32 bits; n_values above every index) as float64.
+                         out (5, n_groups) float64 = mean, std_dev, min, max, sum: nanmean, nanstd, nanmin, nanmax and nansum of
+                         the rows of the groups' matrix padded with NaN to L columns.  A group without a number: NaN, sum 0.
+   nl_nodefeat_node_stats : the groups are the nodes' voxel lists (n_groups = n_nodes): indices into coords (n_vox, D) int64 and
+                         vec01 / vec12 (n_vox, D) float32, NULL = all NaN.  out (6, n_nodes) float64 = z, y, x (mean voxel
+                         coordinate * spacing, z NaN in 2-D), divergence, convergence, vergere; NaN for a node without voxels.
+   nl_nodefeat_kernel_ms : ms[4], device time: node list and labels, border mask and thickness, node statistics (since the last
+                         nl_nodefeat_frame), aggregation (since the last nl_nodefeat_groups).  Transfers excluded. */
+typedef struct nl_nodefeat nl_nodefeat;
+int nl_nodefeat_create(nl_nodefeat **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, const double *spacing, char *err,
+                       size_t errlen);
+int nl_nodefeat_destroy(nl_nodefeat *nodefeat);
+int nl_nodefeat_frame(nl_nodefeat *nodefeat, const void *pixel_class, int class_dtype, const void *comp, int comp_dtype, const void *branch,
+                      int branch_dtype, const void *border, int border_dtype, int64_t *n_nodes, char *err, size_t errlen);
+int nl_nodefeat_fetch(nl_nodefeat *nodefeat, int64_t *coords, void *comp, void *branch, double *thickness, char *err, size_t errlen);
+int nl_nodefeat_groups(nl_nodefeat *nodefeat, const int64_t *offsets, const int64_t *idx, int64_t n_groups, int64_t *longest, char *err,
+                       size_t errlen);
+int nl_nodefeat_aggregate(nl_nodefeat *nodefeat, const void *values, int dtype, int64_t n_values, double *out, char *err, size_t errlen);
+int nl_nodefeat_node_stats(nl_nodefeat *nodefeat, const int64_t *coords, const float *vec01, const float *vec12, int64_t n_vox, double *out,
+                           char *err, size_t errlen);
+int nl_nodefeat_kernel_ms(nl_nodefeat *nodefeat, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit
    Hessians h6[n][6] = (hxx,hxy,hxz,hyy,hyz,hzz) writes out4[n][4] = (l1,l2,l3 sorted by |.|, Frangi

@@ -25,6 +25,7 @@ LIB = os.path.join(HERE, "libnellie_hip.so")
 # (nl_host.h holds what all of them share, nl_stage.h what the last four -- the stage handles -- share beyond that).
 SOURCES = {"nellie_hip.hip": [], "nellie_sample.hip": [], "nellie_comm.hip": [], "nellie_gauss.hip": [], "nellie_gzyx.hip": [], "nellie_label.hip": [],
            "nellie_markers.hip": [], "nellie_hip_track.hip": [], "nellie_hip_flow.hip": [], "nellie_hip_reassign.hip": [], "nellie_hip_voxfeat.hip": [],
+           "nellie_hip_nodefeat.hip": [],
            "nellie_hv.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 # every include of the translation units: a stale library after editing one of them would silently test old kernels
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".inc", ".h"))) + [os.path.join("..", "..", "include", "nellie_amd.h")]

@@ -1,4 +1,5 @@
-"""Feature extraction on the MI355X HIP engine: the voxel level of the reference's Hierarchy."""
+"""Feature extraction: the hierarchy's levels on the HIP engine (voxels, nodes)."""
+from nellie_amd.feature_extraction.nodes import NodeFeatures, Nodes, aggregate_stats_for_class
 from nellie_amd.feature_extraction.voxels import VoxelFeatures, Voxels
 
-__all__ = ["Voxels", "VoxelFeatures"]
+__all__ = ["Voxels", "VoxelFeatures", "Nodes", "NodeFeatures", "aggregate_stats_for_class"]

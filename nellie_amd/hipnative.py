@@ -164,6 +164,13 @@ _PROTOS = {
     "nl_voxfeat_nodes": [_p, _p, _int, _p, _int, C.POINTER(_i64), C.POINTER(_i64)],
     "nl_voxfeat_fetch_nodes": [_p, _p, _p, _p, _p, _p, _p, _p],
     "nl_voxfeat_kernel_ms": [_p, _p],
+    "nl_nodefeat_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p],
+    "nl_nodefeat_frame": [_p, _p, _int, _p, _int, _p, _int, _p, _int, C.POINTER(_i64)],
+    "nl_nodefeat_fetch": [_p, _p, _p, _p, _p],
+    "nl_nodefeat_groups": [_p, _p, _p, _i64, C.POINTER(_i64)],
+    "nl_nodefeat_aggregate": [_p, _p, _int, _i64, _p],
+    "nl_nodefeat_node_stats": [_p, _p, _p, _p, _i64, _p],
+    "nl_nodefeat_kernel_ms": [_p, _p],
     "nl_host_half_round": [_p, _p, _i64],
     "nl_host_half_nansum": [_p, _i64, _int, _p],
     "nl_host_np_sum_f32": [_p, _i64, _p],
@@ -183,6 +190,7 @@ _PLAIN = {
     "nl_flow_destroy": (_int, [_p]),
     "nl_reassign_destroy": (_int, [_p]),
     "nl_voxfeat_destroy": (_int, [_p]),
+    "nl_nodefeat_destroy": (_int, [_p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
 
@@ -1333,4 +1341,82 @@ class VoxelFeatures(_Handle):
 
     def kernel_ms(self) -> float:
         """device time of the kernels since the last frame(), transfers excluded"""
+        return sum(self.kernel_ms_parts().values())
+
+
+class NodeFeatures(_Handle):
+    """Device state of the node level of the hierarchy (include/nellie_amd.h nl_nodefeat_*): one frame's node list and border
+    mask, and one set of groups (CSR lists of indices) over which value arrays are aggregated with numpy's padded pairwise sums.
+    An object used for `groups` / `aggregate` alone needs no frame and may have any shape."""
+
+    PARTS = ("node_list", "thickness", "node_stats", "aggregation")
+    KEYS = ("mean", "std_dev", "min", "max", "sum")
+    STATS = ("z", "y", "x", "divergence", "convergence", "vergere")
+    # what the device converts exactly to float64; anything else is converted on the host, as numpy would
+    VALUE_DTYPES = tuple(np.dtype(t) for t in (np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.float32, np.float64))
+
+    _destroy, _noun = "nl_nodefeat_destroy", "node-feature object"
+
+    def __init__(self, shape=(1, 1), spacing=(1.0, 1.0), device=0):
+        self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("frames", spacing, shape=shape)
+        self._create("nl_nodefeat_create", int(device), self.ndim, nz, ny, nx, _ptr(sp))
+        self.n_nodes = self.n_groups = self.longest = 0
+        self._dtypes = (np.dtype(np.uint8), np.dtype(np.uint8))
+
+    def frame(self, pixel_class, comp, branch, border) -> int:
+        """uploads a frame, lists its nodes (pixel class > 0) and computes their thickness; returns the number of nodes"""
+        pc, c = _frame_array(pixel_class, self.shape, "pixel class", "object"), _frame_array(comp, self.shape, "component label", "object")
+        b, o = _frame_array(branch, self.shape, "branch label", "object"), _frame_array(border, self.shape, "border mask", "object")
+        m = _i64(0)
+        self._call("nl_nodefeat_frame", _ptr(pc), DTYPE_CODES[pc.dtype], _ptr(c), DTYPE_CODES[c.dtype], _ptr(b), DTYPE_CODES[b.dtype], _ptr(o),
+                   DTYPE_CODES[o.dtype], C.byref(m))
+        self.n_nodes, self._dtypes = int(m.value), (c.dtype, b.dtype)
+        return self.n_nodes
+
+    def fetch(self):
+        """(coordinates (n_nodes, D) int64, component labels, branch labels (the frames' dtypes), thickness float64)"""
+        m = self.n_nodes
+        coords, thick = np.empty((m, self.ndim), np.int64), np.empty(m, np.float64)
+        c, b = np.empty(m, self._dtypes[0]), np.empty(m, self._dtypes[1])
+        self._call("nl_nodefeat_fetch", _ptr(coords), _ptr(c), _ptr(b), _ptr(thick))
+        return coords, c, b, thick
+
+    def groups(self, offsets, idx) -> int:
+        """loads the groups idx[offsets[j]:offsets[j + 1]]; returns L, the longest"""
+        off, idx = np.ascontiguousarray(offsets, dtype=np.int64), np.ascontiguousarray(idx, dtype=np.int64)
+        if off.ndim != 1 or off.size < 1 or idx.ndim != 1 or int(off[-1]) != idx.size:
+            raise ValueError("offsets must be 1-D, start the first group and end at len(idx)")
+        longest = _i64(0)
+        self._call("nl_nodefeat_groups", _ptr(off), _ptr(idx), off.size - 1, C.byref(longest))
+        self.n_groups, self.longest = off.size - 1, int(longest.value)
+        return self.longest
+
+    def aggregate(self, values) -> dict:
+        """{key: (n_groups,) float64} for the keys mean, std_dev, min, max, sum of one 1-D value array over the loaded groups"""
+        v = np.asarray(values)
+        if v.ndim != 1:
+            raise ValueError("values must be 1-D")
+        v = np.ascontiguousarray(v, dtype=None if v.dtype in self.VALUE_DTYPES else np.float64)
+        out = np.empty((len(self.KEYS), self.n_groups), np.float64)
+        self._call("nl_nodefeat_aggregate", _ptr(v), DTYPE_CODES[v.dtype], v.size, _ptr(out))
+        return dict(zip(self.KEYS, out))
+
+    def node_stats(self, coords, vec01=None, vec12=None) -> dict:
+        """{name: (n_nodes,) float64} for z, y, x, divergence, convergence, vergere; the loaded groups are the nodes' voxel lists,
+        indices into coords (n_vox, D) and the two vector arrays (None: all NaN)"""
+        xyz = np.ascontiguousarray(coords, dtype=np.int64).reshape(-1, self.ndim)
+        vecs = [None if v is None else np.ascontiguousarray(v, dtype=np.float32) for v in (vec01, vec12)]
+        for v in vecs:
+            if v is not None and v.shape != xyz.shape:
+                raise ValueError(f"vectors of shape {v.shape} for coordinates of shape {xyz.shape}")
+        out = np.empty((len(self.STATS), self.n_nodes), np.float64)
+        self._call("nl_nodefeat_node_stats", _ptr(xyz), _opt(vecs[0]), _opt(vecs[1]), len(xyz), _ptr(out))
+        return dict(zip(self.STATS, out))
+
+    def kernel_ms_parts(self) -> dict:
+        ms = (_f32 * len(self.PARTS))()
+        self._call("nl_nodefeat_kernel_ms", ms)
+        return dict(zip(self.PARTS, (float(v) for v in ms)))
+
+    def kernel_ms(self) -> float:
         return sum(self.kernel_ms_parts().values())
