@@ -679,6 +679,44 @@ int nl_nodefeat_node_stats(nl_nodefeat *nodefeat, const int64_t *coords, const f
                            char *err, size_t errlen);
 int nl_nodefeat_kernel_ms(nl_nodefeat *nodefeat, float *ms, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ branch-level features -------- */
+/* Branches of nellie/feature_extraction/hierarchical.py: everything of the branch level that touches voxels.  The object has its own
+   stream and buffers.  It keeps one frame's skeleton list (the voxels with skeleton label > 0, in raster order) with what is known
+   per skeleton voxel and per skeleton label, and one frame's regions (the distinct labels > 0 of the full branch-label volume) with
+   their sums.  Per-label arrays have one row per label present, ascending, whatever the label values (at most 2^31 - 2).
+   nl_branchfeat_create  : ndim 2 or 3 (nz = 1 for 2), the frame's shape and spacing ((Z,) Y, X in um).
+   nl_branchfeat_frame   : skeleton labels (an integer dtype), component labels and border mask, each in its own dtype (the dtype
+                         codes of nl_filter_load).  Counts the skeleton voxels, their distinct labels, the tips (degree 1) and the
+                         lone tips (degree 0).
+   nl_branchfeat_fetch   : per skeleton voxel: coordinates (n, D) int64, labels (n) int64, degree (n) uint8 = the neighbours (26 or 8)
+                         inside the frame with the same label, radius (n) float64 = the distance in um to the nearest voxel with
+                         border != 0 (as nl_nodefeat_frame measures it), NaN without one; tips (n_tips) and lone (n_lone) int64:
+                         positions in the list, ascending.  Per label: branch_label (B) int64; comp (B elements of the uploaded
+                         dtype) = the component label at the label's first voxel; edges (B, 13 or 4) uint32 = same-label pairs per
+                         offset whose first non-zero component is +1, offsets in the order dz, dy, dx each over -1, 0, 1; count (B)
+                         int32 = its voxels; median (B) float64 = np.median of 2 * radius over them.  NULL pointers are skipped.
+   nl_branchfeat_regions : the branch-label volume (an integer dtype; every extent at most 2^15) and, or NULL, the reassigned labels
+                         (an integer dtype, values in [0, 2^31)).
+   nl_branchfeat_fetch_regions : labels (R) int64 ascending; sums (F, R) int64 with F = 1 + 3 D + D (D + 1) / 2: the voxel count, per
+                         axis the smallest coordinate, the largest, the sum of the coordinates, then the sums of the products
+                         c_a * c_b for a <= b in row order, all exact; mode (R) int64 = the most frequent reassigned label over the
+                         region, the smallest among equals, -1 when none were given.
+   nl_branchfeat_kernel_ms : ms[5], device time: skeleton list and labels, degree and edge counts, border mask and radii, per-label
+                         lists with medians and tips (since the last nl_branchfeat_frame), regions (since the last
+                         nl_branchfeat_regions).  Transfers excluded. */
+typedef struct nl_branchfeat nl_branchfeat;
+int nl_branchfeat_create(nl_branchfeat **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, const double *spacing, char *err,
+                         size_t errlen);
+int nl_branchfeat_destroy(nl_branchfeat *branchfeat);
+int nl_branchfeat_frame(nl_branchfeat *branchfeat, const void *skel, int skel_dtype, const void *comp, int comp_dtype, const void *border,
+                        int border_dtype, int64_t *n_voxels, int64_t *n_labels, int64_t *n_tips, int64_t *n_lone, char *err, size_t errlen);
+int nl_branchfeat_fetch(nl_branchfeat *branchfeat, int64_t *coords, int64_t *labels, uint8_t *degree, double *radius, int64_t *tips, int64_t *lone,
+                        int64_t *branch_label, void *comp, uint32_t *edges, int32_t *count, double *median, char *err, size_t errlen);
+int nl_branchfeat_regions(nl_branchfeat *branchfeat, const void *labels, int dtype, const void *reassigned, int reassigned_dtype,
+                          int64_t *n_regions, char *err, size_t errlen);
+int nl_branchfeat_fetch_regions(nl_branchfeat *branchfeat, int64_t *labels, int64_t *sums, int64_t *mode, char *err, size_t errlen);
+int nl_branchfeat_kernel_ms(nl_branchfeat *branchfeat, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit
    Hessians h6[n][6] = (hxx,hxy,hxz,hyy,hyz,hzz) writes out4[n][4] = (l1,l2,l3 sorted by |.|, Frangi

@@ -5,7 +5,7 @@
 //   nellie_comm.hip     RCCL loader, loopback transport, communicator pool, collectives         -> rccl(), comm_release, reduce_*, ag_reserve, allgather_sizes
 //   nellie_label.hip    Label / Network / streaming                                             -> nl_launch_threshold_pack
 //   nellie_markers.hip  Markers                                                                 -> nl_launch_pack_labels
-//   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the five stage handles share nl_stage.h.
+//   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the six stage handles share nl_stage.h.
 // gfx950 only.
 #pragma once
 #include <stdarg.h>

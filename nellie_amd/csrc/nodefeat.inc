@@ -114,7 +114,8 @@ __device__ __forceinline__ i64 nf_wave_sum(i64 v) {
 }
 
 // ---- node thickness --------------------------------------------------------------------------------------------------------------
-// One wave per node: 2 * the distance in um to the nearest border voxel, NaN when the frame has none (*any_border == 0).
+// nf_nearest_sq: the squared distance (um^2) from voxel v to the nearest set bit of `border`, which has one; called by all 64 lanes
+// of a one-wave workgroup, every lane returns it.  Shared with branchfeat.inc (the radii of the skeleton voxels).
 //
 // A box of half-widths floor(R / s_a) voxels holds every voxel within R: one outside it is at least floor(R / s_a) + 1 > R / s_a
 // voxels away along some axis (a quotient rounded to float64 is never below an integer the exact one reaches).  Its squared
@@ -122,16 +123,8 @@ __device__ __forceinline__ i64 nf_wave_sum(i64 v) {
 // R * R * (1 - 2^-16) for frames below 2^34 voxels per axis, R being at least one voxel.  So when the box's best squared
 // distance is at or below that, it is the frame's.  Otherwise R doubles, until the box is the frame.
 // The lanes take the (row, mask word) pairs of the box; a row's bits may start and end inside a word.
-static __global__ __launch_bounds__(64) void nf_thickness_kernel(const i64 *__restrict__ node_vox, i64 m, NfGeom g, const u64 *__restrict__ border,
-                                                                 const int *__restrict__ any_border, double *__restrict__ thickness) {
-    const i64 node = blockIdx.x;
-    if (node >= m) return;
+__device__ __forceinline__ double nf_nearest_sq(i64 v, const NfGeom &g, const u64 *__restrict__ border) {
     const int lane = threadIdx.x;
-    if (*any_border == 0) {
-        if (lane == 0) thickness[node] = __longlong_as_double(0x7ff8000000000000ll);
-        return;
-    }
-    const i64 v = node_vox[node];
     const i64 c[3] = {v / (g.nx * g.ny), (v / g.nx) % g.ny, v % g.nx};
     const i64 dim[3] = {g.nz, g.ny, g.nx};
     const double *s = g.s3;
@@ -177,6 +170,20 @@ static __global__ __launch_bounds__(64) void nf_thickness_kernel(const i64 *__re
         if (whole || best <= R * R * (1.0 - 0x1p-16)) break;
         R = R + R;
     }
+    return best;
+}
+
+// One wave per node: 2 * the distance in um to the nearest border voxel, NaN when the frame has none (*any_border == 0).
+static __global__ __launch_bounds__(64) void nf_thickness_kernel(const i64 *__restrict__ node_vox, i64 m, NfGeom g, const u64 *__restrict__ border,
+                                                                 const int *__restrict__ any_border, double *__restrict__ thickness) {
+    const i64 node = blockIdx.x;
+    if (node >= m) return;
+    const int lane = threadIdx.x;
+    if (*any_border == 0) {
+        if (lane == 0) thickness[node] = __longlong_as_double(0x7ff8000000000000ll);
+        return;
+    }
+    const double best = nf_nearest_sq(node_vox[node], g, border);
     if (lane == 0) thickness[node] = sqrt(best) * 2.0;
 }
 

@@ -1,5 +1,6 @@
-"""Feature extraction: the hierarchy's levels on the HIP engine (voxels, nodes)."""
+"""Feature extraction: the hierarchy's levels on the HIP engine (voxels, nodes, branches)."""
+from nellie_amd.feature_extraction.branches import BranchFeatures, Branches
 from nellie_amd.feature_extraction.nodes import NodeFeatures, Nodes, aggregate_stats_for_class
 from nellie_amd.feature_extraction.voxels import VoxelFeatures, Voxels
 
-__all__ = ["Voxels", "VoxelFeatures", "Nodes", "NodeFeatures", "aggregate_stats_for_class"]
+__all__ = ["Voxels", "VoxelFeatures", "Nodes", "NodeFeatures", "aggregate_stats_for_class", "Branches", "BranchFeatures"]

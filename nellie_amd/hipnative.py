@@ -171,6 +171,12 @@ _PROTOS = {
     "nl_nodefeat_aggregate": [_p, _p, _int, _i64, _p],
     "nl_nodefeat_node_stats": [_p, _p, _p, _p, _i64, _p],
     "nl_nodefeat_kernel_ms": [_p, _p],
+    "nl_branchfeat_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p],
+    "nl_branchfeat_frame": [_p, _p, _int, _p, _int, _p, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+    "nl_branchfeat_fetch": [_p] * 12,
+    "nl_branchfeat_regions": [_p, _p, _int, _p, _int, C.POINTER(_i64)],
+    "nl_branchfeat_fetch_regions": [_p, _p, _p, _p],
+    "nl_branchfeat_kernel_ms": [_p, _p],
     "nl_host_half_round": [_p, _p, _i64],
     "nl_host_half_nansum": [_p, _i64, _int, _p],
     "nl_host_np_sum_f32": [_p, _i64, _p],
@@ -191,6 +197,7 @@ _PLAIN = {
     "nl_reassign_destroy": (_int, [_p]),
     "nl_voxfeat_destroy": (_int, [_p]),
     "nl_nodefeat_destroy": (_int, [_p]),
+    "nl_branchfeat_destroy": (_int, [_p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
 
@@ -1416,6 +1423,76 @@ class NodeFeatures(_Handle):
     def kernel_ms_parts(self) -> dict:
         ms = (_f32 * len(self.PARTS))()
         self._call("nl_nodefeat_kernel_ms", ms)
+        return dict(zip(self.PARTS, (float(v) for v in ms)))
+
+    def kernel_ms(self) -> float:
+        return sum(self.kernel_ms_parts().values())
+
+
+class BranchFeatures(_Handle):
+    """Device state of the branch level of the hierarchy (include/nellie_amd.h nl_branchfeat_*): one frame's skeleton list with
+    degree, radius and tips per voxel and edge counts, voxel counts and medians per label, and one frame's regions (the labels of
+    the full branch-label volume) with their exact integer sums and the most frequent reassigned label."""
+
+    PARTS = ("skeleton", "degree", "radii", "lists", "regions")
+
+    _destroy, _noun = "nl_branchfeat_destroy", "branch-feature object"
+
+    def __init__(self, shape, spacing, device=0):
+        self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("frames", spacing, shape=shape)
+        self._create("nl_branchfeat_create", int(device), self.ndim, nz, ny, nx, _ptr(sp))
+        self.n_voxels = self.n_labels = self.n_tips = self.n_lone = self.n_regions = 0
+        self.n_offsets = 13 if self.ndim == 3 else 4
+        self._comp_dtype = np.dtype(np.uint8)
+
+    @staticmethod
+    def _labels(a, shape, what):
+        a = _frame_array(a, shape, what, "object")
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"{what} must have an integer dtype, got {a.dtype}")
+        return a
+
+    def frame(self, skel, comp, border):
+        """uploads a frame and lists its skeleton (label > 0); returns (skeleton voxels, distinct labels, tips, lone tips)"""
+        s, c = self._labels(skel, self.shape, "skeleton label"), _frame_array(comp, self.shape, "component label", "object")
+        o = _frame_array(border, self.shape, "border mask", "object")
+        counts = [_i64(0) for _ in range(4)]
+        self._call("nl_branchfeat_frame", _ptr(s), DTYPE_CODES[s.dtype], _ptr(c), DTYPE_CODES[c.dtype], _ptr(o), DTYPE_CODES[o.dtype],
+                   *[C.byref(v) for v in counts])
+        self.n_voxels, self.n_labels, self.n_tips, self.n_lone = (int(v.value) for v in counts)
+        self._comp_dtype = c.dtype
+        return self.n_voxels, self.n_labels, self.n_tips, self.n_lone
+
+    def fetch(self) -> dict:
+        """per skeleton voxel `coords` (n, D) int64, `labels` int64, `degree` uint8, `radius` float64, the positions `tips` and
+        `lone` in the list; per label `branch_label` int64, `comp`, `edges` (B, offsets) uint32, `count` int32, `median` float64"""
+        n, B = self.n_voxels, self.n_labels
+        out = dict(coords=np.empty((n, self.ndim), np.int64), labels=np.empty(n, np.int64), degree=np.empty(n, np.uint8), radius=np.empty(n, np.float64),
+                   tips=np.empty(self.n_tips, np.int64), lone=np.empty(self.n_lone, np.int64), branch_label=np.empty(B, np.int64),
+                   comp=np.empty(B, self._comp_dtype), edges=np.empty((B, self.n_offsets), np.uint32), count=np.empty(B, np.int32),
+                   median=np.empty(B, np.float64))
+        self._call("nl_branchfeat_fetch", *[_ptr(a) for a in out.values()])
+        return out
+
+    def regions(self, labels, reassigned=None) -> int:
+        """the regions of a branch-label volume, with the most frequent reassigned label of each when `reassigned` is given"""
+        a = self._labels(labels, self.shape, "branch label")
+        r = None if reassigned is None else self._labels(reassigned, self.shape, "reassigned label")
+        count = _i64(0)
+        self._call("nl_branchfeat_regions", _ptr(a), DTYPE_CODES[a.dtype], _opt(r), DTYPE_CODES[r.dtype] if r is not None else 0, C.byref(count))
+        self.n_regions = int(count.value)
+        return self.n_regions
+
+    def fetch_regions(self):
+        """(labels (R) int64, sums (F, R) int64: n, min per axis, max per axis, S_a, Q_ab for a <= b; mode (R) int64, -1 without)"""
+        R, D = self.n_regions, self.ndim
+        labels, sums, mode = np.empty(R, np.int64), np.empty((1 + 3 * D + D * (D + 1) // 2, R), np.int64), np.empty(R, np.int64)
+        self._call("nl_branchfeat_fetch_regions", _ptr(labels), _ptr(sums), _ptr(mode))
+        return labels, sums, mode
+
+    def kernel_ms_parts(self) -> dict:
+        ms = (_f32 * len(self.PARTS))()
+        self._call("nl_branchfeat_kernel_ms", ms)
         return dict(zip(self.PARTS, (float(v) for v in ms)))
 
     def kernel_ms(self) -> float:
