@@ -379,6 +379,11 @@ int nl_label_intensity_mask(nl_ctx *ctx, const void *host_original, int dtype, d
    the planes it owns: Label's intensity thresholds on a sharded frame). */
 int nl_label_intensity_mask_planes(nl_ctx *ctx, const void *host_original, int dtype, double thresh, int64_t z0, int64_t z1,
                                    char *err, size_t errlen);
+/* The same against an integer threshold, for NL_U64 and NL_I64 images only: `thresh` is of the image's own type (for NL_U64 its
+   bits) and the comparison is done on integers, as numpy compares a 64-bit integer array with an integer; in float64 the
+   elements beyond 2^53 would round. */
+int nl_label_intensity_mask_int(nl_ctx *ctx, const void *host_original, int dtype, int64_t thresh, int64_t z0, int64_t z1,
+                                char *err, size_t errlen);
 
 /* flat[offset::step] of a field (labelling.py:393, 412). */
 int nl_flat_sample_gather(nl_ctx *ctx, int field, int64_t offset, int64_t step,

@@ -18,3 +18,14 @@ __global__ void intensity_mask_kernel(const T *__restrict__ orig, float *__restr
         if (!((double)orig[i] > thresh)) frangi[i] = frangi[i] * 0.0f;
     }
 }
+
+// The same against an integer threshold of the image's own 64-bit type, compared as integers: beyond 2^53 the conversion to
+// float64 above rounds, and numpy compares a 64-bit integer array with an integer exactly.
+template <typename T>
+__global__ void intensity_mask_int_kernel(const T *__restrict__ orig, float *__restrict__ frangi, T thresh, i64 n) {
+    i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        if (!(orig[i] > thresh)) frangi[i] = frangi[i] * 0.0f;
+    }
+}

@@ -19,9 +19,11 @@ extern "C" int nl_label_load_frangi(nl_ctx *c, const float *host, int64_t z0, in
 }
 
 // planes [z0, z1) of the context's frame against `host_original` = those planes of the original image (a Z slab masks the planes it owns)
-extern "C" int nl_label_intensity_mask_planes(nl_ctx *c, const void *host_original, int dtype, double thresh, int64_t z0, int64_t z1,
-                                              char *err, size_t errlen) {
+// ithresh: the threshold as an integer of the image's own 64-bit type (its bits, for NL_U64), compared as integers; nullptr: `thresh`
+static int intensity_mask_planes(nl_ctx *c, const void *host_original, int dtype, double thresh, const int64_t *ithresh, int64_t z0, int64_t z1,
+                                 char *err, size_t errlen) {
     NL_ENTER(c);
+    if (ithresh && dtype != NL_U64 && dtype != NL_I64) return nl_fail(err, errlen, NL_EINVAL, "an integer threshold needs a 64-bit integer image (dtype code %d)", dtype);
     if (z0 < 0 || z1 > c->nzl || z0 >= z1) return nl_fail(err, errlen, NL_EINVAL, "bad plane range [%lld,%lld)", (i64)z0, (i64)z1);
     const i64 count = (z1 - z0) * c->ny * c->nx;
     const size_t es = dtype_size(dtype);
@@ -32,7 +34,9 @@ extern "C" int nl_label_intensity_mask_planes(nl_ctx *c, const void *host_origin
     if (e != hipSuccess) { hipFree(raw); return nl_fail(err, errlen, NL_EHIP, "upload of the original image failed: %s", hipGetErrorString(e)); }
     float *fr = c->f[c->i_vmax] + z0 * c->ny * c->nx;
     const unsigned int g = grid1d(count);
-    switch (dtype) {
+    if (ithresh && dtype == NL_U64) intensity_mask_int_kernel<uint64_t><<<g, 256, 0, c->stream>>>((const uint64_t *)raw, fr, (uint64_t)*ithresh, count);
+    else if (ithresh) intensity_mask_int_kernel<int64_t><<<g, 256, 0, c->stream>>>((const int64_t *)raw, fr, *ithresh, count);
+    else switch (dtype) {
         case NL_U8: intensity_mask_kernel<uint8_t><<<g, 256, 0, c->stream>>>((const uint8_t *)raw, fr, thresh, count); break;
         case NL_I8: intensity_mask_kernel<int8_t><<<g, 256, 0, c->stream>>>((const int8_t *)raw, fr, thresh, count); break;
         case NL_U16: intensity_mask_kernel<uint16_t><<<g, 256, 0, c->stream>>>((const uint16_t *)raw, fr, thresh, count); break;
@@ -50,9 +54,17 @@ extern "C" int nl_label_intensity_mask_planes(nl_ctx *c, const void *host_origin
     if (e != hipSuccess) return nl_fail(err, errlen, NL_EHIP, "intensity mask kernel: %s", hipGetErrorString(e));
     return NL_OK;
 }
+extern "C" int nl_label_intensity_mask_planes(nl_ctx *c, const void *host_original, int dtype, double thresh, int64_t z0, int64_t z1,
+                                              char *err, size_t errlen) {
+    return intensity_mask_planes(c, host_original, dtype, thresh, nullptr, z0, z1, err, errlen);
+}
 extern "C" int nl_label_intensity_mask(nl_ctx *c, const void *host_original, int dtype, double thresh, char *err, size_t errlen) {
     if (!c) return nl_fail(err, errlen, NL_EINVAL, "ctx is NULL");
-    return nl_label_intensity_mask_planes(c, host_original, dtype, thresh, 0, c->nzl, err, errlen);
+    return intensity_mask_planes(c, host_original, dtype, thresh, nullptr, 0, c->nzl, err, errlen);
+}
+extern "C" int nl_label_intensity_mask_int(nl_ctx *c, const void *host_original, int dtype, int64_t thresh, int64_t z0, int64_t z1,
+                                           char *err, size_t errlen) {
+    return intensity_mask_planes(c, host_original, dtype, 0.0, &thresh, z0, z1, err, errlen);
 }
 
 template <int FG, int CONN>

@@ -104,6 +104,7 @@ _PROTOS = {
     "nl_label_load_frangi": [_p, _p, _i64, _i64],
     "nl_label_intensity_mask": [_p, _p, _int, _f64],
     "nl_label_intensity_mask_planes": [_p, _p, _int, _f64, _i64, _i64],
+    "nl_label_intensity_mask_int": [_p, _p, _int, _i64, _i64, _i64],
     "nl_flat_sample_gather": [_p, _int, _i64, _i64, _p, _i64, C.POINTER(_i64)],
     "nl_flat_sample_gather_positive": [_p, _int, _i64, _i64, _p, _i64, C.POINTER(_i64)],
     "nl_label_run": [_p, _int, _f32, _i64, _int, C.POINTER(_i64)],
@@ -507,7 +508,28 @@ def _frame_array(a, shape, what, owner, dtype=None, dtype_error=TypeError):
         raise ValueError(f"{what} shape {a.shape} does not match the {owner}'s {shape}")
     if dtype is None and a.dtype not in DTYPE_CODES:
         raise dtype_error(f"unsupported {what} dtype {a.dtype}")
+    if dtype is not None and a.dtype != dtype and np.dtype(dtype).kind in "iu":
+        _refuse_lossy_cast(a, np.dtype(dtype), what)
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _refuse_lossy_cast(a, dtype, what):
+    """ValueError where a.astype(dtype), an integer dtype, would change a value: a label that wrapped or lost its fraction would
+    be another object's label, or none.  Checked before the cast, against the extremes and in exact arithmetic."""
+    if a.size == 0 or a.dtype.kind == "b":
+        return
+    if a.dtype.kind not in "iuf":
+        raise TypeError(f"{what} of dtype {a.dtype} cannot be converted to {dtype}")
+    if a.dtype.kind == "f":
+        bad = ~np.isfinite(a)
+        if not bad.any():
+            bad = a != np.trunc(a)
+        if bad.any():
+            raise ValueError(f"{what} holds {a[bad].flat[0].item()!r}, which {dtype} cannot hold: refusing a cast that changes values")
+    info = np.iinfo(dtype)
+    for v in (a.min(), a.max()):
+        if not info.min <= int(v) <= info.max:
+            raise ValueError(f"{what} holds {int(v)}, outside {dtype}'s range [{info.min}, {info.max}]: refusing a cast that changes values")
 
 
 def _kernel_ms(handle, name) -> float:
@@ -953,11 +975,20 @@ class Context(_Handle):
         assert a.shape == (z1 - z0, self.shape[1], self.shape[2])
         self._call("nl_label_load_frangi", _ptr(a), z0, z1)
 
-    def label_intensity_mask(self, original: np.ndarray, thresh: float, z0=None, z1=None):
-        """frangi *= (original > thresh); z0, z1: only those planes, `original` holding exactly them."""
+    def label_intensity_mask(self, original: np.ndarray, thresh, z0=None, z1=None):
+        """frangi *= (original > thresh); z0, z1: only those planes, `original` holding exactly them.  A float `thresh` is
+        compared in float64; an int one (Label._effective_threshold: a 64-bit integer image) as integers of the image's type."""
         a = np.ascontiguousarray(original)
         if a.dtype not in DTYPE_CODES:
             a = a.astype(np.float64)
+        if isinstance(thresh, int) and not isinstance(thresh, bool):
+            if a.dtype not in (np.uint64, np.int64) or not np.iinfo(a.dtype).min <= thresh <= np.iinfo(a.dtype).max:
+                raise ValueError(f"an integer threshold must be of the image's own 64-bit integer type, got {thresh} for {a.dtype}")
+            z0 = 0 if z0 is None else int(z0)
+            z1 = self.shape[0] if z1 is None else int(z1)
+            assert a.shape == (z1 - z0,) + tuple(self.shape[1:])
+            self._call("nl_label_intensity_mask_int", _ptr(a), DTYPE_CODES[a.dtype], thresh - (1 << 64) if thresh >= 1 << 63 else thresh, z0, z1)
+            return
         if z0 is None and z1 is None:
             assert a.shape == self.shape
             self._call("nl_label_intensity_mask", _ptr(a), DTYPE_CODES[a.dtype], float(thresh))

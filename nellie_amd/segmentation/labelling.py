@@ -187,9 +187,19 @@ class Label(FrameCounted):
         return a[None, ...] if a.ndim == 2 else a
 
     @staticmethod
-    def _effective_threshold(original: np.ndarray, thresh) -> float:
+    def _effective_threshold(original: np.ndarray, thresh):
         """The value `original > thresh` really compares against under numpy's promotion rules:
-        python scalars are weak (cast to the array's float dtype); numpy scalars promote with the array."""
+        python scalars are weak (cast to the array's float dtype); numpy scalars promote with the array.
+        An integer threshold on a 64-bit integer image comes back as an int of the image's type, for the integer comparison
+        numpy makes there (float64 rounds the elements beyond 2**53); every other one as the float64 to compare against."""
+        is_int = isinstance(thresh, (int, np.integer)) and not isinstance(thresh, (bool, np.bool_))
+        if is_int and original.dtype.kind in "iu":
+            info, t = np.iinfo(original.dtype), int(thresh)
+            if t < info.min:
+                return -np.inf
+            if t >= info.max:
+                return np.inf
+            return t if original.dtype.itemsize == 8 else float(t)      # narrower elements and their bounds are exact in float64
         if isinstance(thresh, (np.generic, np.ndarray)):
             common = np.result_type(original.dtype, np.asarray(thresh).dtype)
             return float(np.asarray(thresh).astype(common))

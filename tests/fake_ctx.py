@@ -187,7 +187,8 @@ class OracleCtx:
     def label_intensity_mask(self, original, thresh, z0=None, z1=None):
         z0 = 0 if z0 is None else z0
         z1 = self.shape[0] if z1 is None else z1
-        keep = np.asarray(original).astype(np.float64) > float(thresh)
+        # an int threshold: a 64-bit integer image, compared as integers (nl_label_intensity_mask_int)
+        keep = np.asarray(original) > thresh if isinstance(thresh, int) else np.asarray(original).astype(np.float64) > float(thresh)
         self.frangi[z0:z1] = np.where(keep, self.frangi[z0:z1], np.float32(0))
 
     def slab_label_pack(self, thr):
