@@ -650,8 +650,9 @@ int nl_voxfeat_kernel_ms(nl_voxfeat *voxfeat, float *ms, char *err, size_t errle
 /* ------------------------------------------------------------------ node-level features -------- */
 /* Nodes and aggregate_stats_for_class of nellie/feature_extraction/hierarchical.py on the device.  The
    object has its own stream and buffers.  It keeps one frame's node list and border mask (1 bit / voxel), and one set of groups:
-   lists of indices into value arrays, over which any number of value arrays are aggregated.  Every sum is numpy's pairwise sum
-   of a row padded to L, the longest group of the set.
+   lists of indices into value arrays, over which any number of value arrays are aggregated.  Every sum is numpy's sum of a row
+   padded to L, the longest group of the set: the row in blocks of 8192 elements (numpy's ufunc buffer) added in order from 0.0,
+   each block summed pairwise.
    nl_nodefeat_create  : ndim 2 or 3 (nz = 1 for 2), the frame's shape and spacing ((Z,) Y, X in um).  An object that only
                          aggregates may have any shape.
    nl_nodefeat_frame   : pixel class, component labels, branch labels and border mask, each in its own dtype (the dtype codes of

@@ -3,8 +3,9 @@
 //
 // Nodes are the voxels with pixel class > 0, compacted in raster order by the mask, scan and rank of rank_scan.inc.  The border
 // is one bit per voxel; a wave searches a growing box of it around its node for the nearest set bit.  Groups of values (a node's
-// voxels; later a branch's nodes) are CSR lists of indices; one wave reduces one group.  Every sum is numpy's pairwise sum over
-// L elements, the group's k values followed by L - k zeros: the tree's shape comes from L, the work from k (nf_tree_sum).
+// voxels; later a branch's nodes) are CSR lists of indices; one wave reduces one group.  Every sum is numpy's sum of a row of L
+// elements, the group's k values followed by L - k zeros: blocks of 8192 elements added in order, each summed as a pairwise tree
+// whose shape comes from the block's length, the work from k (nf_tree_sum).
 //
 // All arithmetic is float64 in numpy's operation order; compiled with -ffp-contract=off.  Nothing here depends on the order in
 // which waves or lanes finish: two runs give the same bits.
@@ -19,6 +20,7 @@ struct NfGeom {
 
 #define NF_STACK 72                   // entries of a tree walk's stack: two per level, and a tree over 2^31 elements has 26 levels
 #define NF_LEAF 128                   // numpy's PW_BLOCKSIZE: at most that many elements are summed without splitting
+#define NF_BLOCK 8192                 // numpy's ufunc buffer in elements (np.getbufsize()): a row is reduced in such pieces, as TRK_PW_BLOCK
 
 // ---- element access ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double nf_value(const void *__restrict__ p, int dtype, i64 i) {
@@ -187,23 +189,22 @@ static __global__ __launch_bounds__(64) void nf_thickness_kernel(const i64 *__re
     if (lane == 0) thickness[node] = sqrt(best) * 2.0;
 }
 
-// ---- numpy's pairwise sum over padded rows ---------------------------------------------------------------------------------------
-// 0.0 + numpy's pairwise sum of L elements, the first k of which are elem(0 .. k) and the rest +0.0 (k <= L): what np.sum gives
-// for a row of a matrix padded to L columns, and with L = k for a vector.  Called by all 64 lanes of a one-wave workgroup with the
-// same k, L and scratch; every lane returns the sum.  scratch: k / 64 + 2 doubles of the wave's own.
+// ---- numpy's sum over padded rows ------------------------------------------------------------------------------------------------
+// nf_block_tree: numpy's pairwise sum of one block of a row: n elements, the first k of which are elem(base .. base + k) and the
+// rest +0.0 (0 < k <= n <= NF_BLOCK).  Called by all 64 lanes of a one-wave workgroup with the same arguments; every lane returns
+// the sum.  scratch: at most 129 doubles of the wave's own, k / 64 + 2 suffice.
 //
 // The tree splits n > 128 elements at n / 2 rounded down to a multiple of 8 and sums n <= 128 as a leaf: eight accumulators over
 // the largest multiple of 8, combined pairwise, then the remainder in order (below 8 elements: one running sum).  A subtree or a
-// tail made of padding only adds +0.0, which changes nothing but the sign of a zero, and the leading 0.0 + settles that sign
-// whatever the tree gave; so padding is skipped and the work is O(k + log L).  Eight lanes share a leaf, one accumulator each;
-// the leaf sums go through `scratch` and are combined by a second walk of the tree.
-template <typename F> __device__ double nf_tree_sum(F elem, int k, int L, double *__restrict__ scratch) {
-    if (k <= 0) return 0.0;
+// tail made of padding only adds +0.0, which changes nothing but the sign of a zero, and the 0.0 that nf_tree_sum starts from
+// settles that sign whatever the tree gave; so padding is skipped and the work is O(k + log n).  Eight lanes share a leaf, one
+// accumulator each; the leaf sums go through `scratch` and are combined by a second walk of the tree.
+template <typename F> __device__ double nf_block_tree(F elem, int base, int k, int n_block, double *__restrict__ scratch) {
     const int team = threadIdx.x >> 3, j = threadIdx.x & 7;
     int slo[NF_STACK], sn[NF_STACK];
     int top = 1, leaf = 0;
     slo[0] = 0;
-    sn[0] = L;
+    sn[0] = n_block;
     for (;;) {
         int mylo = 0, myn = 0, mine = -1, got = 0;                     // the next eight leaves, one per team
         while (top > 0 && got < 8) {
@@ -223,17 +224,18 @@ template <typename F> __device__ double nf_tree_sum(F elem, int k, int L, double
         }
         if (got == 0) break;
         const int kk = mine < 0 ? 0 : (k - mylo < myn ? k - mylo : myn);      // the leaf's elements that are not padding
+        const int at = base + mylo;
         double r = 0.0;
-        if (L < 8) {                                                   // one leaf, a running sum
-            for (int i = 0; i < kk; ++i) r = r + elem(mylo + i);
+        if (n_block < 8) {                                             // one leaf, a running sum
+            for (int i = 0; i < kk; ++i) r = r + elem(at + i);
         } else {
             const int m8 = myn - myn % 8, stop = kk < m8 ? kk : m8;
-            if (j < stop) r = elem(mylo + j);
-            for (int i = j + 8; i < stop; i += 8) r = r + elem(mylo + i);
+            if (j < stop) r = elem(at + j);
+            for (int i = j + 8; i < stop; i += 8) r = r + elem(at + i);
             r = r + __shfl_xor(r, 1);
             r = r + __shfl_xor(r, 2);
             r = r + __shfl_xor(r, 4);
-            for (int i = m8; i < kk; ++i) r = r + elem(mylo + i);
+            for (int i = m8; i < kk; ++i) r = r + elem(at + i);
         }
         if (mine >= 0 && j == 0) scratch[mine] = r;
     }
@@ -244,7 +246,7 @@ template <typename F> __device__ double nf_tree_sum(F elem, int k, int L, double
     top = 1;
     leaf = 0;
     slo[0] = 0;
-    sn[0] = L;
+    sn[0] = n_block;
     while (top > 0) {
         --top;
         const int lo = slo[top], n = sn[top];
@@ -265,8 +267,24 @@ template <typename F> __device__ double nf_tree_sum(F elem, int k, int L, double
         }
         slo[top] = lo; sn[top] = n2; ++top;
     }
-    const double sum = 0.0 + val[0];
+    const double sum = val[0];
     __syncthreads();                                                   // the scratch may be written again
+    return sum;
+}
+
+// What np.sum gives for a row of a matrix padded to L columns, the first k of which are elem(0 .. k) and the rest +0.0 (k <= L),
+// and with L = k for a vector.  numpy runs a reduction's inner loop in pieces of its ufunc buffer, NF_BLOCK elements, restarting
+// at every row: the sum is 0.0, then for every block b of the row `sum + pairwise tree of the block`, the block's length being
+// min(NF_BLOCK, L - NF_BLOCK * b).  A block of padding adds +0.0 to a sum that began as 0.0 + ..., never -0.0, and changes nothing:
+// only the blocks that start below k are visited.  For L <= NF_BLOCK this is 0.0 + one tree over L.  Called by all 64 lanes of a
+// one-wave workgroup with the same k, L and scratch; every lane returns the sum.  scratch: k / 64 + 2 doubles of the wave's own
+// (one block at a time: a leaf of a split tree has at least 64 elements, so at most 129 leaves hold values).
+template <typename F> __device__ double nf_tree_sum(F elem, int k, int L, double *__restrict__ scratch) {
+    double sum = 0.0;
+    for (i64 b = 0; b < k; b += NF_BLOCK) {                            // i64: the step past a k near 2^31 must not wrap
+        const int base = (int)b, n_block = L - base < NF_BLOCK ? L - base : NF_BLOCK;
+        sum = sum + nf_block_tree(elem, base, k - base < n_block ? k - base : n_block, n_block, scratch);
+    }
     return sum;
 }
 

@@ -6,8 +6,9 @@ convergence and vergere of every node from the voxels assigned to it, and aggreg
 voxels.  Same constructor argument, same `.run()`, same attributes (lists with one entry per frame).
 
 `aggregate_stats_for_class` is the reference's function of that name (hierarchical.py:1165-1272) on the device: mean, std_dev,
-min, max and sum of every 1-D statistic of a class over groups of indices.  Its sums are numpy's pairwise sums over rows padded
-to the longest group of the call, which is what the reference's default path computes; the padded matrix itself is never built.
+min, max and sum of every 1-D statistic of a class over groups of indices.  Its sums are numpy's sums over rows padded to the
+longest group of the call (pairwise within numpy's buffer blocks of 8192 elements, the blocks added in order), which is what the
+reference's default path computes; the padded matrix itself is never built.
 
 `NodeFeatures(im_info).run()` opens the files the reference's Hierarchy opens, runs `Voxels` then `Nodes` and writes the voxel
 and the node table (`features_voxels`, `features_nodes`) as the reference's Hierarchy does.

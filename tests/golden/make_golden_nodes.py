@@ -16,6 +16,11 @@ nodes_synthetic.npz: calls of aggregate_stats_for_class alone with the groups ha
 uint16 and float64 statistics and a 2-D one (skipped); 10 % of the float values are NaN, one group is empty, one all NaN, one made
 of -0.0 only, one as long as L.
 
+nodes_synthetic_wide.npz: the same kind of call for every L of WIDE_L, at and past numpy's reduction buffer of 8192 elements
+(`python tests/golden/make_golden_nodes.py /path/to/nellie-reference synthetic_wide` writes it alone): the same special groups,
+groups of every k of WIDE_K that fits, and groups of L - 1 and L // 2 + 3; the groups are strided ranges over 1500 values, which
+are unsorted and repeat, and keep the file small.
+
 The capture checks tests/node_features_restatement.py against everything it stores, bit for bit, and asserts that the set covers
 the three regimes of the summation tree (L < 8, 8 <= L <= 128, L > 128) and that in the anisotropic 3-D fixture some node's
 nearest border voxel in um is not its nearest in voxels.
@@ -43,6 +48,8 @@ BORDERS = {
 }
 SYNTHETIC_L = (1, 7, 8, 9, 127, 128, 129, 136, 255, 256, 257, 1000)
 SYNTHETIC_STATS = ("f32", "u16", "f64", "vec2d")
+WIDE_L = (8192, 8193, 16_385, 20_011)
+WIDE_K = (1, 7, 129, 8191, 8192, 8193)
 
 
 def make_border(rng, comp, modes):
@@ -160,6 +167,43 @@ def capture_synthetic(aggregate, seed=3):
     return out
 
 
+def capture_wide(aggregate, seed=5):
+    rng = np.random.default_rng(seed)
+    out = dict(stats=np.asarray(SYNTHETIC_STATS), n_calls=np.int64(len(WIDE_L)))
+    n = 1500
+    for c, L in enumerate(WIDE_L):
+        f64 = rng.standard_normal(n) * 10.0 ** rng.integers(-3, 3, n)
+        hole = rng.random(n) < 0.1
+        hole[:4] = True                                            # the all-NaN group reads these
+        hole[4:8] = False
+        f64[hole] = np.nan
+        f64[4:8] = -0.0                                            # the -0.0 group these
+        f32 = f64.astype(np.float32)
+        u16 = rng.integers(0, 65536, n).astype(np.uint16)
+        u16[4:8] = 0
+        child = SimpleNamespace(stats_to_aggregate=list(SYNTHETIC_STATS), f32=[f32], u16=[u16], f64=[f64], vec2d=[rng.random((n, 2)).astype(np.float32)])
+        lens = [L, 0, 5, 9, L] + [k for k in WIDE_K if k <= L] + [L - 1, L // 2 + 3]
+        groups = [(3 + 5 * j + (7 + 6 * j) * np.arange(k)) % n for j, k in enumerate(lens)]       # strided: unsorted, with repeats, overlapping
+        groups[2] = np.arange(lens[2]) % 4
+        groups[3] = 4 + np.arange(lens[3]) % 4
+        groups[4] = groups[4][::-1]
+        groups = [np.array([]) if len(a) == 0 else a.astype(np.int64) for a in groups]
+        with np.errstate(all="ignore"):
+            want = aggregate(child, 0, groups)
+        own = nr.aggregate_stats_for_class(child, 0, groups)
+        same_aggregates(own, want, ("wide", L))
+        assert max(len(a) for a in groups) == L and want["f64"]["sum"].shape == (1, len(groups))
+        assert np.isnan(want["f64"]["mean"][0, 2]) and want["f64"]["sum"][0, 2] == 0.0 and np.isnan(want["f64"]["max"][0, 1])
+        assert np.signbit(want["f64"]["min"][0, 3]) and not np.signbit(want["f64"]["sum"][0, 3])
+        off, idx = nr.as_csr(groups)
+        out.update({f"c{c}_L": np.int64(L), f"c{c}_off": off, f"c{c}_idx": idx})
+        for s in SYNTHETIC_STATS:
+            out[f"c{c}_{s}"] = getattr(child, s)[0]
+            for key in ng.KEYS:
+                out[f"c{c}_{s}_{key}"] = want[s][key]
+    return out
+
+
 def main():
     make_golden.REF = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else make_golden.REF
     make_golden._import_reference()
@@ -178,6 +222,11 @@ def main():
         assert len(out["longest"]) == (0 if vg.load(vname)["skip_nodes"] else vg.load(vname)["T"])
         seen += longest
         print(f"nodes_{name}: nodes {np.diff(out['node_off']).tolist() if 'node_off' in out else []}, L {longest}, {os.path.getsize(path)} B")
+    if not only or "synthetic_wide" in only:
+        path = os.path.join(ng.GOLDEN_DIR, ng.WIDE + ".npz")
+        np.savez_compressed(path, **capture_wide(aggregate_stats_for_class))
+        assert os.path.getsize(path) < 400_000, os.path.getsize(path)
+        print(f"{ng.WIDE}: L {list(WIDE_L)}, {os.path.getsize(path)} B")
     if not only:
         path = os.path.join(ng.GOLDEN_DIR, ng.SYNTHETIC + ".npz")
         np.savez_compressed(path, **capture_synthetic(aggregate_stats_for_class))

@@ -3,12 +3,14 @@ test infrastructure only -- never imported by the package.  It is checked bit fo
 goldens (tests/golden/make_golden_nodes.py) and against the goldens without a GPU (tests/test_nodes_cpu.py); the GPU tests compare
 the HIP engine with it where no golden exists.
 
-Every sum is written out as numpy's pairwise tree, with element-wise additions only and no call to a numpy reduction of floats
-(`PaddedSum`): for the rows of a matrix padded to L columns it walks the whole tree over L, padding included, so it shares nothing
-with the device routine, which skips the padding.  The thickness is the minimum over every border voxel, no search structure."""
+Every sum is written out as numpy's reduction, with element-wise additions only and no call to a numpy reduction of floats
+(`PaddedSum`): for the rows of a matrix padded to L columns it takes the row in numpy's buffer blocks of 8192 columns and walks
+each block's whole pairwise tree, padding included, so it shares nothing with the device routine, which skips the padding.  The
+thickness is the minimum over every border voxel, no search structure."""
 import numpy as np
 
 LEAF = 128                            # numpy's PW_BLOCKSIZE
+BUFFER = 8192                         # numpy's ufunc buffer in elements (np.getbufsize()): a reduction's inner loop runs in such pieces
 KEYS = ("mean", "std_dev", "min", "max", "sum")
 NODE_STATS = ("z", "y", "x", "divergence", "convergence", "vergere")
 
@@ -59,8 +61,12 @@ def leaf_sum(M):
 
 class PaddedSum:
     """np.sum(axis=1) of the matrix whose row j holds group j's values followed by +0.0 up to column L (default: the longest
-    group): the identity 0.0 + the pairwise tree over L elements.  Built once per set of groups, called per value array with one
-    value per (group, position) pair in CSR order."""
+    group).  numpy runs the inner loop of a reduction in pieces of its ufunc buffer, BUFFER elements, which restart at every row:
+    the sum is the identity 0.0, then for each block b of BUFFER columns `+ the pairwise tree of that block`, the block's length
+    being min(BUFFER, L - BUFFER * b).  For L <= BUFFER that is 0.0 + one tree over L.  A block that is padding in some row adds
+    +0.0 to a sum that began as 0.0 + ..., which is never -0.0, and so changes nothing there: only the blocks that start below k
+    matter to a row of k values.  Built once per set of groups, called per value array with one value per (group, position)
+    pair in CSR order."""
 
     def __init__(self, offsets, L=None):
         self.off = np.asarray(offsets, np.int64)
@@ -70,7 +76,8 @@ class PaddedSum:
         assert self.L >= int(self.k.max(initial=0))
         self.gid = np.repeat(np.arange(self.G), self.k)
         self.pos = np.arange(int(self.off[-1])) - np.repeat(self.off[:-1], self.k)
-        self.leaves = leaves(self.L)
+        self.blocks = [(base, min(BUFFER, self.L - base)) for base in range(0, self.L, BUFFER)]
+        self.leaves = [(base + lo, n) for base, length in self.blocks for lo, n in leaves(length)]
         los = np.array([lo for lo, _ in self.leaves], np.int64)
         leaf_of = np.searchsorted(los, self.pos, side="right") - 1
         self.order = np.argsort(leaf_of, kind="stable")
@@ -91,14 +98,15 @@ class PaddedSum:
             sums[lo] = full
 
         def tree(lo, n):
-            if lo >= self.L or (n <= LEAF and lo not in sums):
-                return np.zeros(self.G)
             if n <= LEAF:
-                return sums[lo]
+                return sums[lo] if lo in sums else np.zeros(self.G)
             n2 = n // 2
             n2 -= n2 % 8
             return tree(lo, n2) + tree(lo + n2, n - n2)
-        return 0.0 + tree(0, self.L)
+        total = np.zeros(self.G)
+        for base, length in self.blocks:
+            total = total + tree(base, length)
+        return total
 
 
 def aggregate_values(values, offsets, idx, plan=None):

@@ -2,7 +2,8 @@
 the hierarchy double that Nodes(hierarchy) reads; test infrastructure only.  A fixture `nodes_<case>.npz` sits on the voxel golden
 `voxels_<case>.npz` (tests/voxel_goldens.py), whose reference attributes are the double's `voxels`; it adds the border stack and
 the outputs of the reference's Nodes, concatenated over the frames with the offsets `node_off`: `agg` is (55, nodes), the rows in
-the order of the voxel statistics times KEYS.  `nodes_synthetic.npz` holds calls of the reference's aggregate_stats_for_class alone."""
+the order of the voxel statistics times KEYS.  `nodes_synthetic.npz` and `nodes_synthetic_wide.npz` (L from 8192 on) hold calls of
+the reference's aggregate_stats_for_class alone."""
 import glob
 import os
 from types import SimpleNamespace
@@ -16,11 +17,12 @@ GOLDEN_DIR = os.path.join(HERE, "golden", "nodes")
 KEYS = ("mean", "std_dev", "min", "max", "sum")
 PER_NODE = ("time", "nodes", "component_label", "branch_label", "node_thickness", "z", "y", "x", "divergence", "convergence", "vergere")
 SYNTHETIC = "nodes_synthetic"
+WIDE = "nodes_synthetic_wide"
 
 
 def names():
     found = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "nodes_*.npz")))
-    return [n for n in found if n != SYNTHETIC]
+    return [n for n in found if n not in (SYNTHETIC, WIDE)]
 
 
 def voxels_double(g, fill_empty_vectors=False):
@@ -82,19 +84,28 @@ def load(name):
     return out
 
 
-def synthetic_calls():
-    """[dict(L, offsets, idx, child (stats_to_aggregate and one array per statistic in a list), want {stat: {key: array}})]"""
-    if SYNTHETIC in _CACHE:
-        return _CACHE[SYNTHETIC]
-    z = np.load(os.path.join(GOLDEN_DIR, SYNTHETIC + ".npz"))
+def _calls(name):
+    if name in _CACHE:
+        return _CACHE[name]
+    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
     stats = [str(s) for s in z["stats"]]
     calls = []
     for c in range(int(z["n_calls"])):
         child = SimpleNamespace(stats_to_aggregate=list(stats), **{s: [z[f"c{c}_{s}"]] for s in stats})
         want = {s: {key: z[f"c{c}_{s}_{key}"] for key in KEYS} for s in stats}
         calls.append(dict(L=int(z[f"c{c}_L"]), offsets=z[f"c{c}_off"], idx=z[f"c{c}_idx"], child=child, want=want))
-    _CACHE[SYNTHETIC] = calls
+    _CACHE[name] = calls
     return calls
+
+
+def synthetic_calls():
+    """[dict(L, offsets, idx, child (stats_to_aggregate and one array per statistic in a list), want {stat: {key: array}})]"""
+    return _calls(SYNTHETIC)
+
+
+def wide_calls():
+    """the same for the calls whose L reaches numpy's buffer of 8192 elements and passes it"""
+    return _calls(WIDE)
 
 
 def groups_of(call):
