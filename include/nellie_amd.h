@@ -703,6 +703,9 @@ int nl_nodefeat_kernel_ms(nl_nodefeat *nodefeat, float *ms, char *err, size_t er
                          int32 = its voxels; median (B) float64 = np.median of 2 * radius over them.  NULL pointers are skipped.
    nl_branchfeat_regions : the branch-label volume (an integer dtype; every extent at most 2^15) and, or NULL, the reassigned labels
                          (an integer dtype, values in [0, 2^31)).
+   nl_branchfeat_regions_rows : nl_branchfeat_regions with the sums taken per run of equal labels along X (closed forms, one set
+                         of atomics per run) instead of per voxel: the same regions, sums and mode, bit for bit.  Neither call
+                         needs nl_branchfeat_frame first.
    nl_branchfeat_fetch_regions : labels (R) int64 ascending; sums (F, R) int64 with F = 1 + 3 D + D (D + 1) / 2: the voxel count, per
                          axis the smallest coordinate, the largest, the sum of the coordinates, then the sums of the products
                          c_a * c_b for a <= b in row order, all exact; mode (R) int64 = the most frequent reassigned label over the
@@ -720,6 +723,8 @@ int nl_branchfeat_fetch(nl_branchfeat *branchfeat, int64_t *coords, int64_t *lab
                         int64_t *branch_label, void *comp, uint32_t *edges, int32_t *count, double *median, char *err, size_t errlen);
 int nl_branchfeat_regions(nl_branchfeat *branchfeat, const void *labels, int dtype, const void *reassigned, int reassigned_dtype,
                           int64_t *n_regions, char *err, size_t errlen);
+int nl_branchfeat_regions_rows(nl_branchfeat *branchfeat, const void *labels, int dtype, const void *reassigned, int reassigned_dtype,
+                               int64_t *n_regions, char *err, size_t errlen);
 int nl_branchfeat_fetch_regions(nl_branchfeat *branchfeat, int64_t *labels, int64_t *sums, int64_t *mode, char *err, size_t errlen);
 int nl_branchfeat_kernel_ms(nl_branchfeat *branchfeat, float *ms, char *err, size_t errlen);
 

@@ -6,7 +6,8 @@
 // so every per-label array is dense: one row per label present, whatever the values), per skeleton voxel its degree (same-label
 // neighbours) and its radius (nf_nearest_sq of nodefeat.inc over the border bits), per label the same-label pairs per "positive"
 // offset, the sorted list of 2 * radius and its median, and over the full branch-label volume the exact integer sums of every
-// region and the most frequent reassigned label.
+// region and the most frequent reassigned label.  The organelle level (DESIGN.md section 18) takes the same sums over the
+// component-label volume per run of equal labels along X.
 //
 // Per-label lists are one sorted array: keys (label rank, value) go through a bitonic sort of the whole array, padded with keys
 // above all others to a power of two, after which label b's values lie sorted at [off[b], off[b + 1]).  A group may have any size.
@@ -260,4 +261,67 @@ static __global__ __launch_bounds__(256) void bf_mode_kernel(const u64 *__restri
     }
     const u64 len = (u64)(hi - i);
     atomicMax(&best[key >> 32], (len << 32) | (0xffffffffull - (key & 0xffffffffull)));
+}
+
+// ---- region sums by row runs -----------------------------------------------------------------------------------------------------
+#define BF_ROWS_BAND 16               // consecutive rows (one plane) of a workgroup: four per wave
+
+// field f of the layout of bf_region_kernel: 0 and the fields past the extrema add, 1 .. D take the minimum, D + 1 .. 2 D the maximum
+template <int D> __device__ __forceinline__ void bf_field_apply(u64 *cell, int f, u64 v) {
+    if (f >= 1 && f <= D) atomicMin(cell, v);
+    else if (f > D && f <= 2 * D) atomicMax(cell, v);
+    else atomicAdd(cell, v);
+}
+
+// The sums of bf_region_kernel, bit for bit (integer add, min and max only: no order matters), taken per run of equal labels along
+// X instead of per voxel.  A workgroup owns a band of BF_ROWS_BAND consecutive rows (z, y) of one plane, a wave whole rows of it,
+// which it walks in chunks of 64 voxels.  One ballot marks the lanes whose label differs from the lane before (lane 0 always: a run
+// never continues from a chunk, let alone from a row, into the next -- it becomes two runs, and the sums are additive); the head
+// lane of a run of label > 0 takes the run's length [x0, x0 + len) from the next set bit and adds closed forms, one global atomic
+// per field and run:
+//     n += len;  min / max: x0 and x0 + len - 1 for x, z and y themselves;  S_x += len x0 + len (len - 1) / 2,  S_a += c_a len;
+//     Q_xx += len x0^2 + x0 len (len - 1) + (len - 1) len (2 len - 1) / 6,  Q_ax += c_a S_x(run),  Q_ab += c_a c_b len.
+// len <= 64 here (a chunk) and coordinates < 2^15 (the host checks) keep every term below 2^15 * 2^15 * 2^15 = 2^45 < 2^47; the
+// totals keep bf_region_kernel's bound Q < 2^61.  acc starts as for bf_region_kernel.  (A per-workgroup LDS table that combined the
+// runs of a band before they reached global memory was measured and left out: DESIGN.md section 18.)
+template <int D>
+__global__ __launch_bounds__(256) void bf_region_rows_kernel(BfLabels lab, NfGeom g, i64 bands, const u64 *__restrict__ pres, const int *__restrict__ pre,
+                                                             i64 R, u64 *__restrict__ acc) {
+    constexpr int F = 1 + 3 * D + D * (D + 1) / 2;
+    static_assert(F <= 16, "the host allocates sixteen fields per region");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const i64 z = (i64)blockIdx.x / bands, y0 = ((i64)blockIdx.x % bands) * BF_ROWS_BAND;
+    const i64 y1 = y0 + BF_ROWS_BAND < g.ny ? y0 + BF_ROWS_BAND : g.ny;
+    for (i64 y = y0 + wave; y < y1; y += 4) {
+        const i64 row = (z * g.ny + y) * g.nx;
+        for (i64 xc = 0; xc < g.nx; xc += 64) {                        // uniform over the wave: ballot and shuffle see all 64 lanes
+            const i64 x = xc + lane;
+            i64 l = x < g.nx ? lab(row + x) : 0;                       // past the row's end: background, which ends a run at nx
+            l = l > 0 ? l : 0;
+            const i64 before = __shfl_up(l, 1);
+            const u64 heads = __ballot(lane == 0 || l != before);
+            if (l == 0 || !((heads >> lane) & 1ull)) continue;         // the loop's bounds are uniform: the wave is whole again at its head
+            const u64 rest = lane == 63 ? 0ull : heads >> (lane + 1);  // the heads after this one
+            const u64 len = rest ? (u64)__ffsll((long long)rest) : (u64)(64 - lane);       // <= 64, and x + len <= nx
+            const i64 r = ra_rank(pres, pre, l);
+            const u64 ux = (u64)x;
+            const u64 sx = len * ux + len * (len - 1) / 2;                                 // sum of x over the run
+            const u64 qxx = len * ux * ux + ux * len * (len - 1) + (len - 1) * len * (2 * len - 1) / 6;
+            u64 c[D], v[F];
+            if (D == 3) c[0] = (u64)z;
+            c[D - 2] = (u64)y;
+            c[D - 1] = ux;
+            int f = 0;
+            v[f++] = len;
+            for (int a = 0; a < D; ++a) v[f++] = c[a];
+            for (int a = 0; a < D - 1; ++a) v[f++] = c[a];
+            v[f++] = ux + len - 1;
+            for (int a = 0; a < D - 1; ++a) v[f++] = c[a] * len;
+            v[f++] = sx;
+            for (int a = 0; a < D; ++a)
+                for (int b = a; b < D; ++b) v[f++] = b < D - 1 ? c[a] * c[b] * len : a < D - 1 ? c[a] * sx : qxx;
+#pragma unroll
+            for (int j = 0; j < F; ++j) bf_field_apply<D>(&acc[(i64)j * R + r], j, v[j]);
+        }
+    }
 }

@@ -299,10 +299,12 @@ extern "C" int nl_branchfeat_fetch(nl_branchfeat *h, int64_t *coords, int64_t *l
     return NL_OK;
 }
 
-// The regions of a branch-label volume of the object's shape (an integer dtype): its distinct labels > 0 with their sums, and,
-// when `reassigned` is not NULL (an integer dtype, values in [0, 2^31)), the most frequent reassigned label over every region.
-extern "C" int nl_branchfeat_regions(nl_branchfeat *h, const void *labels, int dtype, const void *reassigned, int reassigned_dtype, int64_t *n_regions,
-                                     char *err, size_t errlen) {
+// The regions of a label volume of the object's shape (an integer dtype): its distinct labels > 0 with their sums, and, when
+// `reassigned` is not NULL (an integer dtype, values in [0, 2^31)), the most frequent reassigned label over every region.  `rows`
+// picks the sum kernel (one lane per voxel, or one head lane per run along X: the same sums); everything else is shared.
+// Needs no frame: every buffer it uses is grown here.
+static int bf_regions(nl_branchfeat *h, bool rows, const void *labels, int dtype, const void *reassigned, int reassigned_dtype, int64_t *n_regions,
+                      char *err, size_t errlen) {
     STAGE_ENTER(h, "branch-feature object");
     if (!labels || !n_regions) return nl_fail(err, errlen, NL_EINVAL, "NULL labels or n_regions");
     const size_t ls = dtype_size(dtype), rs = reassigned ? dtype_size(reassigned_dtype) : 1;
@@ -327,7 +329,10 @@ extern "C" int nl_branchfeat_regions(nl_branchfeat *h, const void *labels, int d
     if (R > 0) {
         NL_HIP(hipMemsetAsync(h->acc, 0, (size_t)(F * R) * 8, st));
         NL_HIP(hipMemsetAsync(h->acc + R, 0xff, (size_t)(h->ndim * R) * 8, st));      // the smallest coordinates
-        if (h->ndim == 3) bf_region_kernel<3><<<bf_grid(n), 256, 0, st>>>(lab, n, h->g, h->pres, h->lpre, R, h->acc);
+        const i64 bands = (h->g.ny + BF_ROWS_BAND - 1) / BF_ROWS_BAND;        // nz * bands <= 2^15 * 2^11 workgroups
+        if (rows && h->ndim == 3) bf_region_rows_kernel<3><<<(unsigned)(h->g.nz * bands), 256, 0, st>>>(lab, h->g, bands, h->pres, h->lpre, R, h->acc);
+        else if (rows) bf_region_rows_kernel<2><<<(unsigned)(h->g.nz * bands), 256, 0, st>>>(lab, h->g, bands, h->pres, h->lpre, R, h->acc);
+        else if (h->ndim == 3) bf_region_kernel<3><<<bf_grid(n), 256, 0, st>>>(lab, n, h->g, h->pres, h->lpre, R, h->acc);
         else bf_region_kernel<2><<<bf_grid(n), 256, 0, st>>>(lab, n, h->g, h->pres, h->lpre, R, h->acc);
         NL_CHECK_LAUNCH();
         counts.resize((size_t)R);
@@ -366,6 +371,16 @@ extern "C" int nl_branchfeat_regions(nl_branchfeat *h, const void *labels, int d
     h->has_regions = true;
     *n_regions = R;
     return NL_OK;
+}
+
+extern "C" int nl_branchfeat_regions(nl_branchfeat *h, const void *labels, int dtype, const void *reassigned, int reassigned_dtype, int64_t *n_regions,
+                                     char *err, size_t errlen) {
+    return bf_regions(h, false, labels, dtype, reassigned, reassigned_dtype, n_regions, err, errlen);
+}
+
+extern "C" int nl_branchfeat_regions_rows(nl_branchfeat *h, const void *labels, int dtype, const void *reassigned, int reassigned_dtype,
+                                          int64_t *n_regions, char *err, size_t errlen) {
+    return bf_regions(h, true, labels, dtype, reassigned, reassigned_dtype, n_regions, err, errlen);
 }
 
 // Downloads the loaded regions: labels (R) int64 ascending, sums (fields, R) int64 with fields = 1 + 3 D + D (D + 1) / 2 (n, the

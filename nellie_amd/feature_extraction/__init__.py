@@ -1,6 +1,8 @@
-"""Feature extraction: the hierarchy's levels on the HIP engine (voxels, nodes, branches)."""
+"""Feature extraction: the hierarchy's levels on the HIP engine (voxels, nodes, branches, organelles)."""
 from nellie_amd.feature_extraction.branches import BranchFeatures, Branches
+from nellie_amd.feature_extraction.components import ComponentFeatures, Components
 from nellie_amd.feature_extraction.nodes import NodeFeatures, Nodes, aggregate_stats_for_class
 from nellie_amd.feature_extraction.voxels import VoxelFeatures, Voxels
 
-__all__ = ["Voxels", "VoxelFeatures", "Nodes", "NodeFeatures", "aggregate_stats_for_class", "Branches", "BranchFeatures"]
+__all__ = ["Voxels", "VoxelFeatures", "Nodes", "NodeFeatures", "aggregate_stats_for_class", "Branches", "BranchFeatures", "Components",
+           "ComponentFeatures"]

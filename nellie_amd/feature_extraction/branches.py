@@ -116,14 +116,19 @@ def skeleton_columns(f, spacing, D):
     return dict(branch_length=length, branch_thickness=thick, branch_aspect_ratio=aspect, branch_tortuosity=tort)
 
 
-def region_columns(sums, mode, spacing, D):
-    """{name: (regions,) float64} of REGION_STATS from the exact sums of every region (hipnative.BranchFeatures.fetch_regions):
-    skimage's area, extent, centroid and major / minor axis length with `spacing`, restated on n, S_a = sum c_a and
-    Q_ab = sum c_a c_b; mode < 0: no reassigned labels"""
+def region_stats(prefix):
+    """the names of the region columns of a level: REGION_STATS with `prefix` in place of `branch`"""
+    return tuple(prefix + k[len("branch"):] if k.startswith("branch_") else k for k in REGION_STATS)
+
+
+def region_columns(sums, mode, spacing, D, prefix="branch"):
+    """{name: (regions,) float64} of REGION_STATS (of region_stats(prefix)) from the exact sums of every region
+    (hipnative.BranchFeatures.fetch_regions): skimage's area, extent, centroid and major / minor axis length with `spacing`,
+    restated on n, S_a = sum c_a and Q_ab = sum c_a c_b; mode < 0: no reassigned labels"""
     R = sums.shape[1]
     s = [float(v) for v in spacing]
     P = float(np.prod(spacing))
-    out = {k: np.full(R, np.nan) for k in REGION_STATS}
+    out = {k: np.full(R, np.nan) for k in region_stats(prefix)}
     if R == 0:
         return out
     n, lo, hi, S = sums[0], sums[1:1 + D], sums[1 + D:1 + 2 * D], sums[1 + 2 * D:1 + 3 * D]
@@ -134,8 +139,8 @@ def region_columns(sums, mode, spacing, D):
             Q[a, b] = Q[b, a] = sums[f]
             f += 1
     area = n * P
-    out["branch_area"] = area
-    out["branch_extent"] = area / (np.prod(hi - lo + 1, axis=0).astype(np.float64) * P)
+    out[prefix + "_area"] = area
+    out[prefix + "_extent"] = area / (np.prod(hi - lo + 1, axis=0).astype(np.float64) * P)
     for a in range(D):
         out["zyx"[3 - D + a]] = (S[a] / n) * s[a]
     n_big, S_big = n.astype(object), S.astype(object)             # Python integers: n * Q - S * S is formed exactly
@@ -146,9 +151,9 @@ def region_columns(sums, mode, spacing, D):
             C[:, a, b] = (n_big * Q[a, b].astype(object) - S_big[a] * S_big[b]).astype(np.float64) / nn * (s[a] * s[b])
     lam = np.clip(np.linalg.eigvalsh(C), 0.0, None)
     if D == 3:
-        out["branch_axis_length_maj"], out["branch_axis_length_min"] = np.sqrt(20.0 * lam.max(axis=1)), np.sqrt(20.0 * lam.min(axis=1))
+        out[prefix + "_axis_length_maj"], out[prefix + "_axis_length_min"] = np.sqrt(20.0 * lam.max(axis=1)), np.sqrt(20.0 * lam.min(axis=1))
     else:
-        out["branch_axis_length_maj"], out["branch_axis_length_min"] = 4.0 * np.sqrt(lam.max(axis=1)), 4.0 * np.sqrt(lam.min(axis=1))
+        out[prefix + "_axis_length_maj"], out[prefix + "_axis_length_min"] = 4.0 * np.sqrt(lam.max(axis=1)), 4.0 * np.sqrt(lam.min(axis=1))
     out["reassigned_label"] = np.where(mode >= 0, mode.astype(np.float64), np.nan)
     return out
 
@@ -260,14 +265,15 @@ class Branches:
 
 def feature_frames(level, labels):
     """per frame with rows: (t, float64 array (rows, columns), header) by the reference's saving rule (hierarchical.py:279-337): the
-    columns t, label, <statistic>_<key> of the node aggregates (if any) and of the voxel aggregates, then <feature>_raw for every
-    feature of features_to_save.  Columns of different lengths raise ValueError."""
+    columns t, label, <statistic>_<key> of the node aggregates (if any), of the voxel aggregates and of the branch aggregates (a
+    level that has them), then <feature>_raw for every feature of features_to_save.  Columns of different lengths raise ValueError."""
     for t in range(len(labels)):
         lab = np.asarray(labels[t])
         if len(lab) == 0:
             continue
         names, columns = [], []
-        for frames in (getattr(level, "aggregate_node_metrics", None), getattr(level, "aggregate_voxel_metrics", None)):
+        for frames in (getattr(level, "aggregate_node_metrics", None), getattr(level, "aggregate_voxel_metrics", None),
+                       getattr(level, "aggregate_branch_metrics", None)):
             if not frames:
                 continue
             names += [f"{stat}_{key}" for stat, keys in frames[t].items() for key in keys]

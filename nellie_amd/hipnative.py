@@ -176,6 +176,7 @@ _PROTOS = {
     "nl_branchfeat_frame": [_p, _p, _int, _p, _int, _p, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "nl_branchfeat_fetch": [_p] * 12,
     "nl_branchfeat_regions": [_p, _p, _int, _p, _int, C.POINTER(_i64)],
+    "nl_branchfeat_regions_rows": [_p, _p, _int, _p, _int, C.POINTER(_i64)],
     "nl_branchfeat_fetch_regions": [_p, _p, _p, _p],
     "nl_branchfeat_kernel_ms": [_p, _p],
     "nl_host_half_round": [_p, _p, _i64],
@@ -1505,12 +1506,14 @@ class BranchFeatures(_Handle):
         self._call("nl_branchfeat_fetch", *[_ptr(a) for a in out.values()])
         return out
 
-    def regions(self, labels, reassigned=None) -> int:
-        """the regions of a branch-label volume, with the most frequent reassigned label of each when `reassigned` is given"""
+    def regions(self, labels, reassigned=None, rows=False) -> int:
+        """the regions of a label volume, with the most frequent reassigned label of each when `reassigned` is given; `rows` takes
+        the sums per run of equal labels along X instead of per voxel: the same values"""
         a = self._labels(labels, self.shape, "branch label")
         r = None if reassigned is None else self._labels(reassigned, self.shape, "reassigned label")
         count = _i64(0)
-        self._call("nl_branchfeat_regions", _ptr(a), DTYPE_CODES[a.dtype], _opt(r), DTYPE_CODES[r.dtype] if r is not None else 0, C.byref(count))
+        self._call("nl_branchfeat_regions_rows" if rows else "nl_branchfeat_regions", _ptr(a), DTYPE_CODES[a.dtype], _opt(r),
+                   DTYPE_CODES[r.dtype] if r is not None else 0, C.byref(count))
         self.n_regions = int(count.value)
         return self.n_regions
 
