@@ -663,6 +663,9 @@ int nl_voxfeat_kernel_ms(nl_voxfeat *voxfeat, float *ms, char *err, size_t errle
                          (n_nodes float64).  NULL pointers are skipped.
    nl_nodefeat_groups  : group j = idx[offsets[j] .. offsets[j + 1]), in the order given, neither sorted nor disjoint; offsets has
                          n_groups + 1 entries from 0.  At most 2^31 - 1 indices in all.  longest = L.
+   nl_nodefeat_set_wide_from : from the next nl_nodefeat_groups on, groups of at least wide_from values are summed one block of
+                         8192 elements per wave and the blocks' sums added in order, the others one group
+                         per wave; 0 = never.  The results are the same bits either way; the default is a measured choice.
    nl_nodefeat_aggregate : values (float32, float64 or integers of at most 32 bits; n_values above every index) as float64.
                          out (5, n_groups) float64 = mean, std_dev, min, max, sum: nanmean, nanstd, nanmin, nanmax and nansum of
                          the rows of the groups' matrix padded with NaN to L columns.  A group without a number: NaN, sum 0.
@@ -680,6 +683,7 @@ int nl_nodefeat_frame(nl_nodefeat *nodefeat, const void *pixel_class, int class_
 int nl_nodefeat_fetch(nl_nodefeat *nodefeat, int64_t *coords, void *comp, void *branch, double *thickness, char *err, size_t errlen);
 int nl_nodefeat_groups(nl_nodefeat *nodefeat, const int64_t *offsets, const int64_t *idx, int64_t n_groups, int64_t *longest, char *err,
                        size_t errlen);
+int nl_nodefeat_set_wide_from(nl_nodefeat *nodefeat, int64_t wide_from, char *err, size_t errlen);
 int nl_nodefeat_aggregate(nl_nodefeat *nodefeat, const void *values, int dtype, int64_t n_values, double *out, char *err, size_t errlen);
 int nl_nodefeat_node_stats(nl_nodefeat *nodefeat, const int64_t *coords, const float *vec01, const float *vec12, int64_t n_vox, double *out,
                            char *err, size_t errlen);

@@ -9,6 +9,7 @@
 
 #define NF_MAX_ROWS ((i64)1 << 30)          // nodes per frame: ranks are ints
 #define NF_MAX_IDX (((i64)1 << 31) - 1)     // indices in all groups together, and groups: a group's length and L are ints
+#define NF_WIDE_FROM (4 * NF_BLOCK + 1)      // groups of at least that many values are summed a buffer block per wave: measured, DESIGN.md section 19
 enum { NF_MS_LIST, NF_MS_THICKNESS, NF_MS_STATS, NF_MS_AGGREGATE, NF_MS_PARTS };
 
 struct nl_nodefeat : StageBase {
@@ -25,6 +26,10 @@ struct nl_nodefeat : StageBase {
     // groups
     i64 groups = 0, total = 0, L = 0, idx_min = 0, idx_max = -1, grp_cap = 0, idx_cap = 0, sc_cap = 0; bool has_groups = false;
     i64 *d_off = nullptr, *d_idx = nullptr; double *d_scratch = nullptr, *d_out = nullptr;
+    // the wide groups of the loaded set: their (group, block) items, one slot of partial results per item and per group
+    i64 wide_from = NF_WIDE_FROM, listed_from = 0, n_wide = 0, n_items = 0, wide_cap = 0, item_cap = 0;
+    i64 *d_wide = nullptr, *d_items = nullptr, *d_pcount = nullptr, *d_wtotal = nullptr; int *d_plo_at = nullptr, *d_phi_at = nullptr;
+    double *d_psum = nullptr, *d_plo = nullptr, *d_phi = nullptr, *d_wmean = nullptr;
     // the voxels' coordinates and vectors of nl_nodefeat_node_stats
     i64 *d_vcoords = nullptr; float *d_v01 = nullptr, *d_v12 = nullptr; i64 vox_cap = 0;
     float ms[NF_MS_PARTS] = {0.f, 0.f, 0.f, 0.f};
@@ -33,7 +38,8 @@ struct nl_nodefeat : StageBase {
 extern "C" int nl_nodefeat_destroy(nl_nodefeat *h) {
     if (!h) return NL_OK;
     stage_close(*h, {h->d_in, h->nbits, h->bbits, h->npre, h->d_wcount, h->d_any, h->scan.d_bsum, h->scan.d_total, h->node_vox, h->coords, h->lab_c,
-                     h->lab_b, h->thick, h->d_off, h->d_idx, h->d_scratch, h->d_out, h->d_vcoords, h->d_v01, h->d_v12},
+                     h->lab_b, h->thick, h->d_off, h->d_idx, h->d_scratch, h->d_out, h->d_vcoords, h->d_v01, h->d_v12, h->d_wide, h->d_items, h->d_pcount, h->d_wtotal,
+                     h->d_plo_at, h->d_phi_at, h->d_psum, h->d_plo, h->d_phi, h->d_wmean},
                 {h->scan.h_total});
     delete h;
     return NL_OK;
@@ -174,7 +180,29 @@ extern "C" int nl_nodefeat_groups(nl_nodefeat *h, const int64_t *offsets, const 
         hi = q == 0 || idx[q] > hi ? idx[q] : hi;
     }
     if (lo < 0) return nl_fail(err, errlen, NL_EINVAL, "negative index in a group");
+    // the wide groups: (group, first item) each, and an item (row of that list, block) for every buffer block that starts below k
+    std::vector<i64> wide, items;
+    for (i64 j = 0; j < n_groups && h->wide_from > 0; ++j) {
+        const i64 k = offsets[j + 1] - offsets[j];
+        if (k == 0 || k < h->wide_from) continue;
+        const i64 w = (i64)wide.size() / 2;
+        wide.push_back(j);
+        wide.push_back((i64)items.size() / 2);
+        for (i64 b = 0; b * NF_BLOCK < k; ++b) {
+            items.push_back(w);
+            items.push_back(b);
+        }
+    }
+    const i64 n_wide = (i64)wide.size() / 2, n_items = (i64)items.size() / 2;
+    if (n_items > NF_MAX_IDX) return nl_fail(err, errlen, NL_EINVAL, "more than %lld buffer blocks in the wide groups of one call", (long long)NF_MAX_IDX);
     hipStream_t st = h->stream;
+    if (int rc = stage_grow(&h->wide_cap, n_wide, n_wide, {{&h->d_wide, 2 * 8}, {&h->d_wmean, 8}, {&h->d_wtotal, 8}}, err, errlen)) return rc;
+    if (int rc = stage_grow(&h->item_cap, n_items, n_items, {{&h->d_items, 2 * 8}, {&h->d_psum, 8}, {&h->d_pcount, 8}, {&h->d_plo, 8}, {&h->d_phi, 8},
+                                                               {&h->d_plo_at, 4}, {&h->d_phi_at, 4}}, err, errlen)) return rc;
+    if (n_wide > 0) {
+        NL_HIP(hipMemcpyAsync(h->d_wide, wide.data(), (size_t)n_wide * 16, hipMemcpyHostToDevice, st));
+        NL_HIP(hipMemcpyAsync(h->d_items, items.data(), (size_t)n_items * 16, hipMemcpyHostToDevice, st));
+    }
     const i64 scratch = total / 64 + 2 * n_groups + 2;
     if (int rc = stage_grow(&h->grp_cap, n_groups + 1, n_groups + 1, {{&h->d_off, 8}, {&h->d_out, 6 * 8}}, err, errlen)) return rc;
     if (int rc = stage_grow(&h->idx_cap, total, total, {{&h->d_idx, 8}}, err, errlen)) return rc;
@@ -187,9 +215,21 @@ extern "C" int nl_nodefeat_groups(nl_nodefeat *h, const int64_t *offsets, const 
     h->L = L;
     h->idx_min = lo;
     h->idx_max = hi;
+    h->listed_from = h->wide_from;
+    h->n_wide = n_wide;
+    h->n_items = n_items;
     h->has_groups = true;
     h->ms[NF_MS_AGGREGATE] = 0.f;
     *longest = L;
+    return NL_OK;
+}
+
+// From the next nl_nodefeat_groups on, groups of at least wide_from values are aggregated a buffer block per wave (nodefeat.inc,
+// nf_wide_block_kernel), the others a group per wave; 0: none.  Either way the values are the same bits.
+extern "C" int nl_nodefeat_set_wide_from(nl_nodefeat *h, int64_t wide_from, char *err, size_t errlen) {
+    if (!h) return nl_fail(err, errlen, NL_EINVAL, "node-feature object is NULL");
+    if (wide_from < 0) return nl_fail(err, errlen, NL_EINVAL, "wide_from must be 0 (never) or at least 1");
+    h->wide_from = wide_from;
     return NL_OK;
 }
 
@@ -207,8 +247,22 @@ extern "C" int nl_nodefeat_aggregate(nl_nodefeat *h, const void *values, int dty
     hipStream_t st = h->stream;
     if (int rc = nf_upload(h, values, n_values, vs, err, errlen)) return rc;
     if (int rc = stage_start(*h, err, errlen)) return rc;
-    nf_aggregate_kernel<<<(unsigned)h->groups, 64, 0, st>>>(h->d_in, dtype, n_values, h->d_off, h->d_idx, h->groups, (int)h->L, h->d_scratch, h->d_out);
+    const i64 wide_from = h->n_wide > 0 ? h->listed_from : 0;          // the threshold the loaded groups were listed under
+    nf_aggregate_kernel<<<(unsigned)h->groups, 64, 0, st>>>(h->d_in, dtype, n_values, h->d_off, h->d_idx, h->groups, (int)h->L, wide_from, h->d_scratch,
+                                                            h->d_out);
     NL_CHECK_LAUNCH();
+    if (h->n_wide > 0) {
+        const NfWide W{h->d_items, h->d_wide, h->d_psum, h->d_pcount, h->d_plo, h->d_phi, h->d_plo_at, h->d_phi_at, h->d_wmean, h->d_wtotal};
+        const unsigned gi = (unsigned)h->n_items, gw = (unsigned)h->n_wide;
+        nf_wide_block_kernel<false><<<gi, 64, 0, st>>>(h->d_in, dtype, n_values, h->d_off, h->d_idx, (int)h->L, W, h->n_items);
+        NL_CHECK_LAUNCH();
+        nf_wide_chain_kernel<false><<<gw, 64, 0, st>>>(h->d_off, h->groups, W, h->n_wide, h->d_out);
+        NL_CHECK_LAUNCH();
+        nf_wide_block_kernel<true><<<gi, 64, 0, st>>>(h->d_in, dtype, n_values, h->d_off, h->d_idx, (int)h->L, W, h->n_items);
+        NL_CHECK_LAUNCH();
+        nf_wide_chain_kernel<true><<<gw, 64, 0, st>>>(h->d_off, h->groups, W, h->n_wide, h->d_out);
+        NL_CHECK_LAUNCH();
+    }
     if (int rc = stage_stop_record(*h, err, errlen)) return rc;
     NL_HIP(hipMemcpyAsync(out, h->d_out, (size_t)h->groups * 5 * 8, hipMemcpyDeviceToHost, st));
     return stage_stop_wait(*h, &h->ms[NF_MS_AGGREGATE], err, errlen);

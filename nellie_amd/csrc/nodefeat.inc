@@ -3,7 +3,8 @@
 //
 // Nodes are the voxels with pixel class > 0, compacted in raster order by the mask, scan and rank of rank_scan.inc.  The border
 // is one bit per voxel; a wave searches a growing box of it around its node for the nearest set bit.  Groups of values (a node's
-// voxels; later a branch's nodes) are CSR lists of indices; one wave reduces one group.  Every sum is numpy's sum of a row of L
+// voxels; later a branch's nodes) are CSR lists of indices; one wave reduces one group, or one buffer block of a wide group (the
+// image's one group per frame, DESIGN.md section 19).  Every sum is numpy's sum of a row of L
 // elements, the group's k values followed by L - k zeros: blocks of 8192 elements added in order, each summed as a pairwise tree
 // whose shape comes from the block's length, the work from k (nf_tree_sum).
 //
@@ -319,34 +320,47 @@ struct NfSquaredDeviation {           // (v - mean)^2 with NaN entries as +0.0: 
     }
 };
 
+// The smallest and the largest value with their positions in the group, at = -1 for none.  Among equal extremes (+0.0 and -0.0)
+// the one latest in the group is taken, as numpy's fmin / fmax reductions do; positions are distinct, so merging is order-free.
+struct NfExtremes {
+    double lo, hi;
+    int lo_at, hi_at;
+    __device__ void take(double x, int at) {                           // positions ascending
+        if (lo_at < 0 || x <= lo) { lo = x; lo_at = at; }
+        if (hi_at < 0 || x >= hi) { hi = x; hi_at = at; }
+    }
+    __device__ void merge(double ol, int ol_at, double oh, int oh_at) {
+        if (ol_at >= 0 && (lo_at < 0 || ol < lo || (ol == lo && ol_at > lo_at))) { lo = ol; lo_at = ol_at; }
+        if (oh_at >= 0 && (hi_at < 0 || oh > hi || (oh == hi && oh_at > hi_at))) { hi = oh; hi_at = oh_at; }
+    }
+    __device__ void wave() {                                           // every lane ends with the wave's
+        for (int w = 32; w > 0; w >>= 1) merge(__shfl_xor(lo, w), __shfl_xor(lo_at, w), __shfl_xor(hi, w), __shfl_xor(hi_at, w));
+    }
+};
+
 // One wave per group: out[key * groups + group] for key = mean, std_dev, min, max, sum, over the group's values as a row padded
-// to L columns.  Among equal extremes (+0.0 and -0.0) the one latest in the group is taken, as numpy's fmin / fmax reductions do.
+// to L columns.  A group of at least wide_from values (wide_from > 0) is left to the block kernels below.
 static __global__ __launch_bounds__(64) void nf_aggregate_kernel(const void *__restrict__ values, int dtype, i64 nval, const i64 *__restrict__ off,
-                                                                 const i64 *__restrict__ idx, i64 groups, int L, double *__restrict__ scratch,
-                                                                 double *__restrict__ out) {
+                                                                 const i64 *__restrict__ idx, i64 groups, int L, i64 wide_from,
+                                                                 double *__restrict__ scratch, double *__restrict__ out) {
     const i64 grp = blockIdx.x;
     if (grp >= groups) return;
     const int lane = threadIdx.x;
     const i64 a = off[grp];
     const int k = (int)(off[grp + 1] - a);
+    if (wide_from > 0 && k > 0 && k >= wide_from) return;
     const NfGroupValues v{values, dtype, nval, idx + a};
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    double lo = nan, hi = nan;
-    int lo_at = -1, hi_at = -1;
+    NfExtremes e{nan, nan, -1, -1};
     i64 count = 0;
     for (int i = lane; i < k; i += 64) {
         const double x = v(i);
         if (x != x) continue;
         ++count;
-        if (lo_at < 0 || x <= lo) { lo = x; lo_at = i; }
-        if (hi_at < 0 || x >= hi) { hi = x; hi_at = i; }
+        e.take(x, i);
     }
-    for (int w = 32; w > 0; w >>= 1) {
-        const double ol = __shfl_xor(lo, w), oh = __shfl_xor(hi, w);
-        const int ol_at = __shfl_xor(lo_at, w), oh_at = __shfl_xor(hi_at, w);
-        if (ol_at >= 0 && (lo_at < 0 || ol < lo || (ol == lo && ol_at > lo_at))) { lo = ol; lo_at = ol_at; }
-        if (oh_at >= 0 && (hi_at < 0 || oh > hi || (oh == hi && oh_at > hi_at))) { hi = oh; hi_at = oh_at; }
-    }
+    e.wave();
+    const double lo = e.lo, hi = e.hi;
     count = nf_wave_sum(count);
     double *sc = scratch + (a / 64 + 2 * grp);
     const double sum = nf_tree_sum(NfZeroNan{v}, k, L, sc);
@@ -357,6 +371,106 @@ static __global__ __launch_bounds__(64) void nf_aggregate_kernel(const void *__r
         out[groups + grp] = sqrt(var);
         out[2 * groups + grp] = lo;
         out[3 * groups + grp] = hi;
+        out[4 * groups + grp] = sum;
+    }
+}
+
+// ---- aggregation of wide groups, one wave per buffer block -----------------------------------------------------------------------
+// A row's blocks of NF_BLOCK elements are independent trees; only the chain `sum = sum + tree(block b)`, b ascending, is ordered
+// (nf_tree_sum).  So a wide group is cut into items (group, block): one wave sums one block exactly as nf_tree_sum would
+// (nf_wide_block_kernel), then one wave per group adds the blocks' sums in that order (nf_wide_chain_kernel).  Twice: the values,
+// which gives the mean, then the squared deviations from it.  The same additions in the same order as nf_aggregate_kernel: the
+// same bits.  No atomics; every item and every group has its own slots.
+struct NfWide {
+    const i64 *items;                 // (n_items, 2): the row of `wide` and the block
+    const i64 *wide;                  // (n_wide, 2): the group and its first item; its items follow one another, blocks ascending
+    double *sum;                      // per item: the block's sum
+    i64 *count;                       // per item: the block's values that are not NaN
+    double *lo, *hi;                  // per item: the block's extremes and their positions in the group (NfExtremes)
+    int *lo_at, *hi_at;
+    double *mean;                     // per wide group
+    i64 *total;                       // per wide group: its values that are not NaN
+};
+
+// One wave per item.  DEV = false: the block's sum of the values (NaN as +0.0), count and extremes.  DEV = true: its sum of the
+// squared deviations from the group's mean.  The leaf sums of nf_block_tree go through LDS: 129 doubles at most.
+template <bool DEV>
+__global__ __launch_bounds__(64) void nf_wide_block_kernel(const void *__restrict__ values, int dtype, i64 nval, const i64 *__restrict__ off,
+                                                           const i64 *__restrict__ idx, int L, NfWide W, i64 n_items) {
+    __shared__ double sc[NF_LEAF + 4];
+    const i64 item = blockIdx.x;
+    if (item >= n_items) return;
+    const int lane = threadIdx.x;
+    const i64 w = W.items[2 * item], b = W.items[2 * item + 1], grp = W.wide[2 * w];
+    const i64 a = off[grp];
+    const int k = (int)(off[grp + 1] - a);
+    const int base = (int)(b * NF_BLOCK), n_block = L - base < NF_BLOCK ? L - base : NF_BLOCK;
+    const int kb = k - base < n_block ? k - base : n_block;           // the block's elements that are not padding
+    if (kb <= 0) return;                                               // never: the host lists the blocks that start below k
+    const NfGroupValues v{values, dtype, nval, idx + a};
+    if (DEV) {
+        const double sum = nf_block_tree(NfSquaredDeviation{v, W.mean[w]}, base, kb, n_block, sc);
+        if (lane == 0) W.sum[item] = sum;
+        return;
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    NfExtremes e{nan, nan, -1, -1};
+    i64 count = 0;
+    for (int i = base + lane; i < base + kb; i += 64) {
+        const double x = v(i);
+        if (x != x) continue;
+        ++count;
+        e.take(x, i);
+    }
+    e.wave();
+    count = nf_wave_sum(count);
+    const double sum = nf_block_tree(NfZeroNan{v}, base, kb, n_block, sc);
+    if (lane == 0) {
+        W.sum[item] = sum;
+        W.count[item] = count;
+        W.lo[item] = e.lo; W.lo_at[item] = e.lo_at;
+        W.hi[item] = e.hi; W.hi_at[item] = e.hi_at;
+    }
+}
+
+// One wave per wide group: 0.0, then + the sum of every block, blocks ascending; the lanes fetch 64 sums at a time and every lane
+// adds them in order.  DEV = false: mean, min, max and sum of the group into `out`, the mean and the count kept for the second
+// pass.  DEV = true: std_dev.
+template <bool DEV>
+__global__ __launch_bounds__(64) void nf_wide_chain_kernel(const i64 *__restrict__ off, i64 groups, NfWide W, i64 n_wide, double *__restrict__ out) {
+    const i64 w = blockIdx.x;
+    if (w >= n_wide) return;
+    const int lane = threadIdx.x;
+    const i64 grp = W.wide[2 * w], first = W.wide[2 * w + 1];
+    const i64 k = off[grp + 1] - off[grp];
+    const int nb = (int)((k + NF_BLOCK - 1) / NF_BLOCK);
+    double sum = 0.0;
+    for (int b0 = 0; b0 < nb; b0 += 64) {
+        const int m = nb - b0 < 64 ? nb - b0 : 64;
+        const double p = lane < m ? W.sum[first + b0 + lane] : 0.0;
+        for (int j = 0; j < m; ++j) sum = sum + __shfl(p, j);
+    }
+    if (DEV) {
+        const double var = sum / (double)W.total[w];
+        if (lane == 0) out[groups + grp] = sqrt(var);
+        return;
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    NfExtremes e{nan, nan, -1, -1};
+    i64 count = 0;
+    for (int b = lane; b < nb; b += 64) {
+        count += W.count[first + b];
+        e.merge(W.lo[first + b], W.lo_at[first + b], W.hi[first + b], W.hi_at[first + b]);
+    }
+    e.wave();
+    count = nf_wave_sum(count);
+    const double mean = sum / (double)count;
+    if (lane == 0) {
+        W.mean[w] = mean;
+        W.total[w] = count;
+        out[grp] = mean;
+        out[2 * groups + grp] = e.lo;
+        out[3 * groups + grp] = e.hi;
         out[4 * groups + grp] = sum;
     }
 }

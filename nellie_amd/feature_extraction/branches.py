@@ -265,15 +265,15 @@ class Branches:
 
 def feature_frames(level, labels):
     """per frame with rows: (t, float64 array (rows, columns), header) by the reference's saving rule (hierarchical.py:279-337): the
-    columns t, label, <statistic>_<key> of the node aggregates (if any), of the voxel aggregates and of the branch aggregates (a
-    level that has them), then <feature>_raw for every feature of features_to_save.  Columns of different lengths raise ValueError."""
+    columns t, label, <statistic>_<key> of the node aggregates (if any), of the voxel aggregates, of the branch aggregates and of the
+    component aggregates (a level that has them), then <feature>_raw for every feature of features_to_save.  Columns of different lengths raise ValueError."""
     for t in range(len(labels)):
         lab = np.asarray(labels[t])
         if len(lab) == 0:
             continue
         names, columns = [], []
         for frames in (getattr(level, "aggregate_node_metrics", None), getattr(level, "aggregate_voxel_metrics", None),
-                       getattr(level, "aggregate_branch_metrics", None)):
+                       getattr(level, "aggregate_branch_metrics", None), getattr(level, "aggregate_component_metrics", None)):
             if not frames:
                 continue
             names += [f"{stat}_{key}" for stat, keys in frames[t].items() for key in keys]

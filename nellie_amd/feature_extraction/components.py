@@ -145,10 +145,11 @@ class Components:
 
 
 def _disjoint_statistics(level, t):
-    """the reference merges the three aggregate dicts of a frame with dict.update: concatenating them is the same table only while
-    no statistic has the same name in two of them"""
+    """the reference merges the aggregate dicts of a frame (three for the organelles, four for the image) with dict.update:
+    concatenating them is the same table only while no statistic has the same name in two of them"""
     seen = set()
-    for frames in (level.aggregate_node_metrics, level.aggregate_voxel_metrics, level.aggregate_branch_metrics):
+    for frames in (level.aggregate_node_metrics, level.aggregate_voxel_metrics, level.aggregate_branch_metrics,
+                   getattr(level, "aggregate_component_metrics", None)):
         if not frames:
             continue
         names = set(frames[t])

@@ -169,6 +169,7 @@ _PROTOS = {
     "nl_nodefeat_frame": [_p, _p, _int, _p, _int, _p, _int, _p, _int, C.POINTER(_i64)],
     "nl_nodefeat_fetch": [_p, _p, _p, _p, _p],
     "nl_nodefeat_groups": [_p, _p, _p, _i64, C.POINTER(_i64)],
+    "nl_nodefeat_set_wide_from": [_p, _i64],
     "nl_nodefeat_aggregate": [_p, _p, _int, _i64, _p],
     "nl_nodefeat_node_stats": [_p, _p, _p, _p, _i64, _p],
     "nl_nodefeat_kernel_ms": [_p, _p],
@@ -1429,6 +1430,10 @@ class NodeFeatures(_Handle):
         self._call("nl_nodefeat_groups", _ptr(off), _ptr(idx), off.size - 1, C.byref(longest))
         self.n_groups, self.longest = off.size - 1, int(longest.value)
         return self.longest
+
+    def set_wide_from(self, n) -> None:
+        """from the next groups() on, groups of at least n values are summed a buffer block per wave; 0: never.  Same bits either way."""
+        self._call("nl_nodefeat_set_wide_from", int(n))
 
     def aggregate(self, values) -> dict:
         """{key: (n_groups,) float64} for the keys mean, std_dev, min, max, sum of one 1-D value array over the loaded groups"""
