@@ -786,7 +786,7 @@ int nl_markers_finish(nl_ctx *ctx, int peak_min_distance, int64_t *n_markers, ch
 int nl_markers_store(nl_ctx *ctx, uint8_t *marker, float *distance, uint8_t *border, char *err, size_t errlen);
 
 /* ---- Network stage, the two dense per-voxel steps (nellie/segmentation/networking.py; 3-D volumes and 2-D images) ----
-   The skeletonisation itself (skimage, networking.py:394-409) and the per-object relabelling stay on the host.
+   The skeletonisation itself (skimage, networking.py:394-409) stays on the host; the rest of the stage is the next block.
    nl_skel_pixel_class  : `_get_pixel_class_impl` (networking.py:672-683) -- skel_mask = skel > 0;
                           class = min(4, convolve(skel_mask, ones(3,3,3), mode="constant", cval=0)) * skel_mask, uint8:
                           1 isolated, 2 tip, 3 edge, 4 junction.  n_skel (may be NULL) = skeleton voxels.
@@ -796,6 +796,38 @@ int nl_markers_store(nl_ctx *ctx, uint8_t *marker, float *distance, uint8_t *bor
    A context of shape (1, ny, nx) gives the reference's 2-D branch (ones(3,3)). */
 int nl_skel_pixel_class(nl_ctx *ctx, const int32_t *skel, uint8_t *pixel_class, int64_t *n_skel, char *err, size_t errlen);
 int nl_skel_branch_labels(nl_ctx *ctx, const uint8_t *pixel_class, int32_t *labels, int64_t *n_labels, char *err, size_t errlen);
+
+/* ---- Network stage behind the thinning (networking.py:828-851), one frame resident on the context from upload to download ----
+   Whole volumes of fewer than 2^31 voxels; ndim = 2 needs a context of shape (1, ny, nx).  Labels are int32 and not negative.
+   nl_network_load       : labels, the thinning's mask (uint8, non-zero = skeleton voxel) and the Frangi frame (float32) go up;
+                           skel = labels * mask (networking.py:408).  max_label (may be NULL) = the largest label.
+   nl_network_clean_seed : `_remove_connected_label_pixels_impl` (networking.py:261-296) -- a skeleton voxel whose 3x3x3 (2-D: 3x3)
+                           neighbourhood, centre included, outside = background, holds two different labels is zeroed, voxels on a
+                           face of the frame never; then `_add_missing_skeleton_labels` (networking.py:342-387) -- every label
+                           without a skeleton voxel gets one at the maximum of the Frangi frame over its voxels.  Among equal
+                           maxima the lowest raster index wins and NaN ranks above every number (the reference's pick follows no
+                           rule there).  n_removed / n_seeded (may be NULL): voxels zeroed / labels seeded.
+   nl_network_classes    : networking.py:839-847 -- the kernels of nl_skel_pixel_class and nl_skel_branch_labels on the resident
+                           skeleton.  n_skel / n_branches may be NULL.
+   nl_network_relabel_load: step 5 alone -- labels and branch labels (int32) go up, nl_network_relabel may follow.
+   nl_network_relabel    : `_relabel_objects` (networking.py:485-577) -- per label L in its bounding box, every voxel of L takes the
+                           branch label of the seed (branch > 0 and label == L) that scipy.ndimage.distance_transform_edt(~seeds,
+                           sampling = spacing, return_indices = True) picks, ties included; objects without a seed and the
+                           background stay 0.  spacing: ndim values.  scratch_voxels: box voxels one batch of objects may hold
+                           (<= 0: half of the free HBM), never less than one frame; objects are not split.  n_objects (objects with a
+                           seed), box_volume (the sum of their box volumes) and n_batches may be NULL.
+   nl_network_fetch      : the branch skeleton labels (int32), the pixel classes (uint8) and the relabelled volume (uint32); each may
+                           be NULL.
+   nl_network_kernel_ms  : ms[4] = stream time of clean, seed, classes, relabel of the current frame, transfers excluded. */
+int nl_network_load(nl_ctx *ctx, const int32_t *labels, const uint8_t *skel_mask, const float *frangi, int ndim, int64_t *max_label,
+                    char *err, size_t errlen);
+int nl_network_clean_seed(nl_ctx *ctx, int64_t *n_removed, int64_t *n_seeded, char *err, size_t errlen);
+int nl_network_classes(nl_ctx *ctx, int64_t *n_skel, int64_t *n_branches, char *err, size_t errlen);
+int nl_network_relabel_load(nl_ctx *ctx, const int32_t *labels, const int32_t *branch, int ndim, int64_t *max_label, char *err, size_t errlen);
+int nl_network_relabel(nl_ctx *ctx, const double *spacing, int64_t scratch_voxels, int64_t *n_objects, int64_t *box_volume,
+                       int64_t *n_batches, char *err, size_t errlen);
+int nl_network_fetch(nl_ctx *ctx, int32_t *branch, uint8_t *pixel_class, uint32_t *relabelled, char *err, size_t errlen);
+int nl_network_kernel_ms(nl_ctx *ctx, float *ms, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -918,10 +918,15 @@ extern "C" int nl_skel_pixel_class(nl_ctx *c, const int32_t *skel_host, uint8_t 
     NL_JOIN_SIDE(c);
     if (!skel_host) return nl_fail(err, errlen, NL_EINVAL, "nl_skel_pixel_class: skel is NULL");
     if (c->own_lo != 0 || c->own_hi != c->nzl || c->gnz != c->nzl) return nl_fail(err, errlen, NL_EINVAL, "the Network kernels run on a whole volume");
+    NL_HIP(hipMemcpyAsync(c->f[3], skel_host, (size_t)c->n * 4, hipMemcpyHostToDevice, c->stream));
+    return nw_pixel_class_resident(c, pixel_class_host, n_skel, err, errlen);
+}
+
+// The same on the int32 skeleton that already lies in f[3] (nl_skel_pixel_class's upload, or the Network stage's own steps).
+int nw_pixel_class_resident(nl_ctx *c, uint8_t *pixel_class_host, int64_t *n_skel, char *err, size_t errlen) {
     const int wpr = (int)((c->nx + 63) / 64);
     const i64 nrows = c->nzl * c->ny, nw = nrows * wpr;
     ProfScope ps(c, "network");
-    NL_HIP(hipMemcpyAsync(c->f[3], skel_host, (size_t)c->n * 4, hipMemcpyHostToDevice, c->stream));
     unsigned long long *skel = (unsigned long long *)c->m[1], *branch = (unsigned long long *)c->m[2];
     nl_launch_pack_labels(grid1d(nw * 64, 256, (i64)1 << 20), c->stream, (const int *)c->f[3], skel, (int)c->nx, nrows, wpr);
     NL_CHECK_LAUNCH();

@@ -52,6 +52,16 @@ struct nl_ctx {
     float *d_vq = nullptr;     // global queue of voxels to eigen-solve (32-byte entries, one region per wave)
     unsigned int *d_vq_count = nullptr;   // entries written per region
     int nw_state = 0;             // Network: 1 after nl_skel_pixel_class (classes + branch bits resident)
+    // Network behind the thinning (nellie_hip_network.hip): the frame stays on the device from nl_network_load to nl_network_fetch
+    int nw_stage = 0;             // 0 nothing, 1 loaded (skel in f[0]), 2 cleaned and seeded (f[3]), 3 classes (f[2]) and branch labels (f[3]), 4 relabelled (f[0])
+    int nw_ndim = 3, nw_has_classes = 0;
+    i64 nw_max_label = 0;
+    int *nw_lab = nullptr; float *nw_fr = nullptr; uint8_t *nw_mask = nullptr;     // labels, Frangi values, thinning mask
+    void *nw_tab = nullptr; i64 nw_tab_cap = 0;                                   // per label: seed key | box | has skeleton | has seed
+    int *nw_feat = nullptr, *nw_stk = nullptr; i64 nw_scr_cap = 0;                 // relabel scratch: one feature and one stack slot per box voxel of a batch
+    void *nw_objs = nullptr; i64 nw_objs_cap = 0;                                  // the frame's NwObj table
+    hipEvent_t nw_ev[2] = {nullptr, nullptr};
+    float nw_ms[4] = {0, 0, 0, 0};                                                 // clean, seed, classes, relabel
     const float *mk_int = nullptr;   // Markers: the float32 intensities when they are read in place (a resident float32 input), else they live in d_vq
     float *mk_use = nullptr;      // Markers: LoG source when use_im = 'frangi' (inside d_vq), else the distance image
     float *mk_scratch = nullptr;  // Markers: volume between the Y and the X pass of the any-radius LoG path, allocated on first use

@@ -5,6 +5,7 @@
 //   nellie_comm.hip     RCCL loader, loopback transport, communicator pool, collectives         -> rccl(), comm_release, reduce_*, ag_reserve, allgather_sizes
 //   nellie_label.hip    Label / Network / streaming                                             -> nl_launch_threshold_pack
 //   nellie_markers.hip  Markers                                                                 -> nl_launch_pack_labels
+//   nellie_hip_network.hip  Network behind the thinning (clean, seed, per-object relabel)        -> nw_release
 //   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the six stage handles share nl_stage.h.
 // gfx950 only.
 #pragma once
@@ -191,6 +192,13 @@ int reduce_u32_max(nl_ctx *c, unsigned int *v, size_t n, char *err, size_t errle
 int ag_reserve(nl_ctx *c, size_t device_bytes, size_t host_bytes, char *err, size_t errlen);
 // bytes_of[r] = rank r's nbytes (one collective and one wait, through the small scratch)
 int allgather_sizes(nl_ctx *c, int64_t nbytes, int64_t *bytes_of, char *err, size_t errlen);
+
+// ---- defined in nellie_label.hip ----------------------------------------------------------------------------------------
+// nl_skel_pixel_class behind its upload: classes (f[2]) and branch bits of the int32 skeleton in f[3]
+int nw_pixel_class_resident(nl_ctx *c, uint8_t *pixel_class_host, int64_t *n_skel, char *err, size_t errlen);
+
+// ---- defined in nellie_hip_network.hip -----------------------------------------------------------------------------------
+void nw_release(nl_ctx *c);                              // the Network stage's own buffers and events (nl_ctx_destroy)
 
 // ---- kernels of one unit launched from another ---------------------------------------------------------------------------
 void nl_launch_threshold_pack(unsigned int grid, hipStream_t st, const float *f, const unsigned long long *support, unsigned long long *bits,

@@ -84,6 +84,13 @@ _PROTOS = {
     "nl_markers_store": [_p, _p, _p, _p],
     "nl_skel_pixel_class": [_p, _p, _p, C.POINTER(_i64)],
     "nl_skel_branch_labels": [_p, _p, _p, C.POINTER(_i64)],
+    "nl_network_load": [_p, _p, _p, _p, _int, C.POINTER(_i64)],
+    "nl_network_clean_seed": [_p, C.POINTER(_i64), C.POINTER(_i64)],
+    "nl_network_classes": [_p, C.POINTER(_i64), C.POINTER(_i64)],
+    "nl_network_relabel_load": [_p, _p, _p, _int, C.POINTER(_i64)],
+    "nl_network_relabel": [_p, C.POINTER(_f64), _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+    "nl_network_fetch": [_p, _p, _p, _p],
+    "nl_network_kernel_ms": [_p, C.POINTER(_f32)],
     "nl_mask_volume_fused": [_p, _f32, C.POINTER(_i64)],
     "nl_log2d_step": [_p, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), _int, _f32, _int, _int],
     "nl_log2d_finish": [_p, C.POINTER(_i64)],
@@ -790,6 +797,78 @@ class Context(_Handle):
         n = _i64(0)
         self._call("nl_skel_branch_labels", None if pc is None else _ptr(pc), _ptr(out), C.byref(n))
         return out, int(n.value)
+
+    # ---- Network behind the thinning (networking.py:828-851): one frame resident from network_load to network_fetch
+    def _network_frame(self, a, what, dtype, like=None):
+        """A frame of the context's shape ((1, ny, nx) contexts take (ny, nx) frames too) and of the shape `like` of the frame's
+        labels, C-contiguous in `dtype`; integer targets refuse a cast that would change a value."""
+        a = np.asarray(a)
+        full = tuple(int(s) for s in self.shape)
+        if like is not None and a.shape != tuple(like):
+            raise ValueError(f"{what} shape {a.shape} does not match the labels' {tuple(like)}")
+        if a.shape != full and not (full[0] == 1 and a.shape == full[1:]):
+            raise ValueError(f"{what} shape {a.shape} does not match the context shape {full}")
+        if a.dtype != dtype and np.dtype(dtype).kind in "iu":
+            _refuse_lossy_cast(a, np.dtype(dtype), what)
+        return np.ascontiguousarray(a, dtype=dtype)
+
+    def network_load(self, labels, skel_mask, frangi):
+        """labels (any integer dtype whose values fit int32), the thinning's mask (bool) and the Frangi frame go up; skel = labels * mask.
+        Returns the largest label."""
+        labels = self._network_frame(labels, "labels", np.int32)
+        mask = np.asarray(skel_mask)
+        if mask.dtype != np.bool_:
+            mask = mask != 0
+        mask = self._network_frame(mask, "skeleton mask", np.bool_, labels.shape).view(np.uint8)
+        frangi = self._network_frame(frangi, "frangi frame", np.float32, labels.shape)
+        self._network_shape = labels.shape
+        n = _i64(0)
+        self._call("nl_network_load", _ptr(labels), _ptr(mask), _ptr(frangi), labels.ndim, C.byref(n))
+        return int(n.value)
+
+    def network_clean_seed(self):
+        """networking.py:261-296 and :342-387 -> (voxels zeroed, labels seeded)."""
+        a, b = _i64(0), _i64(0)
+        self._call("nl_network_clean_seed", C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def network_classes(self):
+        """networking.py:839-847 on the resident skeleton -> (skeleton voxels, branches)."""
+        a, b = _i64(0), _i64(0)
+        self._call("nl_network_classes", C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def network_relabel_load(self, labels, branch):
+        """Step 5 alone: labels and branch labels go up.  Returns the largest label."""
+        labels = self._network_frame(labels, "labels", np.int32)
+        branch = self._network_frame(branch, "branch labels", np.int32, labels.shape)
+        self._network_shape = labels.shape
+        n = _i64(0)
+        self._call("nl_network_relabel_load", _ptr(labels), _ptr(branch), labels.ndim, C.byref(n))
+        return int(n.value)
+
+    def network_relabel(self, spacing, scratch_voxels=None):
+        """networking.py:485-577 -> (objects with a seed, sum of their box volumes, batches)."""
+        sp = np.ascontiguousarray(spacing, dtype=np.float64)
+        if sp.size != len(self._network_shape):
+            raise ValueError(f"spacing needs {len(self._network_shape)} values")
+        a, b, k = _i64(0), _i64(0), _i64(0)
+        self._call("nl_network_relabel", sp.ctypes.data_as(C.POINTER(_f64)), int(scratch_voxels or 0), C.byref(a), C.byref(b), C.byref(k))
+        return int(a.value), int(b.value), int(k.value)
+
+    def network_fetch(self, branch=True, pixel_class=True, relabelled=True):
+        """(branch skeleton labels int32, pixel classes uint8, relabelled uint32), None where not asked for."""
+        shape = self._network_shape
+        s = np.empty(shape, np.int32) if branch else None
+        p = np.empty(shape, np.uint8) if pixel_class else None
+        r = np.empty(shape, np.uint32) if relabelled else None
+        self._call("nl_network_fetch", _opt(s), _opt(p), _opt(r))
+        return s, p, r
+
+    def network_kernel_ms(self):
+        ms = (_f32 * 4)()
+        self._call("nl_network_kernel_ms", ms)
+        return dict(zip(("clean", "seed", "classes", "relabel"), (float(v) for v in ms)))
 
     def set_ndim(self, ndim: int):
         self._call("nl_set_ndim", int(ndim))

@@ -1,10 +1,12 @@
 """
 `run()`: the hot-path half of nellie.run.run (reference nellie/run.py:18-130) -- Filter then Label on the
-MI355X engine, same keyword names, same `timeit` prints.  The later stages (Network, Markers, tracking,
-Hierarchy) are Nellie's own and consume the two files this writes; `markers=True` also runs this package's
+MI355X engine, same keyword names, same `timeit` prints.  The later stages are opt-in: `network=True` runs this
+package's Network (reference run.py:85-86) behind Label and writes im_skel / im_pixel_class / im_skel_relabelled
+(its thinning is the one host call: skimage's, or the `skeletonize` callable); `markers=True` runs this package's
 Markers stage (reference run.py:88-89; it does not depend on Network) and writes im_marker / im_distance /
 im_border; `tracking=True` then runs this package's HuMomentTracking on them (run.py:91-92) and writes
-flow_vector_array.
+flow_vector_array.  Without these keywords the later stages are left to the caller, who finds the two files
+Filter and Label wrote.
 """
 from __future__ import annotations
 
@@ -123,7 +125,7 @@ def run_streamed(im_info, viewer=None, device_index=0, devices=None, shard=None)
 
 
 def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=None, timeit=False, device="auto",
-        low_memory=False, markers=False, devices=None, shard=None, tracking=False):
+        low_memory=False, markers=False, devices=None, shard=None, tracking=False, network=False, skeletonize=None):
     """nellie.run.run's signature (run.py:18-26): `file_info` is a FileInfo (this package's or any object with the same
     fields) from which the ImInfo is built as run.py:49 does; an ImInfo (anything with `pipeline_paths`) or a path / array
     is accepted too.  Returns the ImInfo.
@@ -131,7 +133,12 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
     LOCAL_RANK) of a multi-process Z-slab job over RCCL -- see nellie_amd/engine.py.  Frames beyond one context's size are
     cut into slabs without being asked.
     tracking=True: Hu-moment tracking after Markers; without markers=True it needs Markers' files (im_marker, im_distance)
-    and raises before anything runs if they do not exist."""
+    and raises before anything runs if they do not exist.
+    network=True: Network after Label and before Markers; skeletonize: its thinning, a callable(bool ndarray) -> bool ndarray
+    (None: skimage.morphology.skeletonize, whose absence raises ImportError before anything runs)."""
+    if network and skeletonize is None:
+        from nellie_amd.segmentation.networking import _import_skeletonize
+        _import_skeletonize()
     if hasattr(file_info, "pipeline_paths"):
         im_info = file_info
     else:
@@ -152,6 +159,13 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
     if timeit:
         t2 = time.perf_counter()
         print(f"[timeit] Label: {t2 - t1:.3f}s")
+    if network:
+        from nellie_amd.segmentation.networking import Network
+        Network(im_info, device=device, low_memory=low_memory, skeletonize=skeletonize).run()
+        if timeit:
+            t_net = time.perf_counter()
+            print(f"[timeit] Network: {t_net - t2:.3f}s")
+            t2 = t_net
     if markers:
         from nellie_amd.segmentation.mocap_marking import Markers
         Markers(im_info, device=device, low_memory=low_memory, devices=devices, shard=shard).run()
