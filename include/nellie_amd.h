@@ -786,7 +786,8 @@ int nl_markers_finish(nl_ctx *ctx, int peak_min_distance, int64_t *n_markers, ch
 int nl_markers_store(nl_ctx *ctx, uint8_t *marker, float *distance, uint8_t *border, char *err, size_t errlen);
 
 /* ---- Network stage, the two dense per-voxel steps (nellie/segmentation/networking.py; 3-D volumes and 2-D images) ----
-   The skeletonisation itself (skimage, networking.py:394-409) stays on the host; the rest of the stage is the next block.
+   The skeletonisation itself (skimage, networking.py:394-409) is the last block of this file (3-D) or the caller's (2-D); the rest of
+   the stage is the next block.
    nl_skel_pixel_class  : `_get_pixel_class_impl` (networking.py:672-683) -- skel_mask = skel > 0;
                           class = min(4, convolve(skel_mask, ones(3,3,3), mode="constant", cval=0)) * skel_mask, uint8:
                           1 isolated, 2 tip, 3 edge, 4 junction.  n_skel (may be NULL) = skeleton voxels.
@@ -828,6 +829,27 @@ int nl_network_relabel(nl_ctx *ctx, const double *spacing, int64_t scratch_voxel
                        int64_t *n_batches, char *err, size_t errlen);
 int nl_network_fetch(nl_ctx *ctx, int32_t *branch, uint8_t *pixel_class, uint32_t *relabelled, char *err, size_t errlen);
 int nl_network_kernel_ms(nl_ctx *ctx, float *ms, char *err, size_t errlen);
+
+/* ---- The 3-D thinning (skimage.morphology.skeletonize of a volume: Lee, Kashyap & Chu 1994; networking.py:394-409) ----
+   Whole 3-D volumes of fewer than 2^31 voxels, axes (z, y, x), background outside the frame; ndim != 3 is refused (skimage thins 2-D
+   images by another rule).  The result equals skimage 0.18.3's voxel for voxel, its quirks included: a frame of one plane runs the four
+   in-plane directions only, and the sequential re-check is the component test alone (a solid 6 x 30 x 34 block thins to nothing).
+   rounds_per_sync: rounds of the re-check launched between two read-backs of the counters (<= 0: the default, 8); it changes no result.
+   nl_thin               : stand-alone -- mask (uint8, non-zero = foreground) up, skeleton (uint8, 0 / 1) down.  n_skel may be NULL.
+   nl_network_load_thin  : nl_network_load with the mask thinned on the device from labels > 0: labels and the Frangi frame go up (8
+                           bytes per voxel), no mask.  max_label / n_mask (the mask's voxels) may be NULL.
+   nl_network_fetch_mask : the mask the last nl_network_load_thin or nl_thin left on the context (uint8, 0 / 1).
+   nl_thin_info          : of that thinning, each may be NULL -- counts[7] = foreground voxels in, skeleton voxels out, outer iterations,
+                           sub-iterations, rounds that had work, candidates, voxels removed; ms[1] = its time on the stream, the waits
+                           for the counters included.
+   nl_thin_decide_host   : the kernels' decision functions on the host (no context, no device): flags[i] = bit 0 endpoint, bit 1
+                           Euler-invariant, bit 2 simple of the 27-bit neighbourhood nbhd[i], bit (dz+1)*9 + (dy+1)*3 + (dx+1). */
+int nl_thin(nl_ctx *ctx, const uint8_t *mask, uint8_t *skel, int ndim, int rounds_per_sync, int64_t *n_skel, char *err, size_t errlen);
+int nl_network_load_thin(nl_ctx *ctx, const int32_t *labels, const float *frangi, int ndim, int rounds_per_sync, int64_t *max_label,
+                         int64_t *n_mask, char *err, size_t errlen);
+int nl_network_fetch_mask(nl_ctx *ctx, uint8_t *skel_mask, char *err, size_t errlen);
+int nl_thin_info(nl_ctx *ctx, int64_t *counts, float *ms, char *err, size_t errlen);
+int nl_thin_decide_host(const uint32_t *nbhd, int64_t n, uint8_t *flags);
 
 #ifdef __cplusplus
 }

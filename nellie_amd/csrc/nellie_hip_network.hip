@@ -1,5 +1,6 @@
 // Translation unit of libnellie_hip.so (gfx950): the Network stage behind the thinning (nellie/segmentation/networking.py:828-851).
-// C-ABI in include/nellie_amd.h; kernels in network_relabel.inc; the classes and the branch labels are nellie_label.hip's.  The calls
+// C-ABI in include/nellie_amd.h; kernels in network_relabel.inc; the classes and the branch labels are nellie_label.hip's, the thinning
+// (nl_network_load_thin) is nellie_hip_thin.hip's.  The calls
 // live on the context because that is where the pixel-class and branch-label kernels keep their volumes: one frame goes up
 // (nl_network_load), stays in HBM through clean, seed, classes and relabel, and comes down once (nl_network_fetch).
 //   f[0]  skel = labels * mask, later the relabelled volume     f[2]  pixel classes (uint8)
@@ -14,6 +15,7 @@ void nw_release(nl_ctx *c) {
     for (void *p : {(void *)c->nw_lab, (void *)c->nw_fr, (void *)c->nw_mask, c->nw_tab, (void *)c->nw_feat, (void *)c->nw_stk, c->nw_objs})
         if (p) hipFree(p);
     for (hipEvent_t e : c->nw_ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->thin_ev) if (e) hipEventDestroy(e);
 }
 
 static inline unsigned long long *nw_best(nl_ctx *c) { return (unsigned long long *)c->nw_tab; }
@@ -42,6 +44,7 @@ static int nw_begin(nl_ctx *c, char *err, size_t errlen) {
     if (!c->nw_lab) NL_HIP(hipMalloc((void **)&c->nw_lab, (size_t)c->n * 4));
     c->nw_stage = 0;
     c->nw_has_classes = 0;
+    c->thin_valid = 0;
     for (float &m : c->nw_ms) m = 0.f;
     // the frame takes over the four volumes and the mask planes
     c->i_labels = -1; c->frangi_ready = 0; c->gauss_ext = nullptr; c->fsq_cache_valid = 0; c->mk_state = 0; c->nw_state = 0;
@@ -104,6 +107,33 @@ extern "C" int nl_network_load(nl_ctx *c, const int32_t *labels, const uint8_t *
     nw_skel_kernel<<<grid1d(c->n, 256, 2048), 256, 0, st>>>(c->nw_lab, c->nw_mask, (int *)c->f[0], c->n, d_stats);
     NL_CHECK_LAUNCH();
     if (int rc = nw_labels_done(c, max_label, err, errlen)) return rc;
+    c->nw_stage = 1;
+    return NL_OK;
+}
+
+// Step 1 with the thinning on the device (networking.py:394-409): labels and the Frangi frame go up, the mask is the thinning of
+// labels > 0 (thin.inc; 3-D frames only), then skel = labels * mask as above.  n_mask (may be NULL) = the mask's voxels.
+extern "C" int nl_network_load_thin(nl_ctx *c, const int32_t *labels, const float *frangi, int ndim, int rounds_per_sync, int64_t *max_label,
+                                    int64_t *n_mask, char *err, size_t errlen) {
+    NL_ENTER(c);
+    NL_JOIN_SIDE(c);
+    if (!labels || !frangi) return nl_fail(err, errlen, NL_EINVAL, "nl_network_load_thin: NULL labels or frangi");
+    if (ndim != 3) return nl_fail(err, errlen, NL_EINVAL, "the thinning on the device is the 3-D one: ndim = %d is not supported (thin 2-D frames on the host)", ndim);
+    if (int rc = nw_check(c, ndim, err, errlen)) return rc;
+    if (int rc = nw_begin(c, err, errlen)) return rc;
+    if (!c->nw_fr) NL_HIP(hipMalloc((void **)&c->nw_fr, (size_t)c->n * 4));
+    if (!c->nw_mask) NL_HIP(hipMalloc((void **)&c->nw_mask, (size_t)c->n));
+    c->nw_ndim = ndim;
+    hipStream_t st = c->stream;
+    NL_HIP(hipMemcpyAsync(c->nw_lab, labels, (size_t)c->n * 4, hipMemcpyHostToDevice, st));
+    NL_HIP(hipMemcpyAsync(c->nw_fr, frangi, (size_t)c->n * 4, hipMemcpyHostToDevice, st));
+    if (int rc = thin_device(c, c->nw_lab, rounds_per_sync, err, errlen)) return rc;
+    int *d_stats = (int *)c->d_small + 8;
+    NL_HIP(zero_small(d_stats, 8, st));
+    nw_skel_kernel<<<grid1d(c->n, 256, 2048), 256, 0, st>>>(c->nw_lab, c->nw_mask, (int *)c->f[0], c->n, d_stats);
+    NL_CHECK_LAUNCH();
+    if (int rc = nw_labels_done(c, max_label, err, errlen)) return rc;
+    if (n_mask) *n_mask = c->thin_counts[1];
     c->nw_stage = 1;
     return NL_OK;
 }

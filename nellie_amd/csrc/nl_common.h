@@ -62,6 +62,11 @@ struct nl_ctx {
     void *nw_objs = nullptr; i64 nw_objs_cap = 0;                                  // the frame's NwObj table
     hipEvent_t nw_ev[2] = {nullptr, nullptr};
     float nw_ms[4] = {0, 0, 0, 0};                                                 // clean, seed, classes, relabel
+    // the thinning (nellie_hip_thin.hip): nw_mask is its working image and, afterwards, the skeleton mask
+    int thin_valid = 0;                                                            // nw_mask holds a thinning's result
+    i64 thin_counts[7] = {0, 0, 0, 0, 0, 0, 0};                                    // n_in, n_out, outer, subiters, rounds, candidates, removed
+    float thin_ms = 0;
+    hipEvent_t thin_ev[2] = {nullptr, nullptr};
     const float *mk_int = nullptr;   // Markers: the float32 intensities when they are read in place (a resident float32 input), else they live in d_vq
     float *mk_use = nullptr;      // Markers: LoG source when use_im = 'frangi' (inside d_vq), else the distance image
     float *mk_scratch = nullptr;  // Markers: volume between the Y and the X pass of the any-radius LoG path, allocated on first use

@@ -6,6 +6,7 @@
 //   nellie_label.hip    Label / Network / streaming                                             -> nl_launch_threshold_pack
 //   nellie_markers.hip  Markers                                                                 -> nl_launch_pack_labels
 //   nellie_hip_network.hip  Network behind the thinning (clean, seed, per-object relabel)        -> nw_release
+//   nellie_hip_thin.hip     the 3-D thinning (Lee94 as skimage runs it)                           -> thin_device
 //   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the six stage handles share nl_stage.h.
 // gfx950 only.
 #pragma once
@@ -199,6 +200,11 @@ int nw_pixel_class_resident(nl_ctx *c, uint8_t *pixel_class_host, int64_t *n_ske
 
 // ---- defined in nellie_hip_network.hip -----------------------------------------------------------------------------------
 void nw_release(nl_ctx *c);                              // the Network stage's own buffers and events (nl_ctx_destroy)
+
+// ---- defined in nellie_hip_thin.hip ---------------------------------------------------------------------------------------
+// Thins c->nw_mask in place on the context's stream (3-D frames; f[0..3] are its work lists and state).  labels != NULL: the image is
+// first made from labels > 0 (device pointer); else nw_mask holds it, any non-zero byte foreground.  Leaves thin_counts / thin_ms.
+int thin_device(nl_ctx *c, const int *labels, int rounds_per_sync, char *err, size_t errlen);
 
 // ---- kernels of one unit launched from another ---------------------------------------------------------------------------
 void nl_launch_threshold_pack(unsigned int grid, hipStream_t st, const float *f, const unsigned long long *support, unsigned long long *bits,

@@ -91,6 +91,10 @@ _PROTOS = {
     "nl_network_relabel": [_p, C.POINTER(_f64), _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "nl_network_fetch": [_p, _p, _p, _p],
     "nl_network_kernel_ms": [_p, C.POINTER(_f32)],
+    "nl_thin": [_p, _p, _p, _int, _int, C.POINTER(_i64)],
+    "nl_network_load_thin": [_p, _p, _p, _int, _int, C.POINTER(_i64), C.POINTER(_i64)],
+    "nl_network_fetch_mask": [_p, _p],
+    "nl_thin_info": [_p, C.POINTER(_i64), C.POINTER(_f32)],
     "nl_mask_volume_fused": [_p, _f32, C.POINTER(_i64)],
     "nl_log2d_step": [_p, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), _int, _f32, _int, _int],
     "nl_log2d_finish": [_p, C.POINTER(_i64)],
@@ -208,6 +212,7 @@ _PLAIN = {
     "nl_voxfeat_destroy": (_int, [_p]),
     "nl_nodefeat_destroy": (_int, [_p]),
     "nl_branchfeat_destroy": (_int, [_p]),
+    "nl_thin_decide_host": (_int, [_p, _i64, _p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
 
@@ -311,6 +316,17 @@ def hist_thresholds(counts, edges, with_variance=False):
     if with_variance:
         return out_t(tri.value), out_t(otsu.value), np.float64(var.value)
     return out_t(tri.value), out_t(otsu.value)
+
+
+def thin_decide_host(words):
+    """The thinning kernels' decision functions on the host (nl_thin_decide_host): uint8 flags per 27-bit neighbourhood word, bit 0
+    endpoint, bit 1 Euler-invariant, bit 2 simple.  Needs the library, no device."""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+    flags = np.zeros(w.size, np.uint8)
+    rc = load().cdll.nl_thin_decide_host(_ptr(w), int(w.size), _ptr(flags))
+    if rc != NL_OK:
+        raise ValueError("nl_thin_decide_host refused its arguments")
+    return flags
 
 
 def host_hist_thresholds(values, nbins=256, with_histogram=False):
@@ -825,6 +841,40 @@ class Context(_Handle):
         n = _i64(0)
         self._call("nl_network_load", _ptr(labels), _ptr(mask), _ptr(frangi), labels.ndim, C.byref(n))
         return int(n.value)
+
+    THIN_COUNTS = ("n_in", "n_out", "outer", "subiters", "rounds", "candidates", "removed")
+
+    def network_load_thin(self, labels, frangi, rounds_per_sync=None):
+        """network_load with the mask thinned on the device from labels > 0 (3-D frames).  Returns the largest label."""
+        labels = self._network_frame(labels, "labels", np.int32)
+        if labels.ndim != 3:
+            raise NotImplementedError("the thinning on the device is the 3-D one")
+        frangi = self._network_frame(frangi, "frangi frame", np.float32, labels.shape)
+        self._network_shape = labels.shape
+        n, k = _i64(0), _i64(0)
+        self._call("nl_network_load_thin", _ptr(labels), _ptr(frangi), labels.ndim, int(rounds_per_sync or 0), C.byref(n), C.byref(k))
+        return int(n.value)
+
+    def thin(self, mask, rounds_per_sync=None):
+        """The 3-D thinning of a bool volume of the context's shape -> bool skeleton (skimage.morphology.skeletonize(mask) > 0)."""
+        mask = self._network_frame(mask, "mask", np.bool_)
+        if mask.ndim != 3:
+            raise NotImplementedError("the thinning on the device is the 3-D one")
+        out = np.empty(mask.shape, np.bool_)
+        self._call("nl_thin", _ptr(mask.view(np.uint8)), _ptr(out.view(np.uint8)), 3, int(rounds_per_sync or 0), None)
+        return out
+
+    def network_fetch_mask(self, shape=None):
+        """The mask the last thinning on this context left (bool)."""
+        out = np.empty(tuple(int(s) for s in self.shape) if shape is None else shape, np.bool_)
+        self._call("nl_network_fetch_mask", _ptr(out.view(np.uint8)))
+        return out
+
+    def thin_info(self):
+        """(dict of the last thinning's seven counts, its stream time in ms)."""
+        counts, ms = (_i64 * 7)(), (_f32 * 1)()
+        self._call("nl_thin_info", counts, ms)
+        return dict(zip(self.THIN_COUNTS, (int(v) for v in counts))), float(ms[0])
 
     def network_clean_seed(self):
         """networking.py:261-296 and :342-387 -> (voxels zeroed, labels seeded)."""

@@ -2,7 +2,7 @@
 `run()`: the hot-path half of nellie.run.run (reference nellie/run.py:18-130) -- Filter then Label on the
 MI355X engine, same keyword names, same `timeit` prints.  The later stages are opt-in: `network=True` runs this
 package's Network (reference run.py:85-86) behind Label and writes im_skel / im_pixel_class / im_skel_relabelled
-(its thinning is the one host call: skimage's, or the `skeletonize` callable); `markers=True` runs this package's
+(its thinning is the one host call: skimage's, or the `skeletonize` callable -- or none with skeletonize="hip"); `markers=True` runs this package's
 Markers stage (reference run.py:88-89; it does not depend on Network) and writes im_marker / im_distance /
 im_border; `tracking=True` then runs this package's HuMomentTracking on them (run.py:91-92) and writes
 flow_vector_array.  Without these keywords the later stages are left to the caller, who finds the two files
@@ -135,14 +135,20 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
     tracking=True: Hu-moment tracking after Markers; without markers=True it needs Markers' files (im_marker, im_distance)
     and raises before anything runs if they do not exist.
     network=True: Network after Label and before Markers; skeletonize: its thinning, a callable(bool ndarray) -> bool ndarray
-    (None: skimage.morphology.skeletonize, whose absence raises ImportError before anything runs)."""
+    (None: skimage.morphology.skeletonize, whose absence raises ImportError before anything runs), or "hip": the 3-D thinning on the
+    device (NotImplementedError for a 2-D image, before any stage runs)."""
     if network and skeletonize is None:
         from nellie_amd.segmentation.networking import _import_skeletonize
         _import_skeletonize()
+    elif network:
+        from nellie_amd.segmentation.networking import _check_thinning
+        _check_thinning(skeletonize, file_info)         # an unknown name, or "hip" where `file_info` already says 2-D: before anything runs
     if hasattr(file_info, "pipeline_paths"):
         im_info = file_info
     else:
         im_info = _build_im_info(file_info, shard)
+        if network:
+            _check_thinning(skeletonize, im_info)      # a path or an array: known only now, still before any stage
     if tracking and not markers:
         missing = [k for k in ("im_marker", "im_distance") if not os.path.exists(im_info.pipeline_paths[k])]
         if missing:

@@ -1,10 +1,11 @@
 """
-nellie.segmentation.networking.Network on the MI355X HIP engine: everything behind the thinning.
+nellie.segmentation.networking.Network on the MI355X HIP engine.
 
 `Network` is the stage: it reads im_instance_label and im_preprocessed and writes im_skel, im_pixel_class and im_skel_relabelled, as the
-reference's class of the same name does (networking.py:828-851, :902-931).  Per frame the one host call is the thinning itself
+reference's class of the same name does (networking.py:828-851, :902-931).  By default the one host call per frame is the thinning
 (`skimage.morphology.skeletonize`, networking.py:394-409, or the `skeletonize` callable given); labels, thinning mask and Frangi frame
-then go up once, and on the device
+then go up once.  With skeletonize="hip" (3-D frames) the thinning runs on the device too (segmentation/thinning.py, csrc/thin.inc):
+labels and Frangi frame go up, no mask, and nothing of skimage is imported.  On the device
 
   skel    = labels * mask                                                                    (:408)
   clean   `_remove_connected_label_pixels` (:261-296)
@@ -131,6 +132,20 @@ def relabel_objects(branch_skel_labels, label_frame, scaling, scratch_voxels=Non
         return ctx.network_fetch(branch=False, pixel_class=False)[2]
 
 
+HIP_THINNING = "hip"
+
+
+def _check_thinning(skeletonize, im_info):
+    """The `skeletonize` keyword, judged before any file is created: None (skimage's), a callable, or "hip" on a 3-D im_info."""
+    if skeletonize is None or callable(skeletonize):
+        return
+    if not isinstance(skeletonize, str) or skeletonize != HIP_THINNING:
+        raise ValueError(f"skeletonize={skeletonize!r}: expected None (skimage.morphology.skeletonize), a callable or {HIP_THINNING!r}")
+    if getattr(im_info, "no_z", False):
+        raise NotImplementedError("skeletonize='hip' is the 3-D thinning: for a 2-D image skimage runs another rule, which is not "
+                                  "provided on the device -- pass skeletonize=None (skimage's) or a callable")
+
+
 def _import_skeletonize():
     try:
         from skimage.morphology import skeletonize
@@ -148,14 +163,19 @@ class Network:
                                    equal the whole-frame ones; here a frame is always processed whole on the device, and the
                                    per-object thinning of low_memory is not provided.
     skeletonize                    callable(mask: bool ndarray) -> bool ndarray of the same shape; None: skimage.morphology.skeletonize,
-                                   imported when run() starts (ImportError, naming this keyword, before any file is created).
+                                   imported when run() starts (ImportError, naming this keyword, before any file is created); "hip":
+                                   the 3-D thinning on the device, skimage's result voxel for voxel (NotImplementedError on a 2-D
+                                   im_info, before any file is created).
+    rounds_per_sync                "hip" only: rounds of the thinning's re-check launched between two read-backs (None: the library's
+                                   default); it changes no result.
     scratch_voxels                 box voxels one batch of the relabelling may hold (8 bytes each); None: half of the free HBM.  Never less
                                    than one frame.
-    `kernel_ms` holds one dict per frame of the last run: clean, seed, classes, relabel (ms on the stream, transfers excluded).
+    `kernel_ms` holds one dict per frame of the last run: clean, seed, classes, relabel (ms on the stream, transfers excluded), and
+    "thin" in "hip" mode, where `frame_stats` also gains the thinning's seven counts as thin_*.
     """
 
     def __init__(self, im_info, num_t=None, min_radius_um=0.20, max_radius_um=1, viewer=None, device="auto", low_memory: bool = False,
-                 max_chunk_voxels: int = int(1e6), device_index=0, skeletonize=None, scratch_voxels=None):
+                 max_chunk_voxels: int = int(1e6), device_index=0, skeletonize=None, scratch_voxels=None, rounds_per_sync=None):
         self.im_info = im_info
         self.device = device
         self.device_type = resolve_device(device)
@@ -174,11 +194,13 @@ class Network:
         self.scaling = spacing_of(im_info)
         self.skeletonize = skeletonize
         self.scratch_voxels = scratch_voxels
+        self.rounds_per_sync = rounds_per_sync
         self.shape = ()
         self.im_frangi_memmap = self.label_memmap = self.pixel_class_memmap = self.skel_memmap = self.skel_relabelled_memmap = None
         self.viewer = viewer
         self.kernel_ms = []
         self.frame_stats = []                # per frame: max_label, n_removed, n_seeded, n_skel, n_branches, n_objects, box_volume, n_batches
+                                             # ("hip" thinning: and thin_n_in, thin_n_out, thin_outer, thin_subiters, thin_rounds, ...)
         self._held = Held()
         self._thin = None                    # the thinning in use: `skeletonize`, or skimage's once it has been imported
 
@@ -213,18 +235,27 @@ class Network:
             raise ValueError(f"expected a {len(self.scaling)}-D frame, got shape {labels.shape}")
         if frangi.shape != labels.shape:
             raise ValueError(f"frangi frame shape {frangi.shape} does not match the labels' {labels.shape}")
-        if skel_mask is None:
+        on_device = skel_mask is None and isinstance(self.skeletonize, str)
+        if on_device:
+            _check_thinning(self.skeletonize, self.im_info)
+        elif skel_mask is None:
             if self._thin is None:
                 self._thin = self.skeletonize or _import_skeletonize()
             skel_mask = self._skeleton_mask(labels)
         key = (_ctx_shape(labels.shape), self.device_index)
         ctx = self._held.get(key, lambda: hipnative.Context(key[0], device=key[1]))
-        stats = dict(max_label=ctx.network_load(labels, skel_mask, frangi))
+        thin_ms = None
+        if on_device:
+            stats = dict(max_label=ctx.network_load_thin(labels, frangi, self.rounds_per_sync))
+            counts, thin_ms = ctx.thin_info()
+            stats.update(("thin_" + k, v) for k, v in counts.items())
+        else:
+            stats = dict(max_label=ctx.network_load(labels, skel_mask, frangi))
         stats["n_removed"], stats["n_seeded"] = ctx.network_clean_seed()
         stats["n_skel"], stats["n_branches"] = ctx.network_classes()
         stats["n_objects"], stats["box_volume"], stats["n_batches"] = ctx.network_relabel(self.scaling, self.scratch_voxels)
         out = ctx.network_fetch()
-        self.kernel_ms.append(ctx.network_kernel_ms())
+        self.kernel_ms.append(ctx.network_kernel_ms() if thin_ms is None else dict(ctx.network_kernel_ms(), thin=thin_ms))
         self.frame_stats.append(stats)
         return out
 
@@ -249,7 +280,8 @@ class Network:
 
     def run(self):
         logger.info("Running Network (HIP).")
-        self._thin = self.skeletonize or _import_skeletonize()          # before any file exists
+        _check_thinning(self.skeletonize, self.im_info)                 # before any file exists, like the import
+        self._thin = None if isinstance(self.skeletonize, str) else self.skeletonize or _import_skeletonize()
         require_gpu()
         self._get_t()
         self._allocate_memory()

@@ -8,7 +8,15 @@ Times include the H2D of the int32 skeleton and the D2H of both products (the C-
 The whole stage behind the thinning on one synthetic N^3 frame (default 256) of dilated random walks, the walks standing in for the
 thinning: wall time through Network._run_frame (upload, the five steps, download) and the per-step stream times, best of three;
 then, unless --no-host, the reference's per-object relabelling loop (find_objects + scipy's distance_transform_edt per object,
-networking.py:485-577) on the same frame and host, once, and whether the two relabelled volumes are equal."""
+networking.py:485-577) on the same frame and host, once, and whether the two relabelled volumes are equal.
+
+    python tools/bench_network.py --frame [N] --thin hip [--rounds-per-sync R] [--dump-skel FILE.npy]
+The same frame with the thinning on the device (Network(skeletonize="hip")): the mask is the thinning of labels > 0, not the walks.
+Reports kernel_ms["thin"], the thinning's seven counts and the wall time of _run_frame, best of three; --dump-skel saves the device's
+mask.
+    python tools/bench_network.py --frame [N] --dump-mask FILE.npy
+Saves labels > 0 of that frame and stops (needs no device), so that skimage.morphology.skeletonize can be timed on the same mask by an
+interpreter that has it, and its result compared with --dump-skel's."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -57,14 +65,47 @@ def host_relabel(branch, labels, scaling):
     return out, n_obj, vol
 
 
+def bench_thin(argv, n, walks, labels, frangi, info):
+    from nellie_amd.segmentation.networking import Network
+    how = argv[argv.index("--thin") + 1]
+    rps = int(argv[argv.index("--rounds-per-sync") + 1]) if "--rounds-per-sync" in argv else None
+    net = Network(info, skeletonize=how, rounds_per_sync=rps)
+    net.num_t = 1
+    net.label_memmap, net.im_frangi_memmap = labels[None], frangi[None]
+    wall = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        net._run_frame(0)
+        wall.append(time.perf_counter() - t0)
+    best = min(range(3), key=lambda k: net.kernel_ms[k]["thin"])
+    stats = net.frame_stats[best]
+    res = {"frame": [n, n, n], "walks": walks, "thin": how, "rounds_per_sync": rps, "labels": int(labels.max()),
+           "thin_ms_best": round(net.kernel_ms[best]["thin"], 3), "thin_ms_all": [round(k["thin"], 3) for k in net.kernel_ms],
+           **{k: v for k, v in stats.items() if k.startswith("thin_")},
+           "kernel_ms_best_thin_run": {k: round(v, 3) for k, v in net.kernel_ms[best].items()},
+           "wall_ms_best": round(min(wall) * 1e3, 2), "wall_ms_all": [round(w * 1e3, 2) for w in wall],
+           **{k: v for k, v in stats.items() if not k.startswith("thin_")},
+           "note": "wall: Network._run_frame, thinning on the device; includes H2D of 8 B/voxel and D2H of 9 B/voxel, pageable"}
+    if "--dump-skel" in argv:
+        np.save(argv[argv.index("--dump-skel") + 1], net._held.obj.network_fetch_mask(labels.shape))
+    net.close()
+    print(json.dumps(res))
+
+
 def bench_frame(argv):
     from types import SimpleNamespace
     from nellie_amd.segmentation.networking import Network
     n = int(argv[argv.index("--frame") + 1]) if len(argv) > argv.index("--frame") + 1 and argv[argv.index("--frame") + 1].isdigit() else 256
     walks = int(argv[argv.index("--walks") + 1]) if "--walks" in argv else max(4, n * n * n // 40000)
     labels, line, frangi = walks_frame(n, walks)
+    if "--dump-mask" in argv:
+        np.save(argv[argv.index("--dump-mask") + 1], labels > 0)
+        print(json.dumps({"frame": [n, n, n], "walks": walks, "foreground": int((labels > 0).sum()), "saved": argv[argv.index("--dump-mask") + 1]}))
+        return
     scaling = (0.29, 0.11, 0.11)
     info = SimpleNamespace(no_t=True, no_z=False, shape=(1, n, n, n), axes="TZYX", dim_res=dict(zip("ZYX", scaling), T=1.0))
+    if "--thin" in argv:
+        return bench_thin(argv, n, walks, labels, frangi, info)
     net = Network(info, skeletonize=lambda mask: line)
     net.num_t = 1
     net.label_memmap, net.im_frangi_memmap = labels[None], frangi[None]
