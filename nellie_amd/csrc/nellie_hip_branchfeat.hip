@@ -84,14 +84,6 @@ extern "C" int nl_branchfeat_create(nl_branchfeat **out, int device, int ndim, i
 static bool bf_label_dtype(int dt) { return dtype_size(dt) && dt != NL_F32 && dt != NL_F64; }
 static unsigned bf_grid(i64 n) { return (unsigned)((n + 255) / 256); }
 
-// `count` elements of `size` bytes from the host into *buf, grown when it is too small
-static int bf_upload(nl_branchfeat *h, void **buf, i64 *cap, const void *host, i64 count, size_t size, char *err, size_t errlen) {
-    const i64 bytes = count * (i64)size;
-    if (int rc = stage_grow(cap, bytes, bytes, {{buf, 1}}, err, errlen)) return rc;
-    if (bytes > 0) NL_HIP(hipMemcpyAsync(*buf, host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
-    return NL_OK;
-}
-
 // the scan's workgroup sums hold a scan of `longest` counts afterwards
 static int bf_scan_reserve(nl_branchfeat *h, i64 longest, char *err, size_t errlen) {
     const i64 need = rank_scan_sums(longest);
@@ -188,7 +180,7 @@ extern "C" int nl_branchfeat_frame(nl_branchfeat *h, const void *skel, int skel_
     *n_voxels = *n_labels = *n_tips = *n_lone = 0;
     for (int j = BF_MS_LIST; j <= BF_MS_LISTS; ++j) h->ms[j] = 0.f;
     // ---- the list, its labels and their ranks
-    if (int rc = bf_upload(h, &h->d_lab, &h->lab_cap, skel, n, ss, err, errlen)) return rc;
+    if (int rc = stage_upload(*h, &h->d_lab, &h->lab_cap, skel, n, ss, err, errlen)) return rc;
     if (int rc = bf_scan_reserve(h, h->words, err, errlen)) return rc;
     if (int rc = stage_start(*h, err, errlen)) return rc;
     rank_mask_kernel<<<bf_grid(n), 256, 0, st>>>(BfPositive{h->d_lab, skel_dtype}, n, h->sbits, h->d_wcount);
@@ -225,13 +217,13 @@ extern "C" int nl_branchfeat_frame(nl_branchfeat *h, const void *skel, int skel_
         NL_CHECK_LAUNCH();
         if (int rc = stage_stop(*h, &h->ms[BF_MS_DEGREE], err, errlen)) return rc;
         // ---- the component label at every label's first voxel
-        if (int rc = bf_upload(h, &h->d_in, &h->in_cap, comp, n, cs, err, errlen)) return rc;
+        if (int rc = stage_upload(*h, &h->d_in, &h->in_cap, comp, n, cs, err, errlen)) return rc;
         if (int rc = stage_start(*h, err, errlen)) return rc;
         nf_gather_kernel<<<bf_grid(B), 256, 0, st>>>(h->d_in, (int)cs, h->first_vox, B, h->comp_l);
         NL_CHECK_LAUNCH();
         if (int rc = stage_stop(*h, &h->ms[BF_MS_LIST], err, errlen)) return rc;
         // ---- radii
-        if (int rc = bf_upload(h, &h->d_in, &h->in_cap, border, n, os, err, errlen)) return rc;
+        if (int rc = stage_upload(*h, &h->d_in, &h->in_cap, border, n, os, err, errlen)) return rc;
         NL_HIP(hipMemsetAsync(h->d_any, 0, 4, st));
         if (int rc = stage_start(*h, err, errlen)) return rc;
         nf_border_kernel<<<bf_grid(n), 256, 0, st>>>(NfSet{h->d_in, border_dtype, false}, n, h->bbits, h->d_any);
@@ -318,7 +310,7 @@ static int bf_regions(nl_branchfeat *h, bool rows, const void *labels, int dtype
     h->R = 0;
     *n_regions = 0;
     h->ms[BF_MS_REGIONS] = 0.f;
-    if (int rc = bf_upload(h, &h->d_lab, &h->lab_cap, labels, n, ls, err, errlen)) return rc;
+    if (int rc = stage_upload(*h, &h->d_lab, &h->lab_cap, labels, n, ls, err, errlen)) return rc;
     if (int rc = stage_start(*h, err, errlen)) return rc;
     const BfLabels lab{h->d_lab, dtype, nullptr};
     i64 R = 0;
@@ -345,7 +337,7 @@ static int bf_regions(nl_branchfeat *h, bool rows, const void *labels, int dtype
     if (reassigned && R > 0) {
         const i64 P = bf_pow2(total);
         if (int rc = stage_grow(&h->keys_cap, P, P, {{&h->keys, 8}}, err, errlen)) return rc;
-        if (int rc = bf_upload(h, &h->d_in, &h->in_cap, reassigned, n, rs, err, errlen)) return rc;
+        if (int rc = stage_upload(*h, &h->d_in, &h->in_cap, reassigned, n, rs, err, errlen)) return rc;
         NL_HIP(hipMemsetAsync(h->keys, 0xff, (size_t)P * 8, st));     // above every key
         NL_HIP(hipMemsetAsync(h->d_word, 0, 8, st));
         NL_HIP(hipMemsetAsync(h->d_any + 1, 0, 4, st));

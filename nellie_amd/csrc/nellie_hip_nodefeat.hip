@@ -70,14 +70,6 @@ extern "C" int nl_nodefeat_create(nl_nodefeat **out, int device, int ndim, int64
     return NL_OK;
 }
 
-// `count` elements of `size` bytes from the host into the staging buffer, grown when it is too small
-static int nf_upload(nl_nodefeat *h, const void *host, i64 count, size_t size, char *err, size_t errlen) {
-    const i64 bytes = count * (i64)size;
-    if (int rc = stage_grow(&h->in_cap, bytes, bytes, {{&h->d_in, 1}}, err, errlen)) return rc;
-    if (bytes > 0) NL_HIP(hipMemcpyAsync(h->d_in, host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
-    return NL_OK;
-}
-
 // A frame: pixel class, component labels, branch labels and border mask of the object's shape, each in its own dtype (NL_U8 ..
 // NL_I64).  The voxels with pixel class > 0 become the nodes, in raster order; their two labels are gathered and their thickness
 // (twice the distance in um to the nearest voxel with border != 0, NaN in a frame without one) is computed.  n_nodes = their number.
@@ -94,7 +86,7 @@ extern "C" int nl_nodefeat_frame(nl_nodefeat *h, const void *pixel_class, int cl
     *n_nodes = 0;
     h->ms[NF_MS_LIST] = h->ms[NF_MS_THICKNESS] = h->ms[NF_MS_STATS] = 0.f;
     const unsigned gv = (unsigned)((n + 255) / 256);
-    if (int rc = nf_upload(h, pixel_class, n, ps, err, errlen)) return rc;
+    if (int rc = stage_upload(*h, &h->d_in, &h->in_cap, pixel_class, n, ps, err, errlen)) return rc;
     if (int rc = stage_start(*h, err, errlen)) return rc;
     rank_mask_kernel<<<gv, 256, 0, st>>>(NfSet{h->d_in, class_dtype, true}, n, h->nbits, h->d_wcount);
     NL_CHECK_LAUNCH();
@@ -113,14 +105,14 @@ extern "C" int nl_nodefeat_frame(nl_nodefeat *h, const void *pixel_class, int cl
     const size_t sizes[2] = {cs, bs};
     void *dst[2] = {h->lab_c, h->lab_b};
     for (int f = 0; f < 2 && m > 0; ++f) {
-        if (int rc = nf_upload(h, frames[f], n, sizes[f], err, errlen)) return rc;
+        if (int rc = stage_upload(*h, &h->d_in, &h->in_cap, frames[f], n, sizes[f], err, errlen)) return rc;
         if (int rc = stage_start(*h, err, errlen)) return rc;
         nf_gather_kernel<<<gm, 256, 0, st>>>(h->d_in, (int)sizes[f], h->node_vox, m, dst[f]);
         NL_CHECK_LAUNCH();
         if (int rc = stage_stop(*h, &h->ms[NF_MS_LIST], err, errlen)) return rc;
     }
     if (m > 0) {
-        if (int rc = nf_upload(h, border, n, os, err, errlen)) return rc;
+        if (int rc = stage_upload(*h, &h->d_in, &h->in_cap, border, n, os, err, errlen)) return rc;
         NL_HIP(hipMemsetAsync(h->d_any, 0, 4, st));
         if (int rc = stage_start(*h, err, errlen)) return rc;
         nf_border_kernel<<<gv, 256, 0, st>>>(NfSet{h->d_in, border_dtype, false}, n, h->bbits, h->d_any);
@@ -245,7 +237,7 @@ extern "C" int nl_nodefeat_aggregate(nl_nodefeat *h, const void *values, int dty
     if (h->idx_max >= n_values) return nl_fail(err, errlen, NL_EINVAL, "index %lld in a group, but %lld values", (long long)h->idx_max, (long long)n_values);
     if (h->groups == 0) return NL_OK;
     hipStream_t st = h->stream;
-    if (int rc = nf_upload(h, values, n_values, vs, err, errlen)) return rc;
+    if (int rc = stage_upload(*h, &h->d_in, &h->in_cap, values, n_values, vs, err, errlen)) return rc;
     if (int rc = stage_start(*h, err, errlen)) return rc;
     const i64 wide_from = h->n_wide > 0 ? h->listed_from : 0;          // the threshold the loaded groups were listed under
     nf_aggregate_kernel<<<(unsigned)h->groups, 64, 0, st>>>(h->d_in, dtype, n_values, h->d_off, h->d_idx, h->groups, (int)h->L, wide_from, h->d_scratch,

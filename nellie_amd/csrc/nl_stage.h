@@ -109,6 +109,14 @@ static inline int stage_grow(i64 *cap, i64 need, i64 new_cap, std::initializer_l
 }
 static inline i64 stage_doubled(i64 cap, i64 need) { return need > 2 * cap ? need : 2 * cap; }
 
+// `count` elements of `size` bytes from the host into *buf (capacity *cap, bytes), grown when it is too small; on the handle's stream
+static inline int stage_upload(StageBase &b, void **buf, i64 *cap, const void *host, i64 count, size_t size, char *err, size_t errlen) {
+    const i64 bytes = count * (i64)size;
+    if (int rc = stage_grow(cap, bytes, bytes, {{buf, 1}}, err, errlen)) return rc;
+    if (bytes > 0) NL_HIP(hipMemcpyAsync(*buf, host, (size_t)bytes, hipMemcpyHostToDevice, b.stream));
+    return NL_OK;
+}
+
 // ---- kernel timing ---------------------------------------------------------------------------------------------------------------
 // stage_start .. stage_stop around kernels: the device time between them is added to *ms.  stage_stop synchronises the stream; a
 // caller that enqueues copies behind the kernels calls its two halves, stage_stop_record before them and stage_stop_wait after.

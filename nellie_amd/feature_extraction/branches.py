@@ -21,14 +21,11 @@ accepted and ignored.  There is no CPU engine behind these classes (`device="cpu
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
-from nellie_amd.feature_extraction.nodes import NodeFeatures, _aggregate
+from nellie_amd.feature_extraction.hierarchy import Level
+from nellie_amd.feature_extraction.nodes import NodeFeatures, aggregate_groups
 from nellie_amd.feature_extraction.voxels import _image_name
-from nellie_amd.stage import require_gpu
-from nellie_amd.utils.base_logger import logger
 
 SKELETON_STATS = ("branch_length", "branch_thickness", "branch_aspect_ratio", "branch_tortuosity")
 REGION_STATS = ("branch_area", "branch_axis_length_maj", "branch_axis_length_min", "branch_extent", "branch_solidity", "reassigned_label", "z", "y", "x")
@@ -158,7 +155,11 @@ def region_columns(sums, mode, spacing, D, prefix="branch"):
     return out
 
 
-class Branches:
+class Branches(Level):
+    word, name, table_key, label_list = "branch", "branches", "features_branches", "branch_label"
+    handles = ("_engine", "_aggregator")
+    reads_reassigned = True
+
     def __init__(self, hierarchy):
         self.hierarchy = hierarchy
         self.time = []
@@ -189,22 +190,9 @@ class Branches:
         self._engine = None
         self._aggregator = None
 
-    def close(self):
-        for name in ("_engine", "_aggregator"):
-            if getattr(self, name) is not None:
-                getattr(self, name).close()
-                setattr(self, name, None)
-
     def _aggregate(self, child, labels, t):
         """the reference's dict of dicts of `child`'s statistics over the groups of equal non-zero `labels`, and the device time"""
-        off, idx = _label_groups(labels)
-        for name in child.stats_to_aggregate:
-            values = np.asarray(getattr(child, name)[t]) if name != "reassigned_label" else None
-            if values is not None and values.ndim == 1 and len(values) != np.size(labels):
-                raise ValueError(f"frame {t}: {name} has {len(values)} values for {np.size(labels)} branch labels")
-        self._aggregator.groups(off, idx)
-        out = _aggregate(self._aggregator, child, t)
-        return out, self._aggregator.kernel_ms_parts()["aggregation"]
+        return aggregate_groups(self._aggregator, child, t, *_label_groups(labels), np.size(labels), "branch labels")
 
     def _run_frame(self, t):
         h, eng = self.hierarchy, self._engine
@@ -245,87 +233,16 @@ class Branches:
         self.region_label.append(labels)
         self.kernel_ms.append(dict(eng.kernel_ms_parts(), aggregation=ms))
 
-    def run(self):
+    def _open(self, device):
         from nellie_amd import hipnative
         h = self.hierarchy
-        require_gpu()
-        self.kernel_ms = []
-        try:
-            shape = tuple(np.shape(h.im_skel[0]))
-            device = int(getattr(h, "device_index", 0))
-            self._engine = hipnative.BranchFeatures(shape, h.spacing, device=device)
-            self._aggregator = hipnative.NodeFeatures(device=device)      # one for the run: groups and aggregation need no frame
-            for t in range(h.num_t):
-                if h.viewer is not None:
-                    h.viewer.status = f"Extracting branch features. Frame: {t + 1} of {h.num_t}."
-                self._run_frame(t)
-        finally:
-            self.close()
-
-
-def feature_frames(level, labels):
-    """per frame with rows: (t, float64 array (rows, columns), header) by the reference's saving rule (hierarchical.py:279-337): the
-    columns t, label, <statistic>_<key> of the node aggregates (if any), of the voxel aggregates, of the branch aggregates and of the
-    component aggregates (a level that has them), then <feature>_raw for every feature of features_to_save.  Columns of different lengths raise ValueError."""
-    for t in range(len(labels)):
-        lab = np.asarray(labels[t])
-        if len(lab) == 0:
-            continue
-        names, columns = [], []
-        for frames in (getattr(level, "aggregate_node_metrics", None), getattr(level, "aggregate_voxel_metrics", None),
-                       getattr(level, "aggregate_branch_metrics", None), getattr(level, "aggregate_component_metrics", None)):
-            if not frames:
-                continue
-            names += [f"{stat}_{key}" for stat, keys in frames[t].items() for key in keys]
-            columns += [np.array(vals)[0] for keys in frames[t].values() for vals in keys.values()]
-        names += [f"{name}_raw" for name in level.features_to_save]
-        columns += [np.asarray(getattr(level, name)[t]) for name in level.features_to_save]
-        for name, col in zip(names, columns):
-            if col.shape != lab.shape:
-                raise ValueError(f"frame {t}: column {name} has {len(col)} rows for {len(lab)} labels: the region columns (one row per label "
-                                 f"of label_branches), the aggregates (one per label of the voxels or nodes) and the skeleton columns "
-                                 f"(one per label of im_skel) differ in length")
-        columns = [np.full(len(lab), t, dtype=np.int64), lab] + columns
-        yield t, np.array(columns).T, ["t", "label"] + names
+        self._engine = hipnative.BranchFeatures(tuple(np.shape(h.im_skel[0])), h.spacing, device=device)
+        self._aggregator = hipnative.NodeFeatures(device=device)          # one for the run: groups and aggregation need no frame
 
 
 class BranchFeatures(NodeFeatures):
-    """The voxel, node and branch level of the hierarchy from an ImInfo's files to their tables: opens what `NodeFeatures` opens
-    and, by the reference's rule (hierarchical.py:217-233), the reassigned label stacks; runs `Voxels`, `Nodes` and `Branches`;
-    writes `features_voxels`, `features_nodes` (unless `skip_nodes`) and `features_branches`; the objects stay in `.voxels`,
-    `.nodes` and `.branches`."""
+    """The voxel, node and branch level of the hierarchy from an ImInfo's files to their tables: opens also, by the reference's
+    rule (hierarchical.py:217-233), the reassigned label stacks; runs `Voxels`, `Nodes` and `Branches`; writes `features_voxels`,
+    `features_nodes` (unless `skip_nodes`) and `features_branches`; the objects stay in `.voxels`, `.nodes` and `.branches`."""
 
-    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
-        super().__init__(im_info, skip_nodes=skip_nodes, enable_motility=enable_motility, device=device, device_index=device_index, viewer=viewer)
-        self.im_obj_reassigned = self.im_branch_reassigned = None
-        self.branches = None
-
-    def _allocate_memory(self):
-        super()._allocate_memory()
-        if self.im_info.no_t:
-            return
-        paths = self.im_info.pipeline_paths
-        obj, branch = paths.get("im_obj_label_reassigned"), paths.get("im_branch_label_reassigned")
-        if obj and branch and os.path.exists(obj) and os.path.exists(branch):
-            self.im_obj_reassigned = self.im_info.get_memmap(obj)
-            self.im_branch_reassigned = self.im_info.get_memmap(branch)
-
-    def _save_branches(self):
-        import pandas as pd
-        br = self.branches
-        path = self.im_info.pipeline_paths["features_branches"]
-        header = None
-        for t, frame, names in feature_frames(br, br.branch_label):
-            first = header is None
-            header = header or names
-            pd.DataFrame(frame, columns=header).to_csv(path, index=False, mode="w" if first else "a", header=first)
-        if header is None:                                        # no branch in any frame: the header alone
-            pd.DataFrame(np.zeros((0, 2 + len(br.features_to_save))), columns=["t", "label"] + [f"{k}_raw" for k in br.features_to_save]).to_csv(path, index=False)
-
-    def run(self):
-        super().run()
-        logger.info("Running branch feature extraction (HIP).")
-        self.branches = Branches(self)
-        self.branches.run()
-        self._save_branches()
-        return self.branches
+    levels = NodeFeatures.levels + (Branches,)

@@ -27,11 +27,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from nellie_amd.feature_extraction.branches import BranchFeatures, feature_frames, region_columns, region_stats
-from nellie_amd.feature_extraction.nodes import _aggregate
+from nellie_amd.feature_extraction.branches import BranchFeatures, region_columns, region_stats
+from nellie_amd.feature_extraction.hierarchy import Level
+from nellie_amd.feature_extraction.nodes import aggregate_groups
 from nellie_amd.feature_extraction.voxels import _image_name
-from nellie_amd.stage import require_gpu
-from nellie_amd.utils.base_logger import logger
 
 REGION_STATS = region_stats("organelle")
 
@@ -49,7 +48,11 @@ def _groups_of(label_list, labels):
     return off, order[np.isin(sorted_lab, label_list)].astype(np.int64, copy=False)      # sorted: the groups follow one another
 
 
-class Components:
+class Components(Level):
+    word, name, table_key, label_list = "organelle", "components", "features_organelles", "component_label"
+    handles = ("_engine", "_aggregator")
+    reads_reassigned = True
+
     def __init__(self, hierarchy):
         self.hierarchy = hierarchy
         self.time = []
@@ -74,22 +77,9 @@ class Components:
         self._engine = None
         self._aggregator = None
 
-    def close(self):
-        for name in ("_engine", "_aggregator"):
-            if getattr(self, name) is not None:
-                getattr(self, name).close()
-                setattr(self, name, None)
-
     def _aggregate(self, child, label_list, labels, t):
         """the reference's dict of dicts of `child`'s statistics over the groups of `label_list` in `labels`, and the device time"""
-        off, idx = _groups_of(label_list, labels)
-        for name in child.stats_to_aggregate:
-            values = np.asarray(getattr(child, name)[t]) if name != "reassigned_label" else None
-            if values is not None and values.ndim == 1 and len(values) != np.size(labels):
-                raise ValueError(f"frame {t}: {name} has {len(values)} values for {np.size(labels)} component labels")
-        self._aggregator.groups(off, idx)
-        out = _aggregate(self._aggregator, child, t)
-        return out, self._aggregator.kernel_ms_parts()["aggregation"]
+        return aggregate_groups(self._aggregator, child, t, *_groups_of(label_list, labels), np.size(labels), "component labels")
 
     def _run_frame(self, t):
         h, eng = self.hierarchy, self._engine
@@ -126,67 +116,17 @@ class Components:
             getattr(self, k).append(v)
         self.kernel_ms.append(dict(regions=eng.kernel_ms_parts()["regions"], aggregation=ms + more))
 
-    def run(self):
+    def _open(self, device):
         from nellie_amd import hipnative
         h = self.hierarchy
-        require_gpu()
-        self.kernel_ms = []
-        try:
-            shape = tuple(np.shape(h.label_components[0]))
-            device = int(getattr(h, "device_index", 0))
-            self._engine = hipnative.BranchFeatures(shape, h.spacing, device=device)
-            self._aggregator = hipnative.NodeFeatures(device=device)      # one for the run: groups and aggregation need no frame
-            for t in range(h.num_t):
-                if h.viewer is not None:
-                    h.viewer.status = f"Extracting organelle features. Frame: {t + 1} of {h.num_t}."
-                self._run_frame(t)
-        finally:
-            self.close()
-
-
-def _disjoint_statistics(level, t):
-    """the reference merges the aggregate dicts of a frame (three for the organelles, four for the image) with dict.update:
-    concatenating them is the same table only while no statistic has the same name in two of them"""
-    seen = set()
-    for frames in (level.aggregate_node_metrics, level.aggregate_voxel_metrics, level.aggregate_branch_metrics,
-                   getattr(level, "aggregate_component_metrics", None)):
-        if not frames:
-            continue
-        names = set(frames[t])
-        assert not (seen & names), f"frame {t}: statistics {sorted(seen & names)} are aggregated from two levels"
-        seen |= names
+        self._engine = hipnative.BranchFeatures(tuple(np.shape(h.label_components[0])), h.spacing, device=device)
+        self._aggregator = hipnative.NodeFeatures(device=device)          # one for the run: groups and aggregation need no frame
 
 
 class ComponentFeatures(BranchFeatures):
-    """The voxel, node, branch and organelle level of the hierarchy from an ImInfo's files to their tables: opens what
-    `BranchFeatures` opens, runs `Voxels`, `Nodes`, `Branches` and `Components`, writes `features_voxels`, `features_nodes` (unless
-    `skip_nodes`), `features_branches` and `features_organelles`; the objects stay in `.voxels`, `.nodes`, `.branches` and
-    `.components`."""
+    """The voxel, node, branch and organelle level of the hierarchy from an ImInfo's files to their tables: runs `Voxels`, `Nodes`,
+    `Branches` and `Components`, writes `features_voxels`, `features_nodes` (unless `skip_nodes`), `features_branches` and
+    `features_organelles` (t, label = component_label[t], the node, voxel and branch aggregates in that order, then
+    <feature>_raw); the objects stay in `.voxels`, `.nodes`, `.branches` and `.components`."""
 
-    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
-        super().__init__(im_info, skip_nodes=skip_nodes, enable_motility=enable_motility, device=device, device_index=device_index, viewer=viewer)
-        self.components = None
-
-    def _save_components(self):
-        """the organelle table by the reference's rule (hierarchical.py:280-337, 399-415): t, label = component_label[t], the node,
-        voxel and branch aggregates in that order, then <feature>_raw"""
-        import pandas as pd
-        co = self.components
-        path = self.im_info.pipeline_paths["features_organelles"]
-        header = None
-        for t in range(len(co.component_label)):
-            _disjoint_statistics(co, t)
-        for t, frame, names in feature_frames(co, co.component_label):
-            first = header is None
-            header = header or names
-            pd.DataFrame(frame, columns=header).to_csv(path, index=False, mode="w" if first else "a", header=first)
-        if header is None:                                        # no component in any frame: the header alone
-            pd.DataFrame(np.zeros((0, 2 + len(co.features_to_save))), columns=["t", "label"] + [f"{k}_raw" for k in co.features_to_save]).to_csv(path, index=False)
-
-    def run(self):
-        super().run()
-        logger.info("Running organelle feature extraction (HIP).")
-        self.components = Components(self)
-        self.components.run()
-        self._save_components()
-        return self.components
+    levels = BranchFeatures.levels + (Components,)

@@ -1,0 +1,192 @@
+"""
+What the five feature levels share: `Level`, the life-cycle of one level (its device handles, `close()`, the per-frame loop of
+`run()`); `LevelDriver`, which opens the files the reference's Hierarchy opens (hierarchical.py:190-233) and runs a list of levels
+in order, one loop as the reference's (hierarchical.py:538-566); and `write_table`, the one writer of the five feature tables by
+the reference's saving rule (`feature_frames`; hierarchical.py:279-337, 611-625).
+
+The level modules import this one; it imports none of them.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from nellie_amd.stage import frame_count, require_gpu, resolve_device, spacing_of
+from nellie_amd.utils.base_logger import logger
+
+AGGREGATES = ("aggregate_node_metrics", "aggregate_voxel_metrics", "aggregate_branch_metrics", "aggregate_component_metrics")
+
+
+class Level:
+    """One level of the hierarchy.  A level class names itself (`word` in the messages, `name` of the driver's attribute that holds
+    it), its table (`table_key` in pipeline_paths, `label_list`: the attribute with the labels per frame, None for the row number),
+    what it reads of the driver (`reads_flow`, `reads_reassigned`) and its device handles; it opens them in `_open(device)` and
+    does a frame in `_run_frame(t)`."""
+
+    word = name = table_key = label_list = None
+    handles = ()
+    reads_flow = reads_reassigned = False
+
+    def table_labels(self):
+        return None if self.label_list is None else getattr(self, self.label_list)
+
+    def close(self):
+        for name in self.handles:
+            if getattr(self, name) is not None:
+                getattr(self, name).close()
+                setattr(self, name, None)
+
+    def run(self):
+        h = self.hierarchy
+        require_gpu()
+        self.kernel_ms = []
+        try:
+            self._open(int(getattr(h, "device_index", 0)))
+            for t in range(h.num_t):
+                if h.viewer is not None:
+                    h.viewer.status = f"Extracting {self.word} features. Frame: {t + 1} of {h.num_t}."
+                self._run_frame(t)
+        finally:
+            self.close()
+
+
+def _names(level, t=None):
+    """the column names after t and label: <statistic>_<key> of frame t's aggregates (none for t = None), then <feature>_raw"""
+    names = []
+    for frames in (getattr(level, attr, None) for attr in AGGREGATES):
+        if frames and t is not None:
+            names += [f"{stat}_{key}" for stat, keys in frames[t].items() for key in keys]
+    return names + [f"{name}_raw" for name in level.features_to_save]
+
+
+def feature_frames(level, labels):
+    """per frame with rows: (t, float64 array (rows, columns), header) by the reference's saving rule (hierarchical.py:279-337): the
+    columns t, label, <statistic>_<key> of the node aggregates (if any), of the voxel aggregates, of the branch aggregates and of the
+    component aggregates (a level that has them), then <feature>_raw for every feature of features_to_save.  Columns of different lengths raise ValueError."""
+    for t in range(len(labels)):
+        lab = np.asarray(labels[t])
+        if len(lab) == 0:
+            continue
+        names, columns = _names(level, t), []
+        for frames in (getattr(level, attr, None) for attr in AGGREGATES):
+            if frames:
+                columns += [np.array(vals)[0] for keys in frames[t].values() for vals in keys.values()]
+        columns += [np.asarray(getattr(level, name)[t]) for name in level.features_to_save]
+        for name, col in zip(names, columns):
+            if col.shape != lab.shape:
+                raise ValueError(f"frame {t}: column {name} has {len(col)} rows for {len(lab)} labels: the region columns (one row per label "
+                                 f"of label_branches), the aggregates (one per label of the voxels or nodes) and the skeleton columns "
+                                 f"(one per label of im_skel) differ in length")
+        columns = [np.full(len(lab), t, dtype=np.int64), lab] + columns
+        yield t, np.array(columns).T, ["t", "label"] + names
+
+
+def _disjoint_statistics(level, t):
+    """the reference merges the aggregate dicts of a frame (three for the organelles, four for the image) with dict.update:
+    concatenating them is the same table only while no statistic has the same name in two of them"""
+    seen = set()
+    for frames in (getattr(level, attr, None) for attr in AGGREGATES):
+        if not frames:
+            continue
+        names = set(frames[t])
+        assert not (seen & names), f"frame {t}: statistics {sorted(seen & names)} are aggregated from two levels"
+        seen |= names
+
+
+def write_table(level, path, labels=None):
+    """a level's table as the reference's Hierarchy writes it: per frame one float64 array (feature_frames) through pandas' to_csv,
+    the header once.  `labels`: the label column per frame; None: the row number within the frame, as many rows as the level's first
+    feature has.  The column names are those of the first frame with rows; when no frame has rows the header alone is written, with
+    the names of frame 0 as it stands (without frames: t, label and the <feature>_raw names)."""
+    import pandas as pd
+    if labels is None:
+        labels = [np.arange(len(col), dtype=np.int64) for col in getattr(level, level.features_to_save[0])]
+    for t in range(len(labels)):
+        _disjoint_statistics(level, t)
+    header = None
+    for t, frame, names in feature_frames(level, labels):
+        first = header is None
+        header = header or names
+        pd.DataFrame(frame, columns=header).to_csv(path, index=False, mode="w" if first else "a", header=first)
+    if header is None:
+        header = ["t", "label"] + _names(level, 0 if len(labels) else None)
+        pd.DataFrame(np.zeros((0, len(header))), columns=header).to_csv(path, index=False)
+
+
+class LevelDriver:
+    """Runs the levels listed in `levels` from an ImInfo's files to their tables: opens what the reference's Hierarchy opens
+    (hierarchical.py:190-233), then per level builds it (it stays in the attribute the level names), runs it and writes its table,
+    so a failure in a late level leaves the earlier tables on disk."""
+
+    levels = ()
+
+    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
+        self.im_info = im_info
+        resolve_device(device)
+        self.device = device or "auto"
+        self.device_index = int(device_index)
+        self.skip_nodes = skip_nodes
+        self.enable_motility = enable_motility
+        self.viewer = viewer
+        self.num_t = frame_count(im_info)
+        self.spacing = spacing_of(im_info)
+        self.im_raw = self.im_struct = self.im_distance = self.im_skel = self.im_pixel_class = self.im_border_mask = None
+        self.label_components = self.label_branches = None
+        self.im_obj_reassigned = self.im_branch_reassigned = None
+        self.flow_interpolator_fw = self.flow_interpolator_bw = None
+        self.voxels = self.nodes = self.branches = self.components = self.image = None
+
+    def _allocate_memory(self):
+        paths, get = self.im_info.pipeline_paths, self.im_info.get_memmap
+        self.im_raw = get(self.im_info.im_path)
+        self.im_struct = get(paths["im_preprocessed"])
+        self.im_distance = get(paths["im_distance"])
+        self.im_skel = get(paths["im_skel"])
+        self.label_components = get(paths["im_instance_label"])
+        self.label_branches = get(paths["im_skel_relabelled"])
+        self.im_border_mask = get(paths["im_border"])
+        self.im_pixel_class = get(paths["im_pixel_class"])
+        if self.im_info.no_t:                                    # the files of a single frame have no T axis: one frame per stack
+            for name in ("im_raw", "im_struct", "im_distance", "im_skel", "label_components", "label_branches", "im_border_mask", "im_pixel_class"):
+                setattr(self, name, getattr(self, name)[None])
+            return
+        if not any(cls.reads_reassigned for cls in self.levels):
+            return
+        obj, branch = paths.get("im_obj_label_reassigned"), paths.get("im_branch_label_reassigned")   # the reference's rule (hierarchical.py:217-233)
+        if obj and branch and os.path.exists(obj) and os.path.exists(branch):
+            self.im_obj_reassigned = get(obj)
+            self.im_branch_reassigned = get(branch)
+
+    def _run_with_flow(self, level):
+        """the flow interpolators live as long as the level that reads them"""
+        from nellie_amd.tracking.flow_interpolation import FlowInterpolator
+        try:
+            if self.enable_motility and not self.im_info.no_t and self.num_t > 1:
+                self.flow_interpolator_fw = FlowInterpolator(self.im_info, device_index=self.device_index)
+                self.flow_interpolator_bw = FlowInterpolator(self.im_info, forward=False, device_index=self.device_index)
+            level.run()
+        finally:
+            for obj in (self.flow_interpolator_fw, self.flow_interpolator_bw):
+                if obj is not None:
+                    obj.close()
+
+    def run(self):
+        require_gpu()
+        level = None
+        for cls in self.levels:
+            logger.info(f"Running {cls.word} feature extraction (HIP).")
+            if level is None:
+                self._allocate_memory()
+            level = cls(self)
+            setattr(self, cls.name, level)
+            if cls.reads_flow:
+                self._run_with_flow(level)
+            else:
+                level.run()
+            if level.table_key is None:
+                continue
+            if self.viewer is not None and cls is self.levels[0]:
+                self.viewer.status = "Saving features to csv files."
+            write_table(level, self.im_info.pipeline_paths[level.table_key], level.table_labels())
+        return level

@@ -25,15 +25,16 @@ from __future__ import annotations
 
 import numpy as np
 
-from nellie_amd.feature_extraction.branches import feature_frames
-from nellie_amd.feature_extraction.components import ComponentFeatures, _disjoint_statistics
-from nellie_amd.feature_extraction.nodes import _aggregate
+from nellie_amd.feature_extraction.components import ComponentFeatures
+from nellie_amd.feature_extraction.hierarchy import Level
+from nellie_amd.feature_extraction.nodes import aggregate_groups
 from nellie_amd.feature_extraction.voxels import _image_name
-from nellie_amd.stage import require_gpu
-from nellie_amd.utils.base_logger import logger
 
 
-class Image:
+class Image(Level):
+    word, name, table_key = "image", "image", "features_image"
+    handles = ("_aggregator",)
+
     def __init__(self, hierarchy):
         self.hierarchy = hierarchy
         self.time = []
@@ -47,20 +48,13 @@ class Image:
         self.kernel_ms = []                                       # device time per frame of the last run
         self._aggregator = None
 
-    def close(self):
-        if self._aggregator is not None:
-            self._aggregator.close()
-            self._aggregator = None
+    def table_labels(self):
+        """one row per frame, a frame without voxels included: its label is 0"""
+        return [np.zeros(1, np.int64)] * len(self.time)
 
     def _aggregate(self, child, rows, t, what):
         """the reference's dict of dicts of `child`'s statistics over the one group of all `rows` rows, and the device time"""
-        for name in child.stats_to_aggregate:
-            values = np.asarray(getattr(child, name)[t]) if name != "reassigned_label" else None
-            if values is not None and values.ndim == 1 and len(values) != rows:
-                raise ValueError(f"frame {t}: {name} has {len(values)} values for {rows} {what}")
-        self._aggregator.groups(np.array([0, rows], np.int64), np.arange(rows, dtype=np.int64))
-        out = _aggregate(self._aggregator, child, t)
-        return out, self._aggregator.kernel_ms_parts()["aggregation"]
+        return aggregate_groups(self._aggregator, child, t, np.array([0, rows], np.int64), np.arange(rows, dtype=np.int64), rows, what)
 
     def _run_frame(self, t):
         h = self.hierarchy
@@ -79,49 +73,15 @@ class Image:
         self.aggregate_component_metrics.append(agg)
         self.kernel_ms.append(dict(aggregation=ms + more))
 
-    def run(self):
+    def _open(self, device):
         from nellie_amd import hipnative
-        h = self.hierarchy
-        require_gpu()
-        self.kernel_ms = []
-        try:
-            self._aggregator = hipnative.NodeFeatures(device=int(getattr(h, "device_index", 0)))      # groups and aggregation need no frame
-            for t in range(h.num_t):
-                if h.viewer is not None:
-                    h.viewer.status = f"Extracting image features. Frame: {t + 1} of {h.num_t}."
-                self._run_frame(t)
-        finally:
-            self.close()
+        self._aggregator = hipnative.NodeFeatures(device=device)          # groups and aggregation need no frame
 
 
 class ImageFeatures(ComponentFeatures):
-    """Every level of the hierarchy from an ImInfo's files to their tables: opens what `ComponentFeatures` opens, runs `Voxels`,
-    `Nodes`, `Branches`, `Components` and `Image`, writes `features_voxels`, `features_nodes` (unless `skip_nodes`),
-    `features_branches`, `features_organelles` and `features_image`; the objects stay in `.voxels`, `.nodes`, `.branches`,
-    `.components` and `.image`."""
+    """Every level of the hierarchy from an ImInfo's files to their tables: runs `Voxels`, `Nodes`, `Branches`, `Components` and
+    `Image`, writes `features_voxels`, `features_nodes` (unless `skip_nodes`), `features_branches`, `features_organelles` and
+    `features_image` (t, label = 0, the node, voxel, branch and component aggregates in that order); the objects stay in `.voxels`,
+    `.nodes`, `.branches`, `.components` and `.image`."""
 
-    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
-        super().__init__(im_info, skip_nodes=skip_nodes, enable_motility=enable_motility, device=device, device_index=device_index, viewer=viewer)
-        self.image = None
-
-    def _save_image(self):
-        """the image table by the reference's rule (hierarchical.py:280-337, 417-431): t, label = 0, the node, voxel, branch and
-        component aggregates in that order; one row per frame, a frame without voxels included"""
-        import pandas as pd
-        im = self.image
-        path = self.im_info.pipeline_paths["features_image"]
-        header = None
-        for t in range(len(im.time)):
-            _disjoint_statistics(im, t)
-        for t, frame, names in feature_frames(im, [np.zeros(1, np.int64)] * len(im.time)):
-            first = header is None
-            header = header or names
-            pd.DataFrame(frame, columns=header).to_csv(path, index=False, mode="w" if first else "a", header=first)
-
-    def run(self):
-        super().run()
-        logger.info("Running image feature extraction (HIP).")
-        self.image = Image(self)
-        self.image.run()
-        self._save_image()
-        return self.image
+    levels = ComponentFeatures.levels + (Image,)

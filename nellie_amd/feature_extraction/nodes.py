@@ -23,9 +23,9 @@ from __future__ import annotations
 
 import numpy as np
 
+from nellie_amd.feature_extraction.hierarchy import Level
 from nellie_amd.feature_extraction.voxels import VoxelFeatures, _image_name
 from nellie_amd.stage import require_gpu
-from nellie_amd.utils.base_logger import logger
 
 KEYS = ("mean", "std_dev", "min", "max", "sum")
 
@@ -56,6 +56,17 @@ def _aggregate(engine, child_class, t):
     return out
 
 
+def aggregate_groups(engine, child_class, t, offsets, idx, rows, what):
+    """(the reference's dict of dicts of `child_class`'s statistics over the CSR groups, the device time): every 1-D statistic must
+    have one value per row of the child level, `rows` of them (`what` names them in the error)"""
+    for name in child_class.stats_to_aggregate:
+        values = np.asarray(getattr(child_class, name)[t]) if name != "reassigned_label" else None
+        if values is not None and values.ndim == 1 and len(values) != rows:
+            raise ValueError(f"frame {t}: {name} has {len(values)} values for {rows} {what}")
+    engine.groups(offsets, idx)
+    return _aggregate(engine, child_class, t), engine.kernel_ms_parts()["aggregation"]
+
+
 def aggregate_stats_for_class(child_class, t, list_of_idxs, low_memory: bool = False, device_index: int = 0):
     """{statistic: {mean | std_dev | min | max | sum: (1, groups) float64}} of every 1-D statistic in
     child_class.stats_to_aggregate at frame t over the groups `list_of_idxs`: a list of index arrays, or a CSR pair (offsets,
@@ -68,7 +79,14 @@ def aggregate_stats_for_class(child_class, t, list_of_idxs, low_memory: bool = F
         return _aggregate(engine, child_class, t)
 
 
-class Nodes:
+class Nodes(Level):
+    word, name = "node", "nodes"
+    handles = ("_engine",)
+
+    @property
+    def table_key(self):
+        return None if self.hierarchy.skip_nodes else "features_nodes"
+
     def __init__(self, hierarchy):
         self.hierarchy = hierarchy
         self.time = []
@@ -93,11 +111,6 @@ class Nodes:
         self.longest = []                                         # L, the longest voxel list, per frame of the last run
         self.kernel_ms = []                                       # device time per frame and part of the last run
         self._engine = None
-
-    def close(self):
-        if self._engine is not None:
-            self._engine.close()
-            self._engine = None
 
     def _voxel_lists(self, t):
         """the frame's node -> voxel lists as CSR: this package's Voxels has them in that form already"""
@@ -128,58 +141,20 @@ class Nodes:
             getattr(self, name).append(stats[name])
         self.kernel_ms.append(eng.kernel_ms_parts())
 
-    def run(self):
+    def _open(self, device):
         from nellie_amd import hipnative
         h = self.hierarchy
-        if h.skip_nodes:
-            return
-        require_gpu()
-        self.kernel_ms, self.longest = [], []
-        try:
-            shape = tuple(np.shape(h.im_pixel_class[0]))
-            self._engine = hipnative.NodeFeatures(shape, h.spacing, device=int(getattr(h, "device_index", 0)))
-            for t in range(h.num_t):
-                if h.viewer is not None:
-                    h.viewer.status = f"Extracting node features. Frame: {t + 1} of {h.num_t}."
-                self._run_frame(t)
-        finally:
-            self.close()
+        self.longest = []
+        self._engine = hipnative.NodeFeatures(tuple(np.shape(h.im_pixel_class[0])), h.spacing, device=device)
+
+    def run(self):
+        if not self.hierarchy.skip_nodes:
+            super().run()
 
 
 class NodeFeatures(VoxelFeatures):
-    """The voxel and the node level of the hierarchy from an ImInfo's files to their tables: opens what `VoxelFeatures` opens,
-    runs `Voxels` then `Nodes`, writes `features_voxels` and, unless `skip_nodes`, `features_nodes`; the objects stay in
-    `.voxels` and `.nodes`."""
+    """The voxel and the node level of the hierarchy from an ImInfo's files to their tables: runs `Voxels` then `Nodes`, writes
+    `features_voxels` and, unless `skip_nodes`, `features_nodes`; the objects stay in `.voxels` and `.nodes`."""
 
     low_memory = False
-
-    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
-        super().__init__(im_info, skip_nodes=skip_nodes, enable_motility=enable_motility, device=device, device_index=device_index, viewer=viewer)
-        self.nodes = None
-
-    def _save_nodes(self):
-        """the node table as the reference's Hierarchy writes it (hierarchical.py:279-337, 362-379): per frame the columns t, label
-        (the row number within the frame), <statistic>_<key> of the voxel aggregates, then <feature>_raw for every feature of
-        features_to_save, as one float64 array through pandas' to_csv"""
-        import pandas as pd
-        nd = self.nodes
-        path = self.im_info.pipeline_paths["features_nodes"]
-        header = None
-        for t, frame in enumerate(nd.aggregate_voxel_metrics):
-            names = [f"{stat}_{key}" for stat, keys in frame.items() for key in keys]
-            columns = [np.array(vals)[0] for keys in frame.values() for vals in keys.values()]
-            names += [f"{name}_raw" for name in nd.features_to_save]
-            columns += [np.asarray(getattr(nd, name)[t]) for name in nd.features_to_save]
-            n = len(columns[0])
-            columns = [np.full(n, t, dtype=np.int64), np.arange(n, dtype=np.int64)] + columns
-            header = header or ["t", "label"] + names
-            pd.DataFrame(np.array(columns).T, columns=header).to_csv(path, index=False, mode="w" if t == 0 else "a", header=t == 0)
-
-    def run(self):
-        super().run()
-        logger.info("Running node feature extraction (HIP).")
-        self.nodes = Nodes(self)
-        self.nodes.run()
-        if not self.skip_nodes:
-            self._save_nodes()
-        return self.nodes
+    levels = VoxelFeatures.levels + (Nodes,)

@@ -21,8 +21,7 @@ import os
 
 import numpy as np
 
-from nellie_amd.stage import frame_count, require_gpu, resolve_device, spacing_of
-from nellie_amd.utils.base_logger import logger
+from nellie_amd.feature_extraction.hierarchy import Level, LevelDriver
 
 
 def _split(offsets, values):
@@ -43,7 +42,11 @@ def _image_name(im_info):
     return name
 
 
-class Voxels:
+class Voxels(Level):
+    word, name, table_key = "voxel", "voxels", "features_voxels"
+    handles = ("_engine",)
+    reads_flow = True
+
     def __init__(self, hierarchy):
         self.hierarchy = hierarchy
         self.time = []
@@ -83,6 +86,7 @@ class Voxels:
         self.features_to_save = self.stats_to_aggregate + ["x", "y", "z"]
         self._engine = None
         self._own_interpolators = []
+        self._flow = (None, None)                                # the (forward, backward) interpolators of the run
 
     def _interpolators(self):
         """(forward, backward) interpolators with a device_field method, (None, None) when the stack has no motility.  The
@@ -105,13 +109,13 @@ class Voxels:
         for obj in self._own_interpolators:
             obj.close()
         self._own_interpolators = []
-        if self._engine is not None:
-            self._engine.close()
-            self._engine = None
+        self._flow = (None, None)
+        super().close()
 
-    def _run_frame(self, t, fw, bw):
+    def _run_frame(self, t):
         h = self.hierarchy
         eng = self._engine
+        fw, bw = self._flow
         comp = h.label_components[t]
         n = eng.frame(comp, h.label_branches[t], h.im_raw[t], h.im_struct[t])
         vox, comp_l, branch_l, intensity, structure = eng.fetch_voxels()
@@ -143,88 +147,22 @@ class Voxels:
             getattr(self, name).append(values)
         self.kernel_ms.append(eng.kernel_ms_parts())
 
-    def run(self):
+    def _open(self, device):
         from nellie_amd import hipnative
         h = self.hierarchy
-        if h.num_t is None:
-            h.num_t = 1
-        require_gpu()
-        self.kernel_ms = []
-        try:
-            fw, bw = self._interpolators()
-            shape = tuple(h.label_components[0].shape)
-            dt = h.im_info.dim_res.get("T") or 1.0
-            device = int(getattr(fw, "device_index", getattr(h, "device_index", 0)))
-            self._engine = hipnative.VoxelFeatures(shape, h.spacing, float(dt), device=device)
-            for t in range(h.num_t):
-                if h.viewer is not None:
-                    h.viewer.status = f"Extracting voxel features. Frame: {t + 1} of {h.num_t}."
-                self._run_frame(t, fw, bw)
-        finally:
-            self.close()
+        self._flow = self._interpolators()
+        dt = h.im_info.dim_res.get("T") or 1.0
+        device = int(getattr(self._flow[0], "device_index", device))
+        self._engine = hipnative.VoxelFeatures(tuple(h.label_components[0].shape), h.spacing, float(dt), device=device)
+
+    def run(self):
+        if self.hierarchy.num_t is None:
+            self.hierarchy.num_t = 1
+        super().run()
 
 
-class VoxelFeatures:
+class VoxelFeatures(LevelDriver):
     """The voxel level of the hierarchy from an ImInfo's files to the voxel table: opens what the reference's Hierarchy opens
     (hierarchical.py:190-233), runs `Voxels` and writes `features_voxels`; the `Voxels` object stays in `.voxels`."""
 
-    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
-        self.im_info = im_info
-        resolve_device(device)
-        self.device = device or "auto"
-        self.device_index = int(device_index)
-        self.skip_nodes = skip_nodes
-        self.enable_motility = enable_motility
-        self.viewer = viewer
-        self.num_t = frame_count(im_info)
-        self.spacing = spacing_of(im_info)
-        self.im_raw = self.im_struct = self.im_distance = self.im_skel = self.im_pixel_class = self.im_border_mask = None
-        self.label_components = self.label_branches = None
-        self.flow_interpolator_fw = self.flow_interpolator_bw = None
-        self.voxels = None
-
-    def _allocate_memory(self):
-        paths, get = self.im_info.pipeline_paths, self.im_info.get_memmap
-        self.im_raw = get(self.im_info.im_path)
-        self.im_struct = get(paths["im_preprocessed"])
-        self.im_distance = get(paths["im_distance"])
-        self.im_skel = get(paths["im_skel"])
-        self.label_components = get(paths["im_instance_label"])
-        self.label_branches = get(paths["im_skel_relabelled"])
-        self.im_border_mask = get(paths["im_border"])
-        self.im_pixel_class = get(paths["im_pixel_class"])
-        if self.im_info.no_t:                                    # the files of a single frame have no T axis: one frame per stack
-            for name in ("im_raw", "im_struct", "im_distance", "im_skel", "label_components", "label_branches", "im_border_mask", "im_pixel_class"):
-                setattr(self, name, getattr(self, name)[None])
-
-    def _save(self):
-        """the voxel table as the reference's Hierarchy writes it: per frame the columns t, label (the row number within the
-        frame) and <feature>_raw for every feature of features_to_save, as one float64 array through pandas' to_csv"""
-        import pandas as pd
-        v = self.voxels
-        header = ["t", "label"] + [f"{name}_raw" for name in v.features_to_save]
-        path = self.im_info.pipeline_paths["features_voxels"]
-        for t in range(len(v.x)):
-            n = len(v.x[t])
-            columns = [np.full(n, t, dtype=np.int64), np.arange(n, dtype=np.int64)] + [np.asarray(getattr(v, name)[t]) for name in v.features_to_save]
-            pd.DataFrame(np.array(columns).T, columns=header).to_csv(path, index=False, mode="w" if t == 0 else "a", header=t == 0)
-
-    def run(self):
-        from nellie_amd.tracking.flow_interpolation import FlowInterpolator
-        require_gpu()
-        logger.info("Running voxel feature extraction (HIP).")
-        self._allocate_memory()
-        try:
-            if self.enable_motility and not self.im_info.no_t and self.num_t > 1:
-                self.flow_interpolator_fw = FlowInterpolator(self.im_info, device_index=self.device_index)
-                self.flow_interpolator_bw = FlowInterpolator(self.im_info, forward=False, device_index=self.device_index)
-            self.voxels = Voxels(self)
-            self.voxels.run()
-        finally:
-            for obj in (self.flow_interpolator_fw, self.flow_interpolator_bw):
-                if obj is not None:
-                    obj.close()
-        if self.viewer is not None:
-            self.viewer.status = "Saving features to csv files."
-        self._save()
-        return self.voxels
+    levels = (Voxels,)

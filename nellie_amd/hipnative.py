@@ -510,6 +510,21 @@ class _Handle:
         self.lib.call(name, self._h, *args)
 
 
+class _TimedParts:
+    """The kernel times of a handle whose library call `_ms_symbol` fills one float per name of `PARTS`."""
+
+    PARTS = _ms_symbol = None
+
+    def kernel_ms_parts(self) -> dict:
+        ms = (_f32 * len(self.PARTS))()
+        self._call(self._ms_symbol, ms)
+        return dict(zip(self.PARTS, (float(v) for v in ms)))
+
+    def kernel_ms(self) -> float:
+        """device time of the kernels since the last frame(), transfers excluded"""
+        return sum(self.kernel_ms_parts().values())
+
+
 def _frame_geometry(what, spacing, shape=None, ndim=None):
     """The constructor checks of the stage handles -> (ndim, shape, (nz, ny, nx), spacing as float64); a handle without a frame
     shape gives its ndim instead and gets None for both shapes."""
@@ -1426,7 +1441,7 @@ class Reassigner(_Handle):
         return _kernel_ms(self, "nl_reassign_kernel_ms")
 
 
-class VoxelFeatures(_Handle):
+class VoxelFeatures(_TimedParts, _Handle):
     """Device state of the voxel level of the hierarchy for one stack (include/nellie_amd.h nl_voxfeat_*): one frame stays on
     the device -- mask, labelled voxels and their values -- while its flow vectors, pivots, motility features and node lists are
     computed; only per-voxel results, the two CSR lists and the node limits come back."""
@@ -1435,7 +1450,7 @@ class VoxelFeatures(_Handle):
     MOTILITY = ("vec01", "vec12", "linear_vel_vector", "linear_vel", "angular_vel_vector", "angular_vel", "linear_acc", "angular_acc",
                 "rel_linear_vel", "rel_angular_vel", "rel_linear_acc", "rel_angular_acc", "rel_directionality")
 
-    _destroy, _noun = "nl_voxfeat_destroy", "voxel-feature object"
+    _destroy, _noun, _ms_symbol = "nl_voxfeat_destroy", "voxel-feature object", "nl_voxfeat_kernel_ms"
 
     def __init__(self, shape, spacing, dt, device=0):
         self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("frames", spacing, shape=shape)
@@ -1503,17 +1518,8 @@ class VoxelFeatures(_Handle):
         nstart[m] = vstart[self.n] = p
         return lims, (nstart.astype(np.int64), nval.astype(np.int64)), (vstart.astype(np.int64), vval.astype(np.int64))
 
-    def kernel_ms_parts(self) -> dict:
-        ms = (_f32 * len(self.PARTS))()
-        self._call("nl_voxfeat_kernel_ms", ms)
-        return dict(zip(self.PARTS, (float(v) for v in ms)))
 
-    def kernel_ms(self) -> float:
-        """device time of the kernels since the last frame(), transfers excluded"""
-        return sum(self.kernel_ms_parts().values())
-
-
-class NodeFeatures(_Handle):
+class NodeFeatures(_TimedParts, _Handle):
     """Device state of the node level of the hierarchy (include/nellie_amd.h nl_nodefeat_*): one frame's node list and border
     mask, and one set of groups (CSR lists of indices) over which value arrays are aggregated with numpy's padded pairwise sums.
     An object used for `groups` / `aggregate` alone needs no frame and may have any shape."""
@@ -1524,7 +1530,7 @@ class NodeFeatures(_Handle):
     # what the device converts exactly to float64; anything else is converted on the host, as numpy would
     VALUE_DTYPES = tuple(np.dtype(t) for t in (np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.float32, np.float64))
 
-    _destroy, _noun = "nl_nodefeat_destroy", "node-feature object"
+    _destroy, _noun, _ms_symbol = "nl_nodefeat_destroy", "node-feature object", "nl_nodefeat_kernel_ms"
 
     def __init__(self, shape=(1, 1), spacing=(1.0, 1.0), device=0):
         self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("frames", spacing, shape=shape)
@@ -1586,23 +1592,15 @@ class NodeFeatures(_Handle):
         self._call("nl_nodefeat_node_stats", _ptr(xyz), _opt(vecs[0]), _opt(vecs[1]), len(xyz), _ptr(out))
         return dict(zip(self.STATS, out))
 
-    def kernel_ms_parts(self) -> dict:
-        ms = (_f32 * len(self.PARTS))()
-        self._call("nl_nodefeat_kernel_ms", ms)
-        return dict(zip(self.PARTS, (float(v) for v in ms)))
 
-    def kernel_ms(self) -> float:
-        return sum(self.kernel_ms_parts().values())
-
-
-class BranchFeatures(_Handle):
+class BranchFeatures(_TimedParts, _Handle):
     """Device state of the branch level of the hierarchy (include/nellie_amd.h nl_branchfeat_*): one frame's skeleton list with
     degree, radius and tips per voxel and edge counts, voxel counts and medians per label, and one frame's regions (the labels of
     the full branch-label volume) with their exact integer sums and the most frequent reassigned label."""
 
     PARTS = ("skeleton", "degree", "radii", "lists", "regions")
 
-    _destroy, _noun = "nl_branchfeat_destroy", "branch-feature object"
+    _destroy, _noun, _ms_symbol = "nl_branchfeat_destroy", "branch-feature object", "nl_branchfeat_kernel_ms"
 
     def __init__(self, shape, spacing, device=0):
         self.ndim, self.shape, (nz, ny, nx), sp = _frame_geometry("frames", spacing, shape=shape)
@@ -1657,11 +1655,3 @@ class BranchFeatures(_Handle):
         labels, sums, mode = np.empty(R, np.int64), np.empty((1 + 3 * D + D * (D + 1) // 2, R), np.int64), np.empty(R, np.int64)
         self._call("nl_branchfeat_fetch_regions", _ptr(labels), _ptr(sums), _ptr(mode))
         return labels, sums, mode
-
-    def kernel_ms_parts(self) -> dict:
-        ms = (_f32 * len(self.PARTS))()
-        self._call("nl_branchfeat_kernel_ms", ms)
-        return dict(zip(self.PARTS, (float(v) for v in ms)))
-
-    def kernel_ms(self) -> float:
-        return sum(self.kernel_ms_parts().values())

@@ -170,7 +170,7 @@ def test_reassigned_mode_on_ties_and_zeros():
 
 
 def test_the_branch_table_has_the_reference_columns():
-    from nellie_amd.feature_extraction.branches import feature_frames
+    from nellie_amd.feature_extraction.hierarchy import feature_frames
     g = bg.load("branches_3d_integer_flow")                      # every frame has as many node labels as branches
     own = br.Branches(bg.double_of(g))
     own.run()
@@ -190,7 +190,7 @@ def test_the_branch_table_has_the_reference_columns():
 
 
 def test_the_branch_table_skips_empty_frames_and_refuses_ragged_ones():
-    from nellie_amd.feature_extraction.branches import feature_frames
+    from nellie_amd.feature_extraction.hierarchy import feature_frames
     g = bg.load("branches_3d_empty_frame")
     own = br.Branches(bg.double_of(g, skip_nodes=True))
     own.run()

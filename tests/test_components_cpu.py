@@ -188,10 +188,9 @@ def test_the_scenes_show_what_they_are_for():
 
 
 def _table_of(components, tmp_path, name="table.csv"):
-    from nellie_amd.feature_extraction.components import ComponentFeatures
+    from nellie_amd.feature_extraction.hierarchy import write_table
     path = str(tmp_path / name)
-    stub = SimpleNamespace(components=components, im_info=SimpleNamespace(pipeline_paths={"features_organelles": path}))
-    ComponentFeatures._save_components(stub)
+    write_table(components, path, components.component_label)
     return open(path).read()
 
 

@@ -62,8 +62,7 @@ def test_the_image_table(name):
     """the text of features_image: one header, one row per frame (the empty one included: empty fields, and 0.0 for the sums),
     t and label as floats; the package's feature_frames gives the same array and header from the same object"""
     import pandas as pd
-    from nellie_amd.feature_extraction.branches import feature_frames
-    from nellie_amd.feature_extraction.components import _disjoint_statistics
+    from nellie_amd.feature_extraction.hierarchy import _disjoint_statistics, feature_frames
     g = ig.load(name)
     T, skip = g["base"]["T"], g["base"]["skip_nodes"]
     own = restated(ig.double_of(g))
@@ -90,7 +89,7 @@ def test_the_image_table(name):
 
 def test_disjoint_statistics_sees_the_component_aggregates():
     from types import SimpleNamespace
-    from nellie_amd.feature_extraction.components import _disjoint_statistics
+    from nellie_amd.feature_extraction.hierarchy import _disjoint_statistics
     level = SimpleNamespace(aggregate_node_metrics=[], aggregate_voxel_metrics=[{"a": {}}], aggregate_branch_metrics=[{"b": {}}],
                             aggregate_component_metrics=[{"c": {}}])
     _disjoint_statistics(level, 0)

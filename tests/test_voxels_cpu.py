@@ -125,5 +125,6 @@ def test_voxel_features_opens_the_files_and_writes_the_reference_table(tmp_path)
                       ("label_branches", "branch"), ("im_pixel_class", "pixel_class")):
         assert same(np.asarray(getattr(vf, attr)), g[key]), attr
     vf.voxels = SimpleNamespace(features_to_save=g["ref"]["features_to_save"], **{k: g["ref"][k] for k in g["ref"]["features_to_save"]})
-    vf._save()
+    from nellie_amd.feature_extraction.hierarchy import write_table
+    write_table(vf.voxels, paths["features_voxels"])
     assert open(paths["features_voxels"]).read() == vg.expected_csv(g["ref"])

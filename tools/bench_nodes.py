@@ -58,8 +58,8 @@ def main():
                             skip_nodes=False, enable_motility=True, flow_interpolator_fw=FlowInterpolator(im),
                             flow_interpolator_bw=FlowInterpolator(im, forward=False))
         v = Voxels(h)
-        v._engine = hipnative.VoxelFeatures(shape, spacing, 1.0)
-        v._run_frame(t, h.flow_interpolator_fw, h.flow_interpolator_bw)      # every list of v has one entry: frame 0 below
+        v._engine, v._flow = hipnative.VoxelFeatures(shape, spacing, 1.0), (h.flow_interpolator_fw, h.flow_interpolator_bw)
+        v._run_frame(t)                                   # every list of v has one entry: frame 0 below
         v.close()
         h.flow_interpolator_fw.close()
         h.flow_interpolator_bw.close()

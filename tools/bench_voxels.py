@@ -69,14 +69,14 @@ def main():
                             skip_nodes=False, enable_motility=True, flow_interpolator_fw=FlowInterpolator(im),
                             flow_interpolator_bw=FlowInterpolator(im, forward=False))
         v = Voxels(h)
-        v._engine = hipnative.VoxelFeatures(shape, h.spacing, 1.0)
+        v._engine, v._flow = hipnative.VoxelFeatures(shape, h.spacing, 1.0), (h.flow_interpolator_fw, h.flow_interpolator_bw)
         walls, parts = [], []
         for _ in range(a.repeat + 1):                     # the first run warms up (allocations, code objects)
             for name in list(vars(v)):
                 if isinstance(getattr(v, name), list) and name not in ("stats_to_aggregate", "features_to_save", "_own_interpolators"):
                     setattr(v, name, [])
             t0 = time.perf_counter()
-            v._run_frame(t, h.flow_interpolator_fw, h.flow_interpolator_bw)
+            v._run_frame(t)
             walls.append(time.perf_counter() - t0)
             parts.append(v.kernel_ms[0])
         n_vox, n_nodes, n_pairs = len(v.coords[0]), len(v.node_voxel_idxs[0]), int(v.node_labels_csr[0][0][-1])
