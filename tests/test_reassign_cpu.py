@@ -1,5 +1,6 @@
 """CPU tests of voxel reassignment: the numpy restatement against the reference's goldens (tests/golden/reassign/reassign_*.npz),
-the margins the goldens were captured under, and the public class where no GPU is needed."""
+the margins the goldens were captured under, the public class where no GPU is needed, and the decisive scenes of
+tests/reassign_scenes.py: every case brings the margins it is built for to exactly 0, and each rule turned into its opposite shows."""
 import glob
 import os
 from types import SimpleNamespace
@@ -194,3 +195,172 @@ def test_class_no_t_returns_early(tmp_path):
     assert vr.run() is None
     vr.close()
     assert not os.listdir(tmp_path)
+
+
+# ---- decisive scenes (tests/reassign_scenes.py): every case brings the margins it is built for to exactly 0 --------------------
+import reassign_scenes as scenes   # noqa: E402
+
+CASES = scenes.decisive_cases()
+_runs = {}
+
+
+def restated(case, **rules):
+    """the restatement of a decisive case on its numpy flow restatement, computed once per (case, rules) and left unchanged"""
+    key = (case["id"],) + tuple(sorted(rules))
+    if key not in _runs:
+        branch, obj, flow = case["make"]()
+        _runs[key] = rs.reassign(branch, obj, flow, case["spacing"], case["r"], **rules)
+    return _runs[key]
+
+
+def assert_margins_zero(case, res, what):
+    """the margins a case is built for are exactly 0, and a half-voxel lattice case has at least 100 tie sets"""
+    for letter in case["zero"]:
+        assert res["margin_" + letter] == 0.0, (what, case["id"], letter, res["margin_" + letter])
+    if case["scene"] == "lattice_holes" and case["half_voxel"]:
+        assert res["tie_sets"] >= 100, (what, case["id"], res["tie_sets"])
+
+
+def test_decisive_cases_are_what_the_issue_lists():
+    ids = [c["id"] for c in CASES]
+    assert len(set(ids)) == len(ids) == 2 * 4 * 6 + 1 + 2
+    lattice = [c for c in CASES if c["scene"] == "lattice_holes"]
+    assert all("a" in c["zero"] and "d" in c["zero"] for c in lattice)
+    assert sum(c["dt"] == 1.4 and c["r"] == 0.7 for c in lattice) == 1
+    assert sum("b" in c["zero"] for c in lattice) == 2 * 2 * 2 and sum("c" in c["zero"] for c in lattice) == 2 * 4 + 1
+    for c in CASES:
+        branch, obj, flow = c["make"]()
+        assert branch.dtype == np.int32 and obj.dtype == np.int32 and branch.shape == obj.shape and branch.shape[0] == 2
+        assert flow.shape[1] == 2 * c["D"] + 2 and len(flow) < 2000 and np.all(flow[:, 0] == 0)
+        assert obj[0].size <= {"lattice_holes": 5 * 12 * 70, "crowd": 15 ** 3, "faces_and_outside": 8 * 40 * 70}[c["scene"]]
+    branch, obj, _ = scenes.lattice_holes(3, (0.0, 0.0, 0.0))
+    assert obj[0][2, 5, 30] != obj[0][2, 5, 31] != obj[0][2, 6, 31] and (obj[1] > 0).sum() == (obj[0] > 0).sum() // 2
+    assert 0 < (branch[1] > 0).sum() < (obj[1] > 0).sum()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
+def test_decisive_case_decides(case):
+    res = restated(case)
+    print(f"{case['id']}: margins a {res['margin_a']:.3g} b {res['margin_b']:.3g} c {res['margin_c']:.3g} d {res['margin_d']:.3g}, "
+          f"{res['tie_sets']} tie sets, longest candidate list {res['max_candidates']}")
+    assert res["pairs"] == 1 and len(res["running_matches"]) == 1
+    assert_margins_zero(case, res, "flow restatement")
+
+
+def test_lattice_vectors_survive_a_few_ulps():
+    """the flow vectors arrive as a weighted mean of equal vectors, which need not be bit-exact: the float32 roundings of the
+    centroid and of c - m restore the lattice point, so a vector that is off by a few ulps gives the same result and the same
+    zero margins"""
+    import flow_interpolation_restatement as fr
+    rng = np.random.default_rng(5)
+    for case in CASES:
+        if case["scene"] != "lattice_holes":
+            continue
+        branch, obj, flow = case["make"]()
+
+        def interp(coords, t, forward):
+            out = fr.interpolate_coord(flow, np.asarray(case["spacing"]), case["r"], coords, t, forward)[0]
+            return out * (1.0 + rng.integers(-4, 5, out.shape) * 2.0 ** -52)
+        got, want = rs.reassign(branch, obj, None, case["spacing"], case["r"], interp=interp), restated(case)
+        assert_margins_zero(case, got, "vectors off by up to 4 ulps")
+        for key in ("reassigned_branch", "reassigned_obj"):
+            assert np.array_equal(got[key], want[key]), (case["id"], key)
+        assert all(np.array_equal(a, b) for x, y in zip(got["running_matches"], want["running_matches"]) for a, b in zip(x, y)), case["id"]
+
+
+def crowd_labels(res):
+    return [(int(res["reassigned_obj"][1][t]), int(res["reassigned_branch"][1][t])) for t in scenes.CROWD_TARGETS]
+
+
+def test_crowd_ties_the_vote_over_a_long_list():
+    case = next(c for c in CASES if c["scene"] == "crowd")
+    res = restated(case)
+    # the interior target's list: every lattice offset whose float32 length is below r (the voxel under the target included), and
+    # its own backward candidate
+    k = np.arange(-6, 7)
+    off = np.stack(np.meshgrid(k, k, k, indexing="ij"), axis=-1).reshape(-1, 3)
+    within = rs.error_distance(off.astype(np.float64), np.zeros_like(off, np.float64), np.asarray(case["spacing"])).astype(np.float64) < case["r"]
+    assert res["max_candidates"] == int(within.sum()) + 1 and res["max_candidates"] > 300
+    assert res["margin_c"] == 0.0
+    (A, B, _), (A2, B2, _) = scenes.CROWD_LABELS
+    assert A < B and A2 < B2
+    assert crowd_labels(res) == [(A, 50), (A2, 51)]          # the smaller of the two tied labels; the voxel under the target wins the branch vote
+    assert [o for o, _ in crowd_labels(restated(case, vote_larger=True))] == [B, B2]
+
+
+def test_faces_and_outside_on_the_restatement():
+    import flow_interpolation_restatement as fr
+    case = next(c for c in CASES if c["scene"] == "faces_and_outside")
+    branch, obj, flow = case["make"]()
+    res = restated(case)
+    for face in range(3):                                # labelled voxels on every face and corner of both frames
+        for side in (0, -1):
+            assert np.take(obj[0], side, axis=face).any() and np.take(obj[1], side, axis=face).any()
+    for corner in np.ndindex(2, 2, 2):
+        at = tuple(-c for c in corner)
+        assert obj[0][at] > 0 and obj[1][at] > 0
+    for name in scenes.FACES_REGIONS:
+        m = scenes.faces_region(name)
+        assert (obj[0][m] > 0).all() and (obj[1][m] > 0).all()
+        got = res["reassigned_obj"][1][m]
+        if name in scenes.FACES_STAY_ZERO:
+            assert not got.any() and not res["reassigned_branch"][1][m].any(), name
+        else:
+            assert (got > 0).all() and set(got.tolist()) <= set(obj[0][m].tolist()), name
+    nan = np.argwhere(scenes.faces_region("inner_nan")).astype(np.float64)
+    vec = fr.interpolate_coord(flow, np.asarray(case["spacing"]), case["r"], nan, 0, True)[0]
+    assert vec.shape == nan.shape and np.isnan(vec).all()
+    far = fr.interpolate_coord(flow, np.asarray(case["spacing"]), case["r"], np.argwhere(scenes.faces_region("face_x69_1e12")).astype(np.float64), 0, True)[0]
+    assert np.all(far[:, 2] == 1e12)
+    # the eight-fold tie around (3.5, 27.5, 43.5) goes to the lowest index, a whole voxel diagonal from the point it rounds to
+    vox_next, s = np.argwhere(obj[1] > 0), np.asarray(case["spacing"])
+    c = np.asarray([scenes.FACES_DIAGONAL_TIE], np.float64) + 0.5
+    idx, gap, ties = rs.nearest(vox_next, c, s, case["r"])
+    assert tuple(vox_next[idx[0]]) == scenes.FACES_DIAGONAL_TIE and gap[0] == 0.0 and len(ties[0]) == 8
+    assert np.array_equal(np.rint(c[0]) - vox_next[idx[0]], [1, 1, 1])
+    high = restated(case, nearest_highest=True)
+    m = scenes.faces_region("inner_half")
+    assert not np.array_equal(high["reassigned_obj"][1][m], res["reassigned_obj"][1][m])
+    # d == r exactly: the strict test drops the two regions that the inclusive one keeps
+    inc = restated(case, radius_inclusive=True)
+    for name in ("corner_out_exact", "corner_out_exact_z"):
+        assert inc["reassigned_obj"][1][scenes.faces_region(name)].all()
+
+
+def changed(a, b):
+    """(voxels of the two reassigned stacks that differ, rows of the running matches that differ)"""
+    vox = int((a["reassigned_branch"] != b["reassigned_branch"]).sum() + (a["reassigned_obj"] != b["reassigned_obj"]).sum())
+    rows = 0
+    for (p, n), (p2, n2) in zip(a["running_matches"], b["running_matches"]):
+        rows += abs(len(p) - len(p2)) if len(p) != len(p2) else int(((p != p2).any(axis=1) | (n != n2).any(axis=1)).sum())
+    return vox, rows
+
+
+MUTANT_COUNTS = {}
+
+
+@pytest.mark.parametrize("rule", rs.RULES)
+def test_every_rule_is_observable(rule):
+    """each rule turned into its opposite changes the result of the scenes (cases changed, voxels of the two reassigned stacks,
+    rows of the running matches, over the 51 cases):
+      nearest_highest   (a tie of the nearest voxel goes to the highest index)   38 cases, 5791 voxels, 3288 rows
+      radius_inclusive  (d <= r is kept)                                         5 cases, 189 voxels, 146 rows
+      best_later        (the later candidate on equal d)                         16 cases, 0 voxels, 5577 rows
+      vote_larger       (a vote tie goes to the larger label)                    21 cases, 3837 voxels, 0 rows
+    The half-voxel vectors carry the nearest rule ((0, 0, 0) changes no label under it: the backward candidates at d = 0 win);
+    the counts are printed, and the least a rule must do is change one case."""
+    cases = vox = rows = 0
+    for case in CASES:
+        v, r = changed(restated(case), restated(case, **{rule: True}))
+        cases += bool(v or r)
+        vox += v
+        rows += r
+        if rule == "nearest_highest" and case["scene"] == "lattice_holes" and case["dt"] == 1.0:
+            labels = int((restated(case)["reassigned_obj"][1] != restated(case, **{rule: True})["reassigned_obj"][1]).sum())
+            assert labels >= (100 if case["D"] == 3 else 1) or not case["half_voxel"], (case["id"], labels)
+            if case["vector"] == (0.0, 0.0, 0.0):
+                assert labels == 0, (case["id"], labels)
+    print(f"{rule}: {cases} cases, {vox} voxels, {rows} rows")
+    assert cases >= 1 and vox + rows >= 1
+    if rule in ("nearest_highest", "radius_inclusive", "vote_larger"):
+        assert vox >= 1                                  # these three show in the labels, the best pair only in the matches

@@ -15,13 +15,17 @@ earlier candidate.  Vote per label type: candidates whose source has reassigned[
 weight 1 / (d + 1e-6); per target the weights are summed per source label in (label, -weight, candidate) order, one after the
 other; the largest sum wins, a tie goes to the smaller label.
 
-Every discrete decision comes with its margin (see `reassign`)."""
+Every discrete decision comes with its margin (see `reassign`).  Each of the four rules can be turned into its opposite (`RULES`),
+for tests that show a scene observes the rule; the default is the project's rule."""
 import numpy as np
 
 import flow_interpolation_restatement as fr
 
 
 TIE = 1e-9          # squared distances within this (relative) of the nearest count as tied: margin (a)'s bound
+# the opposite of each rule: a nearest-voxel tie goes to the highest index; d <= r is kept; the best pair is the later candidate
+# on equal d; a vote tie goes to the larger label
+RULES = ("nearest_highest", "radius_inclusive", "best_later", "vote_larger")
 
 
 def select_match_coord_dtype(spatial_shape):
@@ -44,7 +48,7 @@ def error_distance(c, m, s):
     return np.sqrt(d2).astype(np.float32)
 
 
-def nearest(vox_real, c, s, r, pairs=4_000_000):
+def nearest(vox_real, c, s, r, pairs=4_000_000, highest=False):
     """per row of c: (index of the nearest voxel, lowest index on a tie; margin (a): (second d2 - nearest d2) / nearest d2 where the
     nearest lies within 1.01 r, inf elsewhere; the tie sets (e): {row: indices of the voxels tied for nearest -- d2 within TIE,
     relative, of the nearest: another summation order may decide those differently}, same rows)"""
@@ -62,7 +66,7 @@ def nearest(vox_real, c, s, r, pairs=4_000_000):
         for a in range(qs.shape[1]):
             diff = q[:, a, None] - ms[None, :, a]
             d2 = d2 + diff * diff
-        i = np.argmin(d2, axis=1)
+        i = len(ms) - 1 - np.argmin(d2[:, ::-1], axis=1) if highest else np.argmin(d2, axis=1)
         best = d2[np.arange(len(q)), i]
         idx[at:at + step] = i
         near = np.nonzero(best <= lim)[0]
@@ -78,7 +82,7 @@ def nearest(vox_real, c, s, r, pairs=4_000_000):
     return idx, gap, ties
 
 
-def _direction(vox_q, vox_real, vec, sign, s, r):
+def _direction(vox_q, vox_real, vec, sign, s, r, nearest_highest=False, radius_inclusive=False):
     """candidates of one direction: (query rows kept, matched rows of vox_real, d as float64), margins a and b, tie sets"""
     none = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), np.inf, np.inf, {})
     if len(vec) == 0:
@@ -87,17 +91,19 @@ def _direction(vox_q, vox_real, vec, sign, s, r):
     if len(qi) == 0:
         return none
     c = vox_q[qi] + vec[qi] if sign > 0 else vox_q[qi] - vec[qi]
-    m, gap, ties = nearest(vox_real, c, s, r)
+    m, gap, ties = nearest(vox_real, c, s, r, highest=nearest_highest)
     d = error_distance(c, vox_real[m], s)
     margin_b = float(np.min(np.abs(d.astype(np.float64) - r))) / r
     keep = d.astype(np.float64) < r                      # the reference compares the float32 d with a float64 radius
+    if radius_inclusive:
+        keep = d.astype(np.float64) <= r
     ties = {int(qi[k]): v for k, v in ties.items()}
     return qi[keep], m[keep], d[keep].astype(np.float64), float(gap.min()), margin_b, ties
 
 
-def best_pairs(src, tgt, d):
+def best_pairs(src, tgt, d, later=False):
     """per target the candidate with the smallest d, the earlier one on a tie, in target order; margin (d)"""
-    order = np.lexsort((np.arange(len(d)), d, tgt))
+    order = np.lexsort((-np.arange(len(d)) if later else np.arange(len(d)), d, tgt))
     ts, ds = tgt[order], d[order]
     first = np.concatenate([[True], ts[1:] != ts[:-1]])
     same = ~first[1:] & first[:-1]                       # second entry of a target with several
@@ -108,7 +114,7 @@ def best_pairs(src, tgt, d):
     return order[first], margin
 
 
-def vote(tgt, labels, d):
+def vote(tgt, labels, d, larger=False):
     """(targets, winning labels, margin (c)): weights summed per (target, label) in (label, -weight, candidate) order"""
     w = 1.0 / (d + 1e-6)
     order = np.lexsort((np.arange(len(w)), -w, labels, tgt))
@@ -122,7 +128,7 @@ def vote(tgt, labels, d):
         at = pos == k
         sums[seg[at]] = sums[seg[at]] + ws[at] if k else ws[at]
     pt, plab = ts[first], ls[first]
-    order2 = np.lexsort((plab, -sums, pt))
+    order2 = np.lexsort((-plab if larger else plab, -sums, pt))
     pt2, pl2, ps2 = pt[order2], plab[order2], sums[order2]
     head = np.concatenate([[True], pt2[1:] != pt2[:-1]])
     second = ~head[1:] & head[:-1]
@@ -132,7 +138,8 @@ def vote(tgt, labels, d):
     return pt2[head], pl2[head], margin
 
 
-def reassign(branch, obj, flow, spacing, r, store_running_matches=True, max_refine_iterations=3, interp=None):
+def reassign(branch, obj, flow, spacing, r, store_running_matches=True, max_refine_iterations=3, interp=None, nearest_highest=False,
+             radius_inclusive=False, best_later=False, vote_larger=False):
     """branch / obj: (T, ...) label stacks.  interp(coords, t, forward) -> flow vectors (n, D), NaN rows, or shape (0, D); by
     default the flow restatement on `flow`.  Returns a dict:
       reassigned_branch, reassigned_obj  int32 stacks
@@ -142,7 +149,11 @@ def reassign(branch, obj, flow, spacing, r, store_running_matches=True, max_refi
                                          the nearest-voxel step (the voxels of a forward query's tie set, a tied backward query itself)
       min_max_k                          the smallest, over the interpolation calls that found a neighbour, of the largest neighbour
                                          count of a call (0 when none did)
-      pairs                              the number of frame pairs that ran to the end"""
+      pairs                              the number of frame pairs that ran to the end
+      tie_sets                           the number of queries whose nearest-voxel step was tied
+      max_candidates                     the longest candidate list of a target
+      zero_ties                          per frame pair a bool mask over the frame: the targets with two or more candidates at d = 0
+    The four keywords after `interp` turn a rule into its opposite (RULES)."""
     branch, obj = np.asarray(branch), np.asarray(obj)
     T, shape = branch.shape[0], branch.shape[1:]
     D = len(shape)
@@ -158,15 +169,16 @@ def reassign(branch, obj, flow, spacing, r, store_running_matches=True, max_refi
     re_b[0][branch[0] > 0] = branch[0][branch[0] > 0]
     re_o[0][obj[0] > 0] = obj[0][obj[0] > 0]
     dtype = select_match_coord_dtype(shape)
-    res = dict(margin_a=np.inf, margin_b=np.inf, margin_c=np.inf, margin_d=np.inf, tainted=[], pairs=0)
+    res = dict(margin_a=np.inf, margin_b=np.inf, margin_c=np.inf, margin_d=np.inf, tainted=[], pairs=0, tie_sets=0, max_candidates=0, zero_ties=[])
+    how = dict(nearest_highest=nearest_highest, radius_inclusive=radius_inclusive)
     matches = []
     for t in range(T - 1):
         vox_prev = np.argwhere((branch[t] > 0) | (obj[t] > 0))
         vox_next = np.argwhere((branch[t + 1] > 0) | (obj[t + 1] > 0))
         if len(vox_prev) == 0 or len(vox_next) == 0:
             break
-        fq, fm, fd, fa, fb, fties = _direction(vox_prev, vox_next, np.asarray(interp(vox_prev, t, True), np.float64).reshape(-1, D), 1, s, r)
-        bq, bm, bd, ba, bb, bties = _direction(vox_next, vox_prev, np.asarray(interp(vox_next, t + 1, False), np.float64).reshape(-1, D), -1, s, r)
+        fq, fm, fd, fa, fb, fties = _direction(vox_prev, vox_next, np.asarray(interp(vox_prev, t, True), np.float64).reshape(-1, D), 1, s, r, **how)
+        bq, bm, bd, ba, bb, bties = _direction(vox_next, vox_prev, np.asarray(interp(vox_next, t + 1, False), np.float64).reshape(-1, D), -1, s, r, **how)
         res["margin_a"] = min(res["margin_a"], fa, ba)
         res["margin_b"] = min(res["margin_b"], fb, bb)
         taint = np.zeros(shape, bool)
@@ -175,13 +187,18 @@ def reassign(branch, obj, flow, spacing, r, store_running_matches=True, max_refi
         if bties:
             taint[tuple(vox_next[np.fromiter(bties, np.int64)].T)] = True
         res["tainted"].append(taint)
+        res["tie_sets"] += len(fties) + len(bties)
         src = np.concatenate([fq, bm])                   # rows of vox_prev
         tgt = np.concatenate([fm, bq])                   # rows of vox_next
         d = np.concatenate([fd, bd])
         if len(src) == 0:
             break
+        res["max_candidates"] = max(res["max_candidates"], int(np.bincount(tgt).max()))
+        zero = np.zeros(shape, bool)
+        zero[tuple(vox_next[np.nonzero(np.bincount(tgt[d == 0], minlength=len(vox_next)) > 1)[0]].T)] = True
+        res["zero_ties"].append(zero)
         if store_running_matches:
-            best, md = best_pairs(src, tgt, d)
+            best, md = best_pairs(src, tgt, d, later=best_later)
             res["margin_d"] = min(res["margin_d"], md)
             matches.append([vox_prev[src[best]].astype(dtype), vox_next[tgt[best]].astype(dtype)])
         for lab, re in ((branch, re_b), (obj, re_o)):
@@ -192,7 +209,7 @@ def reassign(branch, obj, flow, spacing, r, store_running_matches=True, max_refi
                 un = re[t + 1][tuple(vox_next[c_tgt].T)] == 0
                 if not un.any():
                     break
-                wt, wl, mc = vote(c_tgt[un], c_lab[un], c_d[un])
+                wt, wl, mc = vote(c_tgt[un], c_lab[un], c_d[un], larger=vote_larger)
                 res["margin_c"] = min(res["margin_c"], mc)
                 re[t + 1][tuple(vox_next[wt].T)] = wl
         res["pairs"] += 1
