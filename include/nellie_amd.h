@@ -254,6 +254,28 @@ int nl_chain_flush(nl_ctx *ctx, char *err, size_t errlen);
 int nl_chain_finish(nl_ctx *ctx, int *flags, double *gamma, double *max_abs, double *thr, int64_t *mask_count, char *err, size_t errlen);
 int nl_chain_log(nl_ctx *ctx, int k, int which, int64_t *counts, float *edges, float *range, double *scalars, char *err, size_t errlen);
 
+/* The scales of a frame walked OUT of sigma order.  The frame is max_s(v_s) * AND_s(m_s): any walk order gives the same bits, and a walk
+   queues only voxels alive in the masks walked before it, so the most selective masks should come first.  A whole 3-D volume on one
+   context whose cascade steps are all fused (nl_gauss_step_fused: one kernel, one volume read, one written), so that the Gaussians of
+   three consecutive scales coexist in the three ping-pong volumes:
+     nl_chain_begin_unordered(n)  instead of nl_chain_begin
+     nl_gauss_step ...            the cascade step of scale k (sigma order); refused with NL_ESTATE while three scales are pending
+     nl_chain_sample(k, ...)      right after it: lattice histograms, gamma, bracket, and the forecast of the scale's mask fraction;
+                                  scale k is now pending -- its Gaussian and its lattice cache are kept until it is walked
+     nl_chain_estimates(frac, n)  the forecasts of the scales sampled so far (< 0: none); waits for the newest sampling round.  They
+                                  steer the order only
+     nl_chain_walk(k, ...)        any pending scale: walk, exact histogram, resolve kernel; frees the scale's volume
+     nl_chain_flush / nl_chain_finish / nl_chain_log as above: records, flags and results by sigma index k.
+   The frame's last cascade step pre-zeroes the label volume (NELLIE_PREZERO) only if its third volume holds no pending scale. */
+int nl_gauss_step_fused(nl_ctx *ctx, const double *wz, int rz, const double *wy, int ry, const double *wx, int rx, int *fused,
+                        char *err, size_t errlen);
+int nl_chain_begin_unordered(nl_ctx *ctx, int n_scales, char *err, size_t errlen);
+int nl_chain_sample(nl_ctx *ctx, int k, const double spacing[3], int64_t sz, int64_t sy, int64_t sx, double division, double margin,
+                    double test_scale, char *err, size_t errlen);
+int nl_chain_estimates(nl_ctx *ctx, float *frac, int n, char *err, size_t errlen);
+int nl_chain_walk(nl_ctx *ctx, int k, const double spacing[3], int64_t sz, int64_t sy, int64_t sx, double alpha_sq, double beta_sq,
+                  double division, int64_t z0, int64_t z1, char *err, size_t errlen);
+
 /* Second half of nl_vesselness_spec, with the arguments nl_vesselness_step takes (nl_set_frob_norm first).
    *hit = 1: the exact threshold lies inside the bracket; the parked voxels got the exact h_mask test and the scale
    is complete, bit-identical to nl_vesselness_step (`mask_count` as there).  *hit = 0: no effect. */

@@ -17,6 +17,9 @@
 // condition (no positive sample, degenerate triangle, +inf, queue overflow, bracket miss, empty scale, underflow of the
 // normalised range) or a failed comparison sets `flags`, and the caller redoes the frame the synchronous way: the chain can
 // make a frame faster, never different.
+// The first line of that list needs the scale's Gaussian only, the rest joins the frame's masks: where three Gaussians can coexist the
+// host runs the first line of up to three scales ahead and walks them in the order chain_thr1_kernel's forecast of the mask fraction
+// suggests (nellie_hip.hip: nl_chain_sample / nl_chain_walk).  The records stay indexed by sigma.
 #define NL_CHAIN_BINS 256
 #define NL_CHAIN_MAX_SCALES 16
 
@@ -48,6 +51,10 @@ struct ChainScale {
     int status_gauss, status_raw, status_exact;
     double tri[3], otsu[3];
     ChainHist h_gauss, h_raw, h_exact;
+    // appended (nothing above moves): the share of the scale's lattice points whose raw frob_sq reaches fsq_lo -- a forecast of its
+    // h_mask fraction, < 0 when there is none.  It orders the walks of a frame (nl_chain_walk) and decides no value.
+    float pred_frac;
+    int pad_;
 };
 
 // ---- the two histogram thresholds on the device: hist_thresholds_host on one wave ----------------------------------------
@@ -185,7 +192,7 @@ __device__ inline bool dev_finite_f(float x) { return fabsf(x) <= 3.402823466e38
 // thresholds need nothing from each other.  Every lane computes the same scalars (the element-wise parts of the thresholds
 // are spread over the lanes), lane 0 records them.
 __global__ void __launch_bounds__(64)
-chain_thr1_kernel(ChainScale *cs, double division, double margin, double test_scale) {
+chain_thr1_kernel(ChainScale *cs, double division, double margin, double test_scale, double n_lattice) {
     __shared__ double scratch[6 * NL_CHAIN_BINS];
     int flags = 0;
     if (blockIdx.x == 0) {
@@ -228,7 +235,18 @@ chain_thr1_kernel(ChainScale *cs, double division, double margin, double test_sc
         if (!(dev_finite_f(l) && dev_finite_f(u) && u > 0.0f) || !(l <= u)) flags |= NL_CF_BRACKET;
         else { lo = l; hi = u; }
     }
+    // the forecast: the samples of the bins whose centre reaches the bracket's lower end, over all lattice points
+    float pred = -1.0f;
+    if (!flags && n_lattice > 0.0) {
+        unsigned long long part = 0;
+        for (int i = threadIdx.x; i < NL_CHAIN_BINS; i += 64) {
+            const float centre = (h.edges[i] + h.edges[i + 1]) / 2.0f;
+            if (centre * centre >= lo) part += h.counts[i];
+        }
+        pred = (float)((double)wave_sum_u64(part) / n_lattice);
+    }
     if (threadIdx.x == 0) {
+        cs->pred_frac = pred;
         cs->tri[1] = tri1; cs->otsu[1] = otsu1; cs->status_raw = st1;
         cs->raw_mn = raw_mn; cs->raw_mx = raw_mx;
         cs->fsq_lo = lo; cs->fsq_hi = hi;

@@ -203,6 +203,8 @@ extern "C" int nl_ctx_destroy(nl_ctx *c) {
     if (c->d_blk) hipFree(c->d_blk);
     for (int k = 0; k < 4; ++k) if (c->d_2d[k]) hipFree(c->d_2d[k]);
     if (c->d_fsq_cache) hipFree(c->d_fsq_cache);
+    for (auto &pk : c->fsq_park) if (pk.p) hipFree(pk.p);
+    if (c->h_chain_est) hipHostFree(c->h_chain_est);
     if (c->d_vq) hipFree(c->d_vq);
     if (c->mk_scratch) hipFree(c->mk_scratch);
     if (c->mk_act) hipFree(c->mk_act);
@@ -364,7 +366,7 @@ extern "C" int nl_filter_load(nl_ctx *c, const void *host, int dtype, int64_t z0
     NL_JOIN_SIDE(c);
     if (!host || z0 < 0 || z1 > c->nzl || z0 >= z1) return nl_fail(err, errlen, NL_EINVAL, "bad plane range [%lld,%lld)", (i64)z0, (i64)z1);
     c->i_gauss = 0; c->i_vmax = 3; c->i_labels = -1; c->frangi_ready = 0;
-    c->pz_on = 0; c->prezero_used = 0;
+    c->pz_on = 0; c->prezero_used = 0; c->chain_reorder = 0;
     c->gauss_ext = nullptr;
     // a frame abandoned between nl_gauss_step_ahead and nl_gauss_commit (an exception in the host's scale loop) leaves a cascade step on the
     // side stream that still writes the ping-pong volumes: this frame's first kernels come after it
@@ -405,7 +407,7 @@ extern "C" int nl_filter_begin(nl_ctx *c, char *err, size_t errlen) {
     NL_JOIN_SIDE(c);
     if (!c->d_input) return nl_fail(err, errlen, NL_ESTATE, "nl_filter_begin before nl_input_load");
     c->i_gauss = 0; c->i_vmax = 3; c->i_labels = -1; c->frangi_ready = 0;
-    c->pz_on = 0; c->prezero_used = 0;
+    c->pz_on = 0; c->prezero_used = 0; c->chain_reorder = 0;
     c->mask_slots_used = 0;
     c->gauss_ext = nullptr;
     // a frame abandoned between nl_gauss_step_ahead and nl_gauss_commit (an exception in the host's scale loop) leaves a cascade step on the
@@ -451,6 +453,21 @@ static int gauss_step_volumes(const nl_ctx *c, const double *wz, const double *w
     return (wz ? 1 : 0) + (gauss_can_yx(c, wy, ry, wx, rx) ? 1 : (wy ? 1 : 0) + (wx ? 1 : 0));
 }
 
+// The whole step in one kernel (gauss_zyx.inc)?  See nl_gauss_step.  NELLIE_GAUSS_FUSED=0 / 1: never / whenever the radii allow.
+static bool gauss_takes_zyx(const nl_ctx *c, const double *wz, int rz, const double *wy, int ry, const double *wx, int rx) {
+    const char *e_fz = getenv("NELLIE_GAUSS_FUSED");
+    const bool fused_zyx = e_fz ? atoi(e_fz) != 0 : c->n >= ((i64)1 << 26);
+    return fused_zyx && wz && gauss_can_yx(c, wy, ry, wx, rx) && gyx_tiled() && gl_zyx_ok(c, rz, ry, c->f[(c->i_gauss + 1) % 3]) &&
+           memcmp(wy, wx, (size_t)(2 * ry + 1) * sizeof(double)) == 0;
+}
+// ... asked by the host before it plans a frame out of sigma order: *fused = 1 when nl_gauss_step would take the step in one kernel
+extern "C" int nl_gauss_step_fused(nl_ctx *c, const double *wz, int rz, const double *wy, int ry, const double *wx, int rx, int *fused,
+                                   char *err, size_t errlen) {
+    if (!c || !fused) return nl_fail(err, errlen, NL_EINVAL, "ctx or fused is NULL");
+    *fused = gauss_takes_zyx(c, wz, rz, wy, ry, wx, rx) ? 1 : 0;
+    return NL_OK;
+}
+
 extern "C" int nl_gauss_step(nl_ctx *c, const double *wz, int rz, const double *wy, int ry, const double *wx, int rx,
                              int64_t z0, int64_t z1, char *err, size_t errlen) {
     NL_ENTER(c);
@@ -479,15 +496,22 @@ extern "C" int nl_gauss_step(nl_ctx *c, const double *wz, int rz, const double *
     // (gauss ms per frame, two kernels / fused: 128 x 512 x 512 0.62 / 0.77; 256 x 512 x 512 1.32 / 1.24; 512^3 2.24 / 2.16; 256 x 1024^2
     // 4.44 / 4.00; 1024^3 17.7 / 15.3).
     // NELLIE_GAUSS_FUSED=0 / 1: never / whenever the radii allow (tests run the fused kernel on small volumes that way).
-    const char *e_fz = getenv("NELLIE_GAUSS_FUSED");
-    const bool fused_zyx = e_fz ? atoi(e_fz) != 0 : c->n >= ((i64)1 << 26);
-    if (fused_zyx && wz && can_yx && gyx_tiled() && gl_zyx_ok(c, rz, ry, c->f[(src + 1) % 3]) &&
-        memcmp(wy, wx, (size_t)(2 * ry + 1) * sizeof(double)) == 0) {
+    // A chain that walks its scales out of sigma order (nl_chain_begin: reorder) keeps the Gaussians of its pending scales: the step
+    // writes a volume that holds none of them, and it is the fused step or nothing -- every other form needs a second free volume.
+    const bool reorder = c->chain_reorder && c->chain_n > 0;
+    int dst_zyx = (src + 1) % 3;
+    if (reorder) {
+        if (c->vol_scale[dst_zyx] >= 0) dst_zyx = (src + 2) % 3;
+        if (c->vol_scale[dst_zyx] >= 0 || c->stream == c->side || !gauss_takes_zyx(c, wz, rz, wy, ry, wx, rx))
+            return nl_fail(err, errlen, NL_ESTATE, c->vol_scale[dst_zyx] >= 0 ? "no free Gaussian volume: three scales wait for their walk"
+                                                                                : "a chain out of sigma order takes fused cascade steps only");
+    }
+    if (gauss_takes_zyx(c, wz, rz, wy, ry, wx, rx)) {
         GaussW gy;
         if ((rc = fill_gw(gw, wz, rz, err, errlen)) || (rc = fill_gw(gy, wy, ry, err, errlen))) return rc;
         if ((z0 - rz < 0 && c->gz0 > 0) || (z1 - 1 + rz >= c->nzl && c->gz0 + c->nzl < c->gnz))
             return nl_fail(err, errlen, NL_EINVAL, "Z pass of radius %d on planes [%lld,%lld) reaches outside the local slab", rz, (i64)z0, (i64)z1);
-        const int dst = (src + 1) % 3;
+        const int dst = dst_zyx;
         char scope[32];
         snprintf(scope, sizeof scope, "gauss_zyx<%d,%d>", rz, ry);        // one timer per kernel instantiation, as a profiler lists them
         ProfScope ps(c, scope);
@@ -498,8 +522,13 @@ extern "C" int nl_gauss_step(nl_ctx *c, const double *wz, int rz, const double *
         // ... and the chain's last step the volume Label will paint into: the third ping-pong volume, dead since the step before and
         // for the rest of the frame (nl_chain_begin: pz_on).  A step running ahead is enqueued one nl_chain_scale earlier.
         const bool ahead = c->stream == c->side;
-        const bool prezero = !zero && c->pz_on && c->chain_n > 0 && c->chain_k == c->chain_n - (ahead ? 2 : 1) && z0 == 0 && z1 == c->nzl;
-        float *third = c->f[(src + 2) % 3];
+        // Out of sigma order the steps are counted, and the third volume must hold no scale that still waits for its walk (the host
+        // holds the last step back until then; where an explicit order does not, the labels are written densely as before).
+        const int i_third = 3 - src - dst;
+        const bool last = reorder ? (c->chain_steps == c->chain_n - 1 && c->vol_scale[i_third] < 0)
+                                  : c->chain_k == c->chain_n - (ahead ? 2 : 1);
+        const bool prezero = !zero && c->pz_on && c->chain_n > 0 && last && z0 == 0 && z1 == c->nzl;
+        float *third = c->f[i_third];
         (void)gl_zyx(c, rz, ry, srcp, c->f[dst], v, z0, z1, gauss_ws_of(gw), gauss_ws_of(gy), zero ? c->f[c->i_vmax] : (prezero ? third : nullptr));
         if (zero) { c->vmax_zero_lo = z0; c->vmax_zero_hi = z1; }
         NL_CHECK_LAUNCH();
@@ -551,6 +580,7 @@ extern "C" int nl_gauss_step(nl_ctx *c, const double *wz, int rz, const double *
     c->i_gauss = src;
     c->fsq_cache_valid = 0;
     if (srcp != c->gauss_ext) c->gauss_ext = nullptr;      // a cascade step ran: the Gaussian now lives in f[src]
+    if (reorder) ++c->chain_steps;
     return NL_OK;
 }
 
@@ -1006,12 +1036,18 @@ extern "C" int nl_chain_begin(nl_ctx *c, int n_scales, char *err, size_t errlen)
     NL_CHECK_LAUNCH();
     c->chain_n = n_scales; c->chain_k = 0; c->chain_copy_pending = 0;
     c->def_resolve = 0;
+    c->chain_reorder = 0; c->chain_steps = 0; c->chain_walked = 0;
+    for (int v = 0; v < 3; ++v) { c->vol_scale[v] = -1; c->fsq_park[v].valid = 0; }
     // NELLIE_PREZERO=0: the frame's outputs are written densely, as before (read per frame: one process can run both ways).  A whole
     // 3-D volume on one context only: slabs, images and everything outside the chain keep the dense kernels.
     const char *e_pz = getenv("NELLIE_PREZERO");
     c->pz_on = (e_pz ? atoi(e_pz) != 0 : NL_PREZERO_DEFAULT) && !c->two_d && !c->comm && c->own_lo == 0 && c->own_hi == c->nzl && c->nzl == c->gnz;
     return NL_OK;
 }
+
+static int chain_first_round(nl_ctx *c, ChainScale *cs, i64 sz, i64 sy, i64 sx, double division, double margin, double test_scale, char *err, size_t errlen);
+static int chain_walk_resolve(nl_ctx *c, ChainScale *cs, const double spacing[3], i64 sz, i64 sy, i64 sx, double alpha_sq, double beta_sq, double division,
+                              int64_t z0, int64_t z1, char *err, size_t errlen);
 
 // One scale of the frame, enqueued without a single wait: see chain.inc.  The Gaussian of the scale is current (nl_gauss_step).
 extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, int64_t sy, int64_t sx, double alpha_sq, double beta_sq,
@@ -1033,7 +1069,7 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
         // a margin of 1), the statistics kernel stands where the walk stands, and the vesselness kernel reads gamma_sq / fsq_min / m_inf
         // from the record as the resolve kernel does.  ~20 host round trips of a 2048^2 frame gone.
         if ((rc = sample_first_round(c, NL_FIELD_GAUSS, NL_FIELD_FROB, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, (char *)&cs->h_raw, nullptr, nullptr, true, err, errlen))) return rc;
-        chain_thr1_kernel<<<2, 64, 0, c->stream>>>(cs, division, margin, test_scale);
+        chain_thr1_kernel<<<2, 64, 0, c->stream>>>(cs, division, margin, test_scale, 0.0);
         {
             ProfScope ps(c, "hessian_stats");
             hessian2d_stats_kernel<<<grid2d_rows(c->nx, c->ny), 256, 0, c->stream>>>(gauss_cur(c), geom(c), hessp(c), cs->stats);
@@ -1064,9 +1100,26 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
         NL_CHECK_LAUNCH();
         return NL_OK;
     }
+    if ((rc = chain_first_round(c, cs, sz, sy, sx, division, margin, test_scale, err, errlen))) return rc;
+    return chain_walk_resolve(c, cs, spacing, sz, sy, sx, alpha_sq, beta_sq, division, z0, z1, err, errlen);
+}
+
+// The two halves of a 3-D scale.  The first depends on the scale's Gaussian alone: the lattice samples (which fill the frob_sq cache),
+// gamma, the bracket and the forecast of the mask fraction ...
+static int chain_first_round(nl_ctx *c, ChainScale *cs, i64 sz, i64 sy, i64 sx, double division, double margin, double test_scale, char *err, size_t errlen) {
+    int rc;
     if ((rc = sample_first_round(c, NL_FIELD_GAUSS, NL_FIELD_FROB, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, (char *)&cs->h_raw, nullptr, nullptr, true, err, errlen))) return rc;
-    chain_thr1_kernel<<<2, 64, 0, c->stream>>>(cs, division, margin, test_scale);
+    const i64 g_lo = c->gz0 + c->own_lo, g_hi = c->gz0 + c->own_hi;
+    const i64 cz = (g_hi + sz - 1) / sz - (g_lo + sz - 1) / sz;
+    const double n_lattice = (double)((cz > 0 ? cz : 0) * ((c->ny + sy - 1) / sy) * ((c->nx + sx - 1) / sx));
+    chain_thr1_kernel<<<2, 64, 0, c->stream>>>(cs, division, margin, test_scale, n_lattice);
     NL_CHECK_LAUNCH();
+    return NL_OK;
+}
+// ... the second joins the frame: the walk inside the masks of the scales walked so far, the exact threshold, the resolve kernel.
+static int chain_walk_resolve(nl_ctx *c, ChainScale *cs, const double spacing[3], i64 sz, i64 sy, i64 sx, double alpha_sq, double beta_sq, double division,
+                              int64_t z0, int64_t z1, char *err, size_t errlen) {
+    int rc;
     if ((rc = spec_enqueue(c, spacing, 0.0f, 0.0f, z0, z1, cs->stats, &cs->cnt_walk, &cs->fsq_lo, err, errlen))) return rc;
     // (With the resolve kernel held back, the exact round of the scale on the side stream as well was measured: no gain, docs/HISTORY.md.)
     const bool defer = resolve_defer_ok(c) && c->fsq_cache_valid;     // (the cache is this scale's: the exact round below launches nothing to fill it)
@@ -1089,6 +1142,89 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
     return resolve_enqueue(c, vp, &cs->cnt_resolve, (const float *)cs, err, errlen);
 }
 
+// ---- the scales of a frame walked out of sigma order ---------------------------------------------------------------------------
+// The frame's result is max_s(v_s) * AND_s(m_s): any walk order gives the same bits, and a walk queues only the voxels alive in the masks
+// walked before it -- so the most selective masks should come first.  The cascade itself runs in sigma order; what can be delayed is a
+// scale's walk, for as long as its Gaussian survives: the fused cascade step reads one ping-pong volume and writes one, so three
+// consecutive Gaussians coexist.  nl_chain_begin_unordered starts such a frame.  After every nl_gauss_step the host calls nl_chain_sample(k)
+// -- k in sigma order -- which makes scale k PENDING: its Gaussian stays in the volume the step wrote and its lattice cache is parked
+// beside it.  nl_chain_walk(k) walks any pending scale and frees its volume.  nl_chain_estimates brings the forecasts of the mask
+// fractions to the host, which picks the order (pipeline.py); the records, the flags and nl_chain_finish stay by sigma index.
+extern "C" int nl_chain_begin_unordered(nl_ctx *c, int n_scales, char *err, size_t errlen) {
+    int rc = nl_chain_begin(c, n_scales, err, errlen);
+    if (rc) return rc;
+    if (c->two_d || c->comm) { c->chain_n = 0; return nl_fail(err, errlen, NL_ESTATE, "scales out of sigma order: whole 3-D volumes on one context only"); }
+    c->chain_reorder = 1;
+    return NL_OK;
+}
+
+static void fsq_swap_parked(nl_ctx *c, int v) {
+    nl_ctx::FsqPark &pk = c->fsq_park[v];
+    std::swap(pk.p, c->d_fsq_cache); std::swap(pk.cap, c->fsq_cache_cap); std::swap(pk.valid, c->fsq_cache_valid);
+    for (int i = 0; i < 3; ++i) std::swap(pk.key[i], c->fsq_cache_key[i]);
+}
+
+extern "C" int nl_chain_sample(nl_ctx *c, int k, const double spacing[3], int64_t sz, int64_t sy, int64_t sx, double division, double margin,
+                               double test_scale, char *err, size_t errlen) {
+    NL_ENTER_KEEP_PZ(c);
+    if (!c->d_chain || !c->chain_reorder || c->chain_n < 1) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_sample outside nl_chain_begin_unordered .. nl_chain_finish");
+    if (k != c->chain_k || k >= c->chain_n) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_sample(%d): scale %d is the next in sigma order", k, c->chain_k);
+    if (c->chain_steps != k + 1 || c->gauss_ext) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_sample(%d) without a cascade step of its own", k);
+    if (!(division != 0.0)) return nl_fail(err, errlen, NL_EINVAL, "the chain needs a non-zero threshold division");
+    int rc;
+    if ((rc = set_spacing(c, spacing, err, errlen))) return rc;
+    // the resolve kernel of the last walk, held back until now: beside these threshold kernels, behind the cascade step
+    if ((rc = resolve_deferred_launch(c, true, err, errlen))) return rc;
+    c->chain_par[k][0] = division; c->chain_par[k][1] = margin; c->chain_par[k][2] = test_scale;
+    c->frob_max_abs = 1.0f; c->frob_max_finite = 0.0f;
+    if ((rc = chain_first_round(c, (ChainScale *)c->d_chain + k, sz, sy, sx, division, margin, test_scale, err, errlen))) return rc;
+    const int v = c->i_gauss;
+    fsq_swap_parked(c, v);               // the cache just filled waits with the Gaussian; the buffer that comes back is nobody's
+    c->fsq_cache_valid = 0;
+    c->vol_scale[v] = k; c->chain_vol[k] = v;
+    ++c->chain_k;
+    return NL_OK;
+}
+
+// frac[0 .. n): the forecast mask fraction of every scale sampled so far (chain_thr1_kernel), < 0 where there is none (yet).  Waits for
+// the sampling round of the newest scale -- the one wait a decision about the order costs; nothing the frame computes depends on it.
+extern "C" int nl_chain_estimates(nl_ctx *c, float *frac, int n, char *err, size_t errlen) {
+    NL_ENTER_KEEP_PZ(c);
+    if (!c->d_chain || !c->chain_reorder || c->chain_n < 1) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_estimates outside nl_chain_begin_unordered .. nl_chain_finish");
+    if (!frac || n < 0 || n > NL_CHAIN_MAX_SCALES) return nl_fail(err, errlen, NL_EINVAL, "bad arguments");
+    if (!c->h_chain_est) NL_HIP(hipHostMalloc((void **)&c->h_chain_est, sizeof(float) * NL_CHAIN_MAX_SCALES, hipHostMallocDefault));
+    const int have = c->chain_k < n ? c->chain_k : n;
+    for (int k = 0; k < have; ++k)
+        NL_HIP(hipMemcpyAsync(c->h_chain_est + k, &((const ChainScale *)c->d_chain)[k].pred_frac, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (have) NL_HIP(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < n; ++k) frac[k] = k < have ? c->h_chain_est[k] : -1.0f;
+    return NL_OK;
+}
+
+extern "C" int nl_chain_walk(nl_ctx *c, int k, const double spacing[3], int64_t sz, int64_t sy, int64_t sx, double alpha_sq, double beta_sq,
+                             double division, int64_t z0, int64_t z1, char *err, size_t errlen) {
+    NL_ENTER_KEEP_PZ(c);
+    if (!c->d_chain || !c->chain_reorder || c->chain_n < 1) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_walk outside nl_chain_begin_unordered .. nl_chain_finish");
+    if (k < 0 || k >= c->chain_k || ((c->chain_walked >> k) & 1u)) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_walk(%d): the scale is not pending", k);
+    const int v = c->chain_vol[k];
+    if (c->vol_scale[v] != k) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_walk(%d): its Gaussian is gone", k);
+    int rc;
+    if ((rc = set_spacing(c, spacing, err, errlen))) return rc;
+    // two walks back to back, no sampling round in between: the resolve kernel of the first runs in line
+    if ((rc = resolve_deferred_launch(c, false, err, errlen))) return rc;
+    fsq_swap_parked(c, v);               // this scale's lattice cache becomes the current one
+    c->frob_max_abs = 1.0f; c->frob_max_finite = 0.0f;
+    const int newest = c->i_gauss;
+    c->i_gauss = v;                      // gauss_cur(): the walk and the exact round read this scale's Gaussian
+    rc = chain_walk_resolve(c, (ChainScale *)c->d_chain + k, spacing, sz, sy, sx, alpha_sq, beta_sq, division, z0, z1, err, errlen);
+    c->i_gauss = newest;
+    c->fsq_cache_valid = 0;              // (the cache describes volume v, no longer the current Gaussian)
+    if (rc) return rc;
+    c->vol_scale[v] = -1;
+    c->chain_walked |= 1u << k;
+    return NL_OK;
+}
+
 // Optional, before nl_chain_finish: start the download of the records now, so that work enqueued after this call (the samples
 // of the frame's percentile threshold) runs on the device while nl_chain_finish waits for the records only and repeats the
 // decisions on the host.
@@ -1109,6 +1245,7 @@ extern "C" int nl_chain_finish(nl_ctx *c, int *flags, double *gamma, double *max
     NL_ENTER_KEEP_PZ(c);
     if (!c->d_chain || c->chain_k < 1) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_finish without scales");
     const int n = c->chain_k;
+    if (c->chain_reorder && c->chain_walked != (1u << n) - 1u) return nl_fail(err, errlen, NL_ESTATE, "nl_chain_finish while a sampled scale waits for its walk");
     if (!c->chain_copy_pending) { int rcd = resolve_deferred_launch(c, false, err, errlen); if (rcd) return rcd; }
     if (c->chain_copy_pending) {
         NL_HIP(hipEventSynchronize(c->ev_chain));
@@ -1127,7 +1264,7 @@ extern "C" int nl_chain_finish(nl_ctx *c, int *flags, double *gamma, double *max
         if (thr) thr[k] = (double)h[k].thr;
         if (mask_count) mask_count[k] = (int64_t)(h[k].cnt_walk + h[k].cnt_resolve);
     }
-    c->chain_n = 0; c->pz_on = 0;
+    c->chain_n = 0; c->pz_on = 0; c->chain_reorder = 0;
     return NL_OK;
 }
 

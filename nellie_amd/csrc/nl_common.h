@@ -153,6 +153,16 @@ struct nl_ctx {
     void *d_chain = nullptr, *h_chain = nullptr;     // device-resident threshold chain (chain.inc): records of a frame's scales, pinned mirror
     int chain_n = 0, chain_k = 0;
     double chain_par[16][3] = {};                    // (division, margin, test scale) each scale was enqueued with
+    // Scales walked out of sigma order (nl_chain_sample / nl_chain_walk): what is "the current scale's" elsewhere, once per PENDING
+    // scale -- sampled, not walked yet.  Its Gaussian stays in the ping-pong volume the cascade step wrote, its frob_sq lattice cache is
+    // parked beside that volume; at most three are alive, one per volume.
+    int chain_reorder = 0;                           // this frame's chain runs that way (nl_chain_begin)
+    int chain_steps = 0;                             // cascade steps since nl_chain_begin
+    unsigned chain_walked = 0;                       // bit k: scale k has been walked
+    int chain_vol[16] = {};                          // the volume holding scale k's Gaussian
+    int vol_scale[3] = {-1, -1, -1};                 // the pending scale whose Gaussian volume v holds, or -1
+    struct FsqPark { float *p = nullptr; i64 cap = 0, key[3] = {0, 0, 0}; int valid = 0; } fsq_park[3];
+    float *h_chain_est = nullptr;                    // pinned landing area of the forecasts (nl_chain_estimates)
 
     void *comm = nullptr;             // ncclComm_t (RCCL), set by nl_comm_init
     int fuse_reduce = 0;              // nl_comm_fuse: the sampling / statistics entry points reduce across the ranks on the device

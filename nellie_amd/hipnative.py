@@ -143,6 +143,11 @@ _PROTOS = {
     "nl_chain_flush": [_p],
     "nl_chain_finish": [_p, _p, _p, _p, _p, _p],
     "nl_chain_log": [_p, _int, _int, _p, _p, _p, _p],
+    "nl_gauss_step_fused": [_p, _p, _int, _p, _int, _p, _int, C.POINTER(_int)],
+    "nl_chain_begin_unordered": [_p, _int],
+    "nl_chain_sample": [_p, _int, _p, _i64, _i64, _i64, _f64, _f64, _f64],
+    "nl_chain_estimates": [_p, _p, _int],
+    "nl_chain_walk": [_p, _int, _p, _i64, _i64, _i64, _f64, _f64, _f64, _i64, _i64],
     "nl_pinned_alloc": [C.POINTER(_p), _i64],
     "nl_host_register": [_p, _i64],
     "nl_input_load_async": [_p, _int, _p, _int],
@@ -618,19 +623,30 @@ class Context(_Handle):
     def gauss_commit(self):
         self._call("nl_gauss_commit")
 
-    def gauss_step(self, wz, wy, wx, z0=0, z1=None, ahead=False):
-        """ahead=True: enqueue the step on the side stream; it becomes current at gauss_commit()."""
-        z1 = self.shape[0] if z1 is None else z1
-        args = []
-        keep = []
-        for w in (wz, wy, wx):
+    @staticmethod
+    def _weight_args(ws):
+        args, keep = [], []
+        for w in ws:
             if w is None:
                 args += [None, 0]
             else:
                 w = np.ascontiguousarray(w, dtype=np.float64)
                 keep.append(w)
                 args += [_ptr(w), (len(w) - 1) // 2]
+        return args, keep
+
+    def gauss_step(self, wz, wy, wx, z0=0, z1=None, ahead=False):
+        """ahead=True: enqueue the step on the side stream; it becomes current at gauss_commit()."""
+        z1 = self.shape[0] if z1 is None else z1
+        args, keep = self._weight_args((wz, wy, wx))
         self._call("nl_gauss_step_ahead" if ahead else "nl_gauss_step", *args, z0, z1)
+
+    def gauss_step_fused(self, wz, wy, wx) -> bool:
+        """Would gauss_step take this step in one kernel (one volume read, one written)?"""
+        args, keep = self._weight_args((wz, wy, wx))
+        fused = _int(0)
+        self._call("nl_gauss_step_fused", *args, C.byref(fused))
+        return bool(fused.value)
 
     def sample_gather(self, field, strides):
         sz, sy, sx = (int(s) for s in strides)
@@ -981,6 +997,27 @@ class Context(_Handle):
         sz, sy, sx = (int(s) for s in strides)
         self._call("nl_chain_scale", sp, sz, sy, sx, float(alpha_sq), float(beta_sq), float(division), float(margin), float(test_scale),
                    int(z0), int(z1))
+
+    # ... with the scales walked out of sigma order (include/nellie_amd.h: nl_chain_begin_unordered)
+    def chain_begin_unordered(self, n_scales):
+        self._call("nl_chain_begin_unordered", int(n_scales))
+        self._chain_n = int(n_scales)
+
+    def chain_sample(self, k, spacing, strides, division, margin, test_scale=1.0):
+        sp = (_f64 * 3)(*[float(s) for s in spacing])
+        sz, sy, sx = (int(s) for s in strides)
+        self._call("nl_chain_sample", int(k), sp, sz, sy, sx, float(division), float(margin), float(test_scale))
+
+    def chain_estimates(self):
+        """The forecast h_mask fraction of every scale sampled so far, < 0 where there is none; one short wait."""
+        frac = np.full(self._chain_n, -1.0, np.float32)
+        self._call("nl_chain_estimates", _ptr(frac), int(frac.size))
+        return frac
+
+    def chain_walk(self, k, spacing, strides, alpha_sq, beta_sq, division, z0=-1, z1=-1):
+        sp = (_f64 * 3)(*[float(s) for s in spacing])
+        sz, sy, sx = (int(s) for s in strides)
+        self._call("nl_chain_walk", int(k), sp, sz, sy, sx, float(alpha_sq), float(beta_sq), float(division), int(z0), int(z1))
 
     def chain_flush(self):
         self._call("nl_chain_flush")

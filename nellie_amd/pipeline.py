@@ -228,6 +228,40 @@ class FrameTrace:
 
 
 # ----------------------------------------------------------------------------- the pipeline
+def run_scale_schedule(n, order, step, walk, choose):
+    """A frame of n scales inside three Gaussian volumes: step(k) runs cascade step k and its first sampling round (sigma order), walk(k)
+    walks a sampled scale.  A volume is busy while its scale waits for the walk, and the newest one while a step still needs it as its
+    source; steps run ahead while a volume is free.  The LAST step also wants its third volume dead (it pre-zeroes the label volume
+    there), so it waits until only its own source is pending -- unless an explicit order asks for the last scale earlier.
+    order: a permutation of range(n), or None: choose(pending, steps_left) picks.  False: the order does not fit (nothing run twice)."""
+    pending, done, newest, pos = [], 0, None, 0
+    while pos < n:
+        busy = set(pending) | ({newest} if newest is not None else set())
+        can_step = done < n and len(busy) <= 2
+        want = order[pos] if order is not None else None
+        if can_step and done == n - 1 and not set(pending) <= {newest}:
+            can_step = want is not None and want not in pending
+        if can_step:
+            step(done)
+            pending.append(done)
+            newest = done
+            done += 1
+            continue
+        if want is None:
+            want = choose(list(pending), n - done)
+        if want not in pending:
+            return False
+        walk(want)
+        pending.remove(want)
+        pos += 1
+    return True
+
+
+def scale_order_fits(order) -> bool:
+    """Can the scales be walked in this order (a permutation of range(n)) inside three Gaussian volumes?"""
+    return run_scale_schedule(len(order), list(order), lambda k: None, lambda k: None, None)
+
+
 class FramePipeline:
     """One (Z, Y, X) frame on one GPU, resident in HBM across Filter and Label."""
 
@@ -570,7 +604,23 @@ class FramePipeline:
         deltas = list(cascade_deltas(sigmas, zr))
         if self.two_d:
             deltas = [(0.0, d[1], d[2]) for d in deltas]          # sigma_vec = (s, s): no Z axis (filtering.py:281-282)
-        ctx.chain_begin(len(sigmas))
+        order = self._scale_order(deltas)            # None: sigma order
+        if order is None:
+            self._scales_in_sigma_order(p, spacing, strides, deltas)
+        else:
+            self._scales_out_of_order(p, spacing, strides, deltas, order)
+        return self._chain_epilogue(strides, sigmas)
+
+    # tests: {sigma index: factor on that scale's predicted threshold} -- a bracket miss in one scale of the chain
+    _chain_test_scales = {}
+
+    def _chain_test_scale(self, k):
+        return self._chain_test_scales.get(k, self._one_pass_test_scale)
+
+    def _scales_in_sigma_order(self, p, spacing, strides, deltas):
+        ctx = self.ctx
+        n = len(deltas)
+        ctx.chain_begin(n)
         # No cascade step runs ahead here: that device (sharded.py) fills the GPU while the host waits for a scale's collectives,
         # and the chain has no such waits -- beside the walk the step only competes with it (measured on a 128 x 2048 x 2048 slab:
         # 34.1 ms/step with a step running ahead, 29.9 without; the synchronous path: 31.6 / 30.4).
@@ -593,16 +643,88 @@ class FramePipeline:
             ctx.gauss_step(*ws, z0=z0, z1=z1, **({"ahead": True} if on_side else {}))
             return True
 
-        for k in range(len(sigmas)):
+        for k in range(n):
             if ahead:
                 ctx.gauss_commit()
             else:
                 cascade_step(k, False)
             self._after_cascade_step(k)
-            ahead = run_ahead and k + 1 < len(sigmas) and cascade_step(k + 1, True)
+            ahead = run_ahead and k + 1 < n and cascade_step(k + 1, True)
             vz0, vz1 = self._vess_range()
             ctx.chain_scale(spacing, strides, float(p.alpha_sq), float(p.beta_sq), float(p.frob_thresh_division), margin,
-                            self._one_pass_test_scale, z0=vz0, z1=vz1)
+                            self._chain_test_scale(k), z0=vz0, z1=vz1)
+
+    # ---- scales walked out of sigma order (csrc/nellie_hip.hip: nl_chain_begin_unordered) --------------------------
+    # NELLIE_SCALE_ORDER, read per frame: unset / "auto" = most selective pending mask first, "sigma" = sigma order, "3,2,1,4,5" = that
+    # order (1-based sigma indices), refused if it does not fit three Gaussian volumes.  Whole 3-D frames on one context whose cascade
+    # steps are all fused; every other frame keeps sigma order.
+    _scale_reorder_ok = True             # (a Z-slab pipeline: no)
+    last_scale_order = None              # tests / tools: the walk order of the last frame (0-based), None in sigma order
+    _all_steps_fused = {}
+
+    def _scale_order(self, deltas):
+        """None: sigma order.  "auto", or a schedulable 0-based permutation."""
+        self.last_scale_order = None
+        env = os.environ.get("NELLIE_SCALE_ORDER", "auto").strip().lower() or "auto"
+        if env == "sigma" or not self._scale_reorder_ok or self.two_d or not hasattr(self.ctx, "chain_begin_unordered"):
+            return None
+        if self._chain_ahead(int(np.prod(self.shape))):
+            return None                  # (small frames: the next cascade step runs beside the walk, on the two free volumes)
+        key = (tuple(deltas), os.environ.get("NELLIE_GAUSS_FUSED"))
+        if key not in self._all_steps_fused:          # (asked once per cascade: the frame's first kernel waits for this function)
+            self._all_steps_fused = {key: all(all(s > 0 for s in d) and self.ctx.gauss_step_fused(*[gaussian_weights(s) for s in d])
+                                              for d in deltas)}
+        if not self._all_steps_fused[key]:
+            return None
+        if env == "auto":
+            return "auto"
+        n = len(deltas)
+        try:
+            order = [int(t) - 1 for t in env.split(",")]
+        except ValueError:
+            raise ValueError(f"NELLIE_SCALE_ORDER={env!r}: expected auto, sigma or a permutation such as 3,2,1,4,5") from None
+        if sorted(order) != list(range(n)):
+            raise ValueError(f"NELLIE_SCALE_ORDER={env!r} is not a permutation of the frame's {n} scales (1..{n})")
+        if not scale_order_fits(order):
+            raise ValueError(f"NELLIE_SCALE_ORDER={env!r} cannot be scheduled inside three Gaussian volumes: a scale's walk can be "
+                             f"delayed by two cascade steps at most")
+        return order
+
+    def _scales_out_of_order(self, p, spacing, strides, deltas, order):
+        ctx = self.ctx
+        n = len(deltas)
+        ctx.chain_begin_unordered(n)
+        division = float(p.frob_thresh_division)
+        est = {}
+        walked = []
+
+        def step(k):
+            ws = [gaussian_weights(d) for d in deltas[k]]
+            z0, z1 = self._gauss_range((len(ws[0]) - 1) // 2)
+            ctx.gauss_step(*ws, z0=z0, z1=z1)
+            ctx.chain_sample(k, spacing, strides, division, self.one_pass_margin, self._chain_test_scale(k))
+
+        def walk(k):
+            vz0, vz1 = self._vess_range()
+            ctx.chain_walk(k, spacing, strides, float(p.alpha_sq), float(p.beta_sq), division, z0=vz0, z1=vz1)
+            walked.append(k)
+
+        def choose(pending, steps_left):
+            # the smallest forecast mask fraction; ties and missing forecasts: sigma order.  A forecast costs one short wait, taken
+            # only while a cascade step is still to come (the frame's last two walks are thin either way)
+            if len(pending) > 1 and steps_left and any(k not in est for k in pending):
+                for k, f in enumerate(ctx.chain_estimates()):
+                    if f >= 0:
+                        est[k] = float(f)
+            if any(k not in est for k in pending):
+                return min(pending)
+            return min(pending, key=lambda k: (est[k], k))
+
+        run_scale_schedule(n, None if order == "auto" else order, step, walk, choose)
+        self.last_scale_order = walked
+
+    def _chain_epilogue(self, strides, sigmas) -> bool:
+        ctx = self.ctx
         # filter()'s percentile threshold reads lattice samples of the result: their compaction is enqueued BEFORE the wait, so it
         # runs while the host waits for the chain's records and repeats its decisions (one round trip less per frame)
         # Round 4: with the percentile selected on the device (nl_tail_enqueue) the WHOLE epilogue is enqueued before the wait -- the

@@ -231,6 +231,7 @@ class RcclComm:
 
 class ShardedFramePipeline(FramePipeline):
     _tail_ok = False            # the percentile samples are gathered across the ranks (pipeline.py: _scales_on_the_device)
+    _scale_reorder_ok = False   # a slab's cascade steps wait for ghost planes, in sigma order (pipeline.py: _scale_order)
 
     def __init__(self, gshape, rank, world, comm_factory, params: FilterParams, device: int = 0, ctx_factory=None, halo=None,
                  halo_mode=None):
