@@ -31,16 +31,20 @@ def clean(skel, ndim):
     return np.where(ambiguous & inner, 0, skel)
 
 
-def seed_rank(frangi):
-    """Sort key of the seeding rule: larger is better; NaN above every number, -0.0 equal to 0.0."""
-    f = np.asarray(frangi, np.float32).ravel() + np.float32(0.0)
+def seed_rank(frangi, nan_highest=True, zeros_equal=True):
+    """Sort key of the seeding rule: larger is better; NaN above every number, -0.0 equal to 0.0.
+    nan_highest=False, zeros_equal=False: other rules (NaN below every number; -0.0 below 0.0), which the tests must tell apart."""
+    f = np.asarray(frangi, np.float32).ravel()
+    if zeros_equal:
+        f = f + np.float32(0.0)
     u = f.view(np.uint32).astype(np.uint64)
     key = np.where(u & 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
-    return np.where(np.isnan(f), 0xFFFFFFFF, key).astype(np.uint64)
+    return np.where(np.isnan(f), 0xFFFFFFFF if nan_highest else 0, key).astype(np.uint64)
 
 
-def seed(skel_clean, labels, frangi):
-    """Every label > 0 without a voxel in skel_clean gets one at the maximum of frangi over its voxels."""
+def seed(skel_clean, labels, frangi, lowest_index=True, nan_highest=True, zeros_equal=True):
+    """Every label > 0 without a voxel in skel_clean gets one at the maximum of frangi over its voxels.  The three keywords are the
+    rule among equal maxima, NaNs and signed zeros; the defaults are the device's."""
     out = np.array(skel_clean, copy=True)
     lab = np.asarray(labels).ravel()
     have = np.unique(out)
@@ -48,12 +52,12 @@ def seed(skel_clean, labels, frangi):
     missing = missing[missing > 0]
     if missing.size == 0:
         return out, 0
-    rank = seed_rank(frangi)
+    rank = seed_rank(frangi, nan_highest, zeros_equal)
     flat = out.reshape(-1)
     for L in missing:
         idx = np.flatnonzero(lab == L)
         r = rank[idx]
-        flat[idx[np.flatnonzero(r == r.max())[0]]] = L
+        flat[idx[np.flatnonzero(r == r.max())[0 if lowest_index else -1]]] = L
     return out, int(missing.size)
 
 
