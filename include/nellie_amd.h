@@ -754,6 +754,32 @@ int nl_branchfeat_regions_rows(nl_branchfeat *branchfeat, const void *labels, in
 int nl_branchfeat_fetch_regions(nl_branchfeat *branchfeat, int64_t *labels, int64_t *sums, int64_t *mode, char *err, size_t errlen);
 int nl_branchfeat_kernel_ms(nl_branchfeat *branchfeat, float *ms, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ adjacency maps -------- */
+/* The edge lists of Hierarchy._save_adjacency_maps (nellie/feature_extraction/hierarchical.py): every list is (m, 2) int64 rows
+   (row, column), ascending in the row.  The object has its own stream and buffers and no frame shape.  An operation computes its
+   rows on the device and reports their number; nl_adjacency_fetch downloads the rows of the last operation.
+   nl_adjacency_pairs  : labels (n elements, NL_I32 or NL_I64) -> (i, labels[i] - bias) for every i with labels[i] > 0.
+   nl_adjacency_expand : the CSR of one list of values per row (offsets: n_rows + 1 entries that start at 0, do not decrease and end
+                         at the number of values; otherwise NL_EINVAL before any launch) -> (row, value), the values of a row in
+                         their order.
+   nl_adjacency_lookup : (i, j) with j the last position of child[i] in parent (p labels), for every child that occurs there.  A
+                         child above the largest parent label is NL_EINVAL, the message naming its row and label (found by the
+                         kernel, read by the host afterwards; the object stays usable); so is a negative label on either side
+                         (checked on the host).  No parents: no rows.  Labels are at most 2^31 - 2.
+   nl_adjacency_fetch  : out (n_edges, 2) int64 of the last operation (NL_ESTATE without one).
+   nl_adjacency_kernel_ms : ms[3], device time of the last call of pairs, expand and lookup.  Transfers excluded.
+   At most 2^31 - 1 edges per list. */
+typedef struct nl_adjacency nl_adjacency;
+int nl_adjacency_create(nl_adjacency **out, int device, char *err, size_t errlen);
+int nl_adjacency_destroy(nl_adjacency *adjacency);
+int nl_adjacency_pairs(nl_adjacency *adjacency, const void *labels, int dtype, int64_t n, int64_t bias, int64_t *n_edges, char *err, size_t errlen);
+int nl_adjacency_expand(nl_adjacency *adjacency, const int64_t *offsets, const int64_t *values, int64_t n_rows, int64_t *n_edges, char *err,
+                        size_t errlen);
+int nl_adjacency_lookup(nl_adjacency *adjacency, const int64_t *child, int64_t n, const int64_t *parent, int64_t p, int64_t *n_edges, char *err,
+                        size_t errlen);
+int nl_adjacency_fetch(nl_adjacency *adjacency, int64_t *out, char *err, size_t errlen);
+int nl_adjacency_kernel_ms(nl_adjacency *adjacency, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit
    Hessians h6[n][6] = (hxx,hxy,hxz,hyy,hyz,hzz) writes out4[n][4] = (l1,l2,l3 sorted by |.|, Frangi

@@ -4,11 +4,16 @@ What the five feature levels share: `Level`, the life-cycle of one level (its de
 in order, one loop as the reference's (hierarchical.py:538-566); and `write_table`, the one writer of the five feature tables by
 the reference's saving rule (`feature_frames`; hierarchical.py:279-337, 611-625).
 
-The level modules import this one; it imports none of them.
+`Hierarchy` is the drop-in for the reference's class of that name (hierarchical.py:44-608): a `LevelDriver` over all five levels
+that then writes the adjacency maps.  `adjacency_maps` builds those six edge lists (hierarchical.py:433-536) on the device
+(csrc/adjacency.inc).
+
+The level modules import this one; it imports none of them: `Hierarchy` looks its levels up when it is first asked for them.
 """
 from __future__ import annotations
 
 import os
+import pickle
 
 import numpy as np
 
@@ -190,3 +195,91 @@ class LevelDriver:
                 self.viewer.status = "Saving features to csv files."
             write_table(level, self.im_info.pipeline_paths[level.table_key], level.table_labels())
         return level
+
+
+ADJACENCY_KEYS = ("v_b", "v_n", "v_o", "n_b", "n_o", "b_o")         # the pickle's keys, in the reference's order
+
+
+def adjacency_maps(hierarchy, device_index: int = 0, kernel_ms=None):
+    """The reference's adjacency maps (hierarchical.py:433-536) of any object with its attributes (`voxels`, `nodes`, `branches`,
+    `components`, `skip_nodes`): {key: one (m, 2) int64 array per frame} for v_b (voxel, branch label - 1), v_n (voxel, every node of
+    its list), v_o (voxel, component label), n_b, n_o and b_o (row, position of its label among the parent level's labels); v_n, n_b
+    and n_o are empty lists under skip_nodes.  The frame counts are the reference's: len(voxels.time) for the voxel lists,
+    len(nodes.time) for the node lists, len(branches.time) for b_o.  v_n comes from `voxels.node_labels_csr[t]` where that exists,
+    else from `voxels.node_labels[t]` (a None entry is an empty list).  One device handle serves all frames.
+    Differences: a child label above its parents' largest raises ValueError (IndexError in the reference), a negative label raises
+    ValueError (numpy would wrap it around).  `kernel_ms`: a dict that receives the device time per operation, summed."""
+    from nellie_amd import hipnative
+    from nellie_amd.feature_extraction.nodes import _as_csr
+    require_gpu()
+    v, n, b, c = hierarchy.voxels, hierarchy.nodes, hierarchy.branches, hierarchy.components
+    skip_nodes = bool(hierarchy.skip_nodes)
+    maps = {key: [] for key in ADJACENCY_KEYS}
+    ms = dict.fromkeys(hipnative.Adjacency.PARTS, 0.0)
+    adj = hipnative.Adjacency(device=device_index)
+
+    def timed(op, *args):
+        out = getattr(adj, op)(*args)
+        ms[op] += adj.kernel_ms_parts()[op]
+        return out
+
+    try:
+        csr = getattr(v, "node_labels_csr", None)
+        for t in range(len(v.time)):
+            if not skip_nodes:
+                if csr is not None and len(csr) > t:
+                    off, val = _as_csr(tuple(csr[t]))
+                else:
+                    off, val = _as_csr([() if a is None else a for a in v.node_labels[t]])
+                maps["v_n"].append(timed("expand", off, val))
+            maps["v_b"].append(timed("pairs", np.asarray(v.branch_labels[t]), 1))
+            maps["v_o"].append(timed("pairs", np.asarray(v.component_labels[t]), 0))
+        if not skip_nodes:
+            for t in range(len(n.time)):
+                maps["n_b"].append(timed("lookup", np.asarray(n.branch_label[t]), np.asarray(b.branch_label[t])))
+                maps["n_o"].append(timed("lookup", np.asarray(n.component_label[t]), np.asarray(c.component_label[t])))
+        for t in range(len(b.time)):
+            maps["b_o"].append(timed("lookup", np.asarray(b.component_label[t]), np.asarray(c.component_label[t])))
+    finally:
+        adj.close()
+    if kernel_ms is not None:
+        kernel_ms.update(ms)
+    return maps
+
+
+class Hierarchy(LevelDriver):
+    """Drop-in for nellie.feature_extraction.hierarchical.Hierarchy: same constructor arguments and defaults (and `device_index`),
+    same `.run()`, same files -- the five feature tables, written level by level as `ImageFeatures` writes them, and the
+    `adjacency_maps` pickle unless `enable_adjacency` is false.  `low_memory`, `node_chunk_size` and `max_node_mask_elems` are
+    accepted and ignored; there is no CPU engine (`device="cpu"` raises).  The level objects stay in `.voxels`, `.nodes`,
+    `.branches`, `.components` and `.image`; `adjacency_kernel_ms` holds the device time of the last run's edge lists."""
+
+    def __init__(self, im_info, skip_nodes: bool = True, viewer=None, use_gpu: bool = True, low_memory: bool = False,
+                 enable_motility: bool = True, enable_adjacency: bool = True, device: str = None, node_chunk_size: int = None,
+                 max_node_mask_elems: int = int(5e7), device_index: int = 0):
+        super().__init__(im_info, skip_nodes=skip_nodes, enable_motility=enable_motility, device=device, device_index=device_index, viewer=viewer)
+        self.use_gpu = True
+        self.low_memory = low_memory
+        self.enable_adjacency = enable_adjacency
+        self.node_chunk_size = node_chunk_size
+        self.max_node_mask_elems = int(max_node_mask_elems)
+        self.adjacency_kernel_ms = {}
+
+    @property
+    def levels(self):
+        from nellie_amd.feature_extraction.image import ImageFeatures
+        return ImageFeatures.levels
+
+    def _save_adjacency_maps(self):
+        edges = adjacency_maps(self, device_index=self.device_index, kernel_ms=self.adjacency_kernel_ms)
+        with open(self.im_info.pipeline_paths["adjacency_maps"], "wb") as f:
+            pickle.dump(edges, f)
+
+    def run(self):
+        super().run()
+        if self.viewer is not None:
+            self.viewer.status = "Finalizing run."
+        if self.enable_adjacency:
+            self._save_adjacency_maps()
+        if self.viewer is not None:
+            self.viewer.status = "Done!"

@@ -196,6 +196,12 @@ _PROTOS = {
     "nl_branchfeat_regions_rows": [_p, _p, _int, _p, _int, C.POINTER(_i64)],
     "nl_branchfeat_fetch_regions": [_p, _p, _p, _p],
     "nl_branchfeat_kernel_ms": [_p, _p],
+    "nl_adjacency_create": [C.POINTER(_p), _int],
+    "nl_adjacency_pairs": [_p, _p, _int, _i64, _i64, C.POINTER(_i64)],
+    "nl_adjacency_expand": [_p, _p, _p, _i64, C.POINTER(_i64)],
+    "nl_adjacency_lookup": [_p, _p, _i64, _p, _i64, C.POINTER(_i64)],
+    "nl_adjacency_fetch": [_p, _p],
+    "nl_adjacency_kernel_ms": [_p, _p],
     "nl_host_half_round": [_p, _p, _i64],
     "nl_host_half_nansum": [_p, _i64, _int, _p],
     "nl_host_np_sum_f32": [_p, _i64, _p],
@@ -217,6 +223,7 @@ _PLAIN = {
     "nl_voxfeat_destroy": (_int, [_p]),
     "nl_nodefeat_destroy": (_int, [_p]),
     "nl_branchfeat_destroy": (_int, [_p]),
+    "nl_adjacency_destroy": (_int, [_p]),
     "nl_thin_decide_host": (_int, [_p, _i64, _p]),
 }
 ALL_SYMBOLS = sorted(list(_PROTOS) + list(_PLAIN))
@@ -1692,3 +1699,55 @@ class BranchFeatures(_TimedParts, _Handle):
         labels, sums, mode = np.empty(R, np.int64), np.empty((1 + 3 * D + D * (D + 1) // 2, R), np.int64), np.empty(R, np.int64)
         self._call("nl_branchfeat_fetch_regions", _ptr(labels), _ptr(sums), _ptr(mode))
         return labels, sums, mode
+
+
+class Adjacency(_TimedParts, _Handle):
+    """Device state of the hierarchy's adjacency maps (include/nellie_amd.h nl_adjacency_*): the three operations its six edge
+    lists are made of.  Each returns a C-contiguous (m, 2) int64 array of (row, column) pairs, ascending in the row."""
+
+    PARTS = ("pairs", "expand", "lookup")
+
+    _destroy, _noun, _ms_symbol = "nl_adjacency_destroy", "adjacency object", "nl_adjacency_kernel_ms"
+
+    def __init__(self, device=0):
+        self._create("nl_adjacency_create", int(device))
+
+    @staticmethod
+    def _labels(a, what, keep32=False):
+        """1-D labels as int64 (or as the int32 they are); a cast that would change a value is refused"""
+        a = np.asarray(a)
+        if a.ndim != 1:
+            raise ValueError(f"{what} must be 1-D")
+        if a.dtype == np.int64 or (keep32 and a.dtype == np.int32):
+            return np.ascontiguousarray(a)
+        _refuse_lossy_cast(a, np.dtype(np.int64), what)
+        return np.ascontiguousarray(a, dtype=np.int64)
+
+    def _fetch(self, m) -> np.ndarray:
+        out = np.empty((int(m.value), 2), np.int64)
+        self._call("nl_adjacency_fetch", _ptr(out))
+        return out
+
+    def pairs(self, labels, bias=0) -> np.ndarray:
+        """(i, labels[i] - bias) for every i with labels[i] > 0"""
+        lab = self._labels(labels, "labels", keep32=True)
+        m = _i64(0)
+        self._call("nl_adjacency_pairs", _ptr(lab), DTYPE_CODES[lab.dtype], lab.size, int(bias), C.byref(m))
+        return self._fetch(m)
+
+    def expand(self, offsets, values) -> np.ndarray:
+        """(row, value) for every value of the CSR: offsets starts at 0, does not decrease and ends at len(values)"""
+        off, val = self._labels(offsets, "offsets"), self._labels(values, "values")
+        if off.size < 1 or int(off[-1]) != val.size:
+            raise ValueError("offsets must hold at least one entry and end at len(values)")
+        m = _i64(0)
+        self._call("nl_adjacency_expand", _ptr(off), _ptr(val), off.size - 1, C.byref(m))
+        return self._fetch(m)
+
+    def lookup(self, child_labels, parent_labels) -> np.ndarray:
+        """(i, j) for every child label that occurs among the parents, j its last position there.  ValueError for a child above
+        the parents' largest label (numpy's IndexError in the reference) and for a negative label (which numpy would wrap)."""
+        child, parent = self._labels(child_labels, "child labels"), self._labels(parent_labels, "parent labels")
+        m = _i64(0)
+        self._call("nl_adjacency_lookup", _ptr(child), child.size, _ptr(parent), parent.size, C.byref(m))
+        return self._fetch(m)

@@ -5,8 +5,10 @@ package's Network (reference run.py:85-86) behind Label and writes im_skel / im_
 (its thinning is the one host call: skimage's, or the `skeletonize` callable -- or none with skeletonize="hip"); `markers=True` runs this package's
 Markers stage (reference run.py:88-89; it does not depend on Network) and writes im_marker / im_distance /
 im_border; `tracking=True` then runs this package's HuMomentTracking on them (run.py:91-92) and writes
-flow_vector_array.  Without these keywords the later stages are left to the caller, who finds the two files
-Filter and Label wrote.
+flow_vector_array; `reassign=True` runs this package's VoxelReassigner behind tracking (run.py:94-95) and writes
+im_obj_label_reassigned / im_branch_label_reassigned; `features=True` runs this package's Hierarchy last (run.py:97-98) and writes the
+five feature tables and the adjacency maps.  `full=True` turns all five on: the reference's whole run().  Without these keywords the
+later stages are left to the caller, who finds the two files Filter and Label wrote.
 """
 from __future__ import annotations
 
@@ -124,8 +126,19 @@ def run_streamed(im_info, viewer=None, device_index=0, devices=None, shard=None)
     return im_info
 
 
+def _require_inputs(im_info, keyword, asked, written, with_keywords, stages):
+    """run(<keyword>=True): every file of `written` ({key of pipeline_paths: a requested stage will write it}) that no stage of
+    this call writes must exist already"""
+    if not asked:
+        return
+    missing = [k for k, comes in written.items() if not comes and not os.path.exists(im_info.pipeline_paths[k])]
+    if missing:
+        raise FileNotFoundError(f"run({keyword}=True) needs the files {missing}: run with {with_keywords}, or run {stages} first")
+
+
 def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=None, timeit=False, device="auto",
-        low_memory=False, markers=False, devices=None, shard=None, tracking=False, network=False, skeletonize=None):
+        low_memory=False, markers=False, devices=None, shard=None, tracking=False, network=False, skeletonize=None, reassign=False,
+        features=False, full=False):
     """nellie.run.run's signature (run.py:18-26): `file_info` is a FileInfo (this package's or any object with the same
     fields) from which the ImInfo is built as run.py:49 does; an ImInfo (anything with `pipeline_paths`) or a path / array
     is accepted too.  Returns the ImInfo.
@@ -136,7 +149,13 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
     and raises before anything runs if they do not exist.
     network=True: Network after Label and before Markers; skeletonize: its thinning, a callable(bool ndarray) -> bool ndarray
     (None: skimage.morphology.skeletonize, whose absence raises ImportError before anything runs), or "hip": the 3-D thinning on the
-    device (NotImplementedError for a 2-D image, before any stage runs)."""
+    device (NotImplementedError for a 2-D image, before any stage runs).
+    reassign=True: VoxelReassigner after tracking (skipped, as tracking is, for a stack without T); features=True: Hierarchy
+    (skip_nodes=False) last.  Either needs the files of the stages before it: those that no requested stage will write must exist, or
+    FileNotFoundError names them before anything runs.
+    full=True: network, markers, tracking, reassign and features, the reference's whole run()."""
+    if full:
+        network = markers = tracking = reassign = features = True
     if network and skeletonize is None:
         from nellie_amd.segmentation.networking import _import_skeletonize
         _import_skeletonize()
@@ -153,6 +172,10 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
         missing = [k for k in ("im_marker", "im_distance") if not os.path.exists(im_info.pipeline_paths[k])]
         if missing:
             raise FileNotFoundError(f"run(tracking=True) needs Markers' outputs {missing}: run with markers=True, or run Markers first")
+    _require_inputs(im_info, "reassign", reassign and not im_info.no_t, dict(flow_vector_array=tracking, im_skel_relabelled=network, im_instance_label=True),
+                    "tracking=True and network=True", "HuMomentTracking and Network")
+    _require_inputs(im_info, "features", features, dict(im_skel=network, im_pixel_class=network, im_skel_relabelled=network, im_distance=markers,
+                                                        im_border=markers), "network=True and markers=True", "Network and Markers")
     t0 = time.perf_counter() if timeit else None
     preprocessing = Filter(im_info, remove_edges=remove_edges, device=device, low_memory=low_memory, devices=devices, shard=shard)
     preprocessing.run()
@@ -183,6 +206,18 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
         HuMomentTracking(im_info, device=device, low_memory=low_memory).run()
         if timeit:
             print(f"[timeit] Tracking: {time.perf_counter() - t3:.3f}s")
+    if reassign and not im_info.no_t:
+        from nellie_amd.tracking.voxel_reassignment import VoxelReassigner
+        t4 = time.perf_counter()
+        VoxelReassigner(im_info, device=device, low_memory=low_memory).run()
+        if timeit:
+            print(f"[timeit] VoxelReassigner: {time.perf_counter() - t4:.3f}s")
+    if features:
+        from nellie_amd.feature_extraction.hierarchy import Hierarchy
+        t5 = time.perf_counter()
+        Hierarchy(im_info, skip_nodes=False, device=device, low_memory=low_memory).run()
+        if timeit:
+            print(f"[timeit] Hierarchy: {time.perf_counter() - t5:.3f}s")
     if timeit:
         print(f"[timeit] Total: {time.perf_counter() - t0:.3f}s")
     return im_info
