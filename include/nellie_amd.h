@@ -630,6 +630,45 @@ int nl_reassign_fetch(nl_reassign *reassigner, int which, int64_t *vox, int32_t 
                       char *err, size_t errlen);
 int nl_reassign_kernel_ms(nl_reassign *reassigner, float *ms, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ voxel tracks of a label stack -------- */
+/* LabelTracks of nellie/tracking/all_tracks_for_label.py on the device.  A track set has its own stream
+   and buffers: `mask_slots` frame masks (labels > 0, 1 bit / voxel) that the caller keeps resident and replaces as it sees fit,
+   the seeds, the coordinates of a run and its rows [id, frame, (z,) y, x] (float64).  The coordinates never cross the host; the
+   surviving rows come down once.  A run is seed, begin, the backward steps, the forward steps, one filter call per frame with
+   rows, finish, fetch.
+   nl_tracks_create  : ndim 2 or 3 (nz = 1 for 2), the frame's shape and the number of mask slots.
+   nl_tracks_mask    : the labels > 0 mask of a frame (int32, frame shape) into a slot.
+   nl_tracks_seed    : the seeds: every skip-th voxel in raster order of the slot's mask (use_label = 0) or of labels == label.
+                       labels != NULL: the start frame, uploaded for this call only; it also builds the slot's mask.  Seeding by
+                       label needs it.  n_seeds = their number.
+   nl_tracks_begin   : sizes the run's buffers before any work: n_seeds * (steps + 1) rows per direction (0 steps: the direction
+                       does not run).  Ids are id0 + the seed's index.  NL_ENOMEM when that does not fit.
+   nl_tracks_step    : one frame of a direction.  flow: a field with the direction's rows of frame_from loaded, NULL when there
+                       are none.  When no coordinate finds a row nothing changes and n_rows = 0.  Otherwise a coordinate whose
+                       vector row is all NaN is NaN from here on, every other one moves by + vector (backward: - vector) and emits
+                       [id, frame_to, coord].  first != 0: the direction's first frame -- the coordinates start from the seeds and
+                       a kept one emits [id, frame_from, old coord] before its new row.  Backward steps come first.
+   nl_tracks_filter  : for the rows of one frame: a row stays if its coordinates, rounded half to even, lie inside the frame on a
+                       set bit of the mask in `slot` (slot < 0: the frame is outside the stack, its rows go); a NaN or infinite
+                       coordinate goes.  Also orders the backward rows: by id, within an id by ascending frame.
+   nl_tracks_finish  : one scan and one compaction.  n_rows = rows that stay: the backward ones, then the forward ones as emitted.
+   nl_tracks_fetch   : those rows, (n_rows, 2 + ndim) float64.
+   nl_tracks_kernel_ms : device time of the kernels since the last nl_tracks_seed: ms[0] masks, [1] seeding, [2] flow
+                       interpolation, [3] steps, [4] filter and order, [5] scan and compaction.  Transfers excluded. */
+typedef struct nl_tracks nl_tracks;
+int nl_tracks_create(nl_tracks **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, int mask_slots, char *err, size_t errlen);
+int nl_tracks_destroy(nl_tracks *tracks);
+int nl_tracks_mask(nl_tracks *tracks, int slot, const int32_t *labels, char *err, size_t errlen);
+int nl_tracks_seed(nl_tracks *tracks, int slot, const int32_t *labels, int use_label, int32_t label, int skip, int64_t *n_seeds,
+                   char *err, size_t errlen);
+int nl_tracks_begin(nl_tracks *tracks, int64_t fw_steps, int64_t bw_steps, int64_t id0, char *err, size_t errlen);
+int nl_tracks_step(nl_tracks *tracks, nl_flow *flow, int backward, int first, int64_t frame_from, int64_t frame_to, int64_t *n_rows,
+                   char *err, size_t errlen);
+int nl_tracks_filter(nl_tracks *tracks, int64_t frame, int slot, char *err, size_t errlen);
+int nl_tracks_finish(nl_tracks *tracks, int64_t *n_rows, char *err, size_t errlen);
+int nl_tracks_fetch(nl_tracks *tracks, double *rows, char *err, size_t errlen);
+int nl_tracks_kernel_ms(nl_tracks *tracks, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ voxel-level features -------- */
 /* Voxels of nellie/feature_extraction/hierarchical.py on the device.  The object has its own stream and
    buffers and keeps one frame: mask (1 bit / voxel), the labelled voxels in raster order and their values.

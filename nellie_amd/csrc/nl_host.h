@@ -7,7 +7,7 @@
 //   nellie_markers.hip  Markers                                                                 -> nl_launch_pack_labels
 //   nellie_hip_network.hip  Network behind the thinning (clean, seed, per-object relabel)        -> nw_release
 //   nellie_hip_thin.hip     the 3-D thinning (Lee94 as skimage runs it)                           -> thin_device
-//   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the seven stage handles share nl_stage.h.
+//   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the eight stage handles share nl_stage.h.
 // gfx950 only.
 #pragma once
 #include <stdarg.h>

@@ -173,6 +173,15 @@ _PROTOS = {
     "nl_reassign_pair": [_p, _p, _p, C.POINTER(_i64)],
     "nl_reassign_fetch": [_p, _int, _p, _p, _p, _p],
     "nl_reassign_kernel_ms": [_p, C.POINTER(_f32)],
+    "nl_tracks_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _int],
+    "nl_tracks_mask": [_p, _int, _p],
+    "nl_tracks_seed": [_p, _int, _p, _int, C.c_int32, _int, C.POINTER(_i64)],
+    "nl_tracks_begin": [_p, _i64, _i64, _i64],
+    "nl_tracks_step": [_p, _p, _int, _int, _i64, _i64, C.POINTER(_i64)],
+    "nl_tracks_filter": [_p, _i64, _int],
+    "nl_tracks_finish": [_p, C.POINTER(_i64)],
+    "nl_tracks_fetch": [_p, _p],
+    "nl_tracks_kernel_ms": [_p, _p],
     "nl_voxfeat_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _f64],
     "nl_voxfeat_frame": [_p, _p, _p, _p, _int, _p, _int, C.POINTER(_i64)],
     "nl_voxfeat_fetch_voxels": [_p, _p, _p, _p, _p, _p],
@@ -220,6 +229,7 @@ _PLAIN = {
     "nl_track_destroy": (_int, [_p]),
     "nl_flow_destroy": (_int, [_p]),
     "nl_reassign_destroy": (_int, [_p]),
+    "nl_tracks_destroy": (_int, [_p]),
     "nl_voxfeat_destroy": (_int, [_p]),
     "nl_nodefeat_destroy": (_int, [_p]),
     "nl_branchfeat_destroy": (_int, [_p]),
@@ -1483,6 +1493,64 @@ class Reassigner(_Handle):
 
     def kernel_ms(self) -> float:
         return _kernel_ms(self, "nl_reassign_kernel_ms")
+
+
+class LabelTrackSet(_TimedParts, _Handle):
+    """Device state of the voxel tracks of a label stack (include/nellie_amd.h nl_tracks_*): `mask_slots` frame masks which the
+    caller keeps resident, the seeds, the coordinates of a run and its rows.  A run is seed(), begin(), the backward step()s, the
+    forward step()s, filter() for every frame with rows, finish(), fetch()."""
+
+    _destroy, _noun = "nl_tracks_destroy", "track set"
+    PARTS, _ms_symbol = ("mask", "seed", "flow", "step", "filter", "compact"), "nl_tracks_kernel_ms"
+
+    def __init__(self, shape, mask_slots=1, device=0):
+        self.ndim, self.shape, (nz, ny, nx), _ = _frame_geometry("label frames", (1.0,) * len(shape), shape=shape)
+        self.mask_slots = int(mask_slots)
+        self._create("nl_tracks_create", int(device), self.ndim, nz, ny, nx, self.mask_slots)
+        self.n_seeds = self.n_rows = 0
+
+    def _labels(self, labels):
+        return _frame_array(labels, self.shape, "label frame", "track set", np.int32)
+
+    def mask(self, slot, labels):
+        """the labels > 0 mask of a frame into a slot"""
+        self._call("nl_tracks_mask", int(slot), _ptr(self._labels(labels)))
+
+    def seed(self, slot, labels=None, label=None, skip=1) -> int:
+        """every skip-th voxel, in raster order, of the slot's mask or (label given, with the start frame in `labels`) of
+        labels == label; a frame given in `labels` also becomes the slot's mask.  Returns the number of seeds."""
+        lab = None if labels is None else self._labels(labels)
+        n = _i64(0)
+        self._call("nl_tracks_seed", int(slot), _opt(lab), 0 if label is None else 1, 0 if label is None else int(label), int(skip), C.byref(n))
+        self.n_seeds = int(n.value)
+        return self.n_seeds
+
+    def begin(self, fw_steps, bw_steps, id0=0):
+        self._call("nl_tracks_begin", int(fw_steps), int(bw_steps), int(id0))
+
+    def step(self, flow, backward, first, frame_from, frame_to) -> int:
+        """one frame of a direction with the rows loaded in the FlowField `flow` (None: the frame has none); returns the number of
+        rows it emitted"""
+        n = _i64(0)
+        self._call("nl_tracks_step", flow._h if flow is not None else None, 1 if backward else 0, 1 if first else 0, int(frame_from),
+                   int(frame_to), C.byref(n))
+        return int(n.value)
+
+    def filter(self, frame, slot):
+        """the final filter for the rows of one frame against the mask in `slot` (None: the frame is outside the stack)"""
+        self._call("nl_tracks_filter", int(frame), -1 if slot is None else int(slot))
+
+    def finish(self) -> int:
+        n = _i64(0)
+        self._call("nl_tracks_finish", C.byref(n))
+        self.n_rows = int(n.value)
+        return self.n_rows
+
+    def fetch(self) -> np.ndarray:
+        """the surviving rows [id, frame, (z,) y, x], (n_rows, 2 + ndim) float64"""
+        rows = np.empty((self.n_rows, 2 + self.ndim), np.float64)
+        self._call("nl_tracks_fetch", _ptr(rows))
+        return rows
 
 
 class VoxelFeatures(_TimedParts, _Handle):
