@@ -669,6 +669,38 @@ int nl_tracks_finish(nl_tracks *tracks, int64_t *n_rows, char *err, size_t errle
 int nl_tracks_fetch(nl_tracks *tracks, double *rows, char *err, size_t errlen);
 int nl_tracks_kernel_ms(nl_tracks *tracks, float *ms, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ the analysis overlay -------- */
+/* The overlay of nellie_napari/nellie_analysis.py on the device: a column of a feature table painted onto
+   the labelled voxels of a frame.  An overlay object is made for one frame shape and has its own stream and buffers; the state of
+   the loaded frame (mask, rows, groups) stays until the next load, so another column costs one small upload and the paint.
+   nl_overlay_create : ndim 2 or 3 (nz = 1 for 2) and the frame's shape.
+   nl_overlay_load   : the label frame (int32, frame shape).  Its voxels with label > 0, in raster order, are the rows; n_rows = V.
+   nl_overlay_groups : the rows' groups.  group != NULL: one per row (V ints, -1: none).  Else a CSR: offsets (V + 1 entries from 0,
+                       not decreasing, ending at n_idx) and idx (n_idx group indices, in any order, repeats allowed).  A group
+                       index is 0 .. 2^31 - 2.
+   nl_overlay_values : direct = 0: attr is the column by group index, n_attr entries, more than the largest group index.  A row's
+                       value is the mean of attr[g] over its distinct groups g with attr[g] not NaN, NaN without one.  The sum is
+                       np.sum's over the dense float64 column of n_attr entries, +0.0 where the row has no group or attr is NaN:
+                       pairwise = 0: from +0.0, one add per entry in ascending g; else numpy's pairwise trees over pieces of 8192
+                       entries, added in order.  direct != 0: attr holds the rows' values themselves, n_attr = V.
+   nl_overlay_paint  : the dense frame, one streaming pass.  kind 0: float64, the row's value at a labelled voxel, NaN elsewhere;
+                       1: float32, the value rounded once; 2: uint64 labels, the truncated value, 0 where it is NaN, negative,
+                       infinite or 2^64 and above, 0 elsewhere.
+   nl_overlay_fetch_values : the V values, float64.
+   nl_overlay_fetch_frame  : the painted frame in the element type of its kind.
+   nl_overlay_kernel_ms    : device time of the kernels of the last load (ms[0]), values (ms[1]) and paint (ms[2]) call. */
+typedef struct nl_overlay nl_overlay;
+int nl_overlay_create(nl_overlay **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, char *err, size_t errlen);
+int nl_overlay_destroy(nl_overlay *overlay);
+int nl_overlay_load(nl_overlay *overlay, const int32_t *labels, int64_t *n_rows, char *err, size_t errlen);
+int nl_overlay_groups(nl_overlay *overlay, const int32_t *group, const int64_t *offsets, const int32_t *idx, int64_t n_idx, char *err,
+                      size_t errlen);
+int nl_overlay_values(nl_overlay *overlay, const double *attr, int64_t n_attr, int direct, int pairwise, char *err, size_t errlen);
+int nl_overlay_paint(nl_overlay *overlay, int kind, char *err, size_t errlen);
+int nl_overlay_fetch_values(nl_overlay *overlay, double *values, char *err, size_t errlen);
+int nl_overlay_fetch_frame(nl_overlay *overlay, void *frame, char *err, size_t errlen);
+int nl_overlay_kernel_ms(nl_overlay *overlay, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ voxel-level features -------- */
 /* Voxels of nellie/feature_extraction/hierarchical.py on the device.  The object has its own stream and
    buffers and keeps one frame: mask (1 bit / voxel), the labelled voxels in raster order and their values.

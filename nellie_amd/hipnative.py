@@ -182,6 +182,14 @@ _PROTOS = {
     "nl_tracks_finish": [_p, C.POINTER(_i64)],
     "nl_tracks_fetch": [_p, _p],
     "nl_tracks_kernel_ms": [_p, _p],
+    "nl_overlay_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64],
+    "nl_overlay_load": [_p, _p, C.POINTER(_i64)],
+    "nl_overlay_groups": [_p, _p, _p, _p, _i64],
+    "nl_overlay_values": [_p, _p, _i64, _int, _int],
+    "nl_overlay_paint": [_p, _int],
+    "nl_overlay_fetch_values": [_p, _p],
+    "nl_overlay_fetch_frame": [_p, _p],
+    "nl_overlay_kernel_ms": [_p, _p],
     "nl_voxfeat_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _f64],
     "nl_voxfeat_frame": [_p, _p, _p, _p, _int, _p, _int, C.POINTER(_i64)],
     "nl_voxfeat_fetch_voxels": [_p, _p, _p, _p, _p, _p],
@@ -230,6 +238,7 @@ _PLAIN = {
     "nl_flow_destroy": (_int, [_p]),
     "nl_reassign_destroy": (_int, [_p]),
     "nl_tracks_destroy": (_int, [_p]),
+    "nl_overlay_destroy": (_int, [_p]),
     "nl_voxfeat_destroy": (_int, [_p]),
     "nl_nodefeat_destroy": (_int, [_p]),
     "nl_branchfeat_destroy": (_int, [_p]),
@@ -1551,6 +1560,95 @@ class LabelTrackSet(_TimedParts, _Handle):
         rows = np.empty((self.n_rows, 2 + self.ndim), np.float64)
         self._call("nl_tracks_fetch", _ptr(rows))
         return rows
+
+
+class Overlay(_TimedParts, _Handle):
+    """Device state of the analysis overlay for one frame shape (include/nellie_amd.h nl_overlay_*): the mask and rows of the
+    loaded label frame, the rows' groups, their values and the painted frame.  load(), groups() or groups_csr(), values() or
+    values_direct(), paint(), fetch_values() / fetch_frame(); what an earlier call left stays until load() replaces the frame."""
+
+    _destroy, _noun = "nl_overlay_destroy", "overlay"
+    PARTS, _ms_symbol = ("load", "values", "paint"), "nl_overlay_kernel_ms"
+    KINDS = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.uint64): 2}
+
+    def __init__(self, shape, device=0):
+        self.ndim, self.shape, (nz, ny, nx), _ = _frame_geometry("label frames", (1.0,) * len(shape), shape=shape)
+        self._create("nl_overlay_create", int(device), self.ndim, nz, ny, nx)
+        self.n_rows = None
+        self.painted = None
+
+    def load(self, labels) -> int:
+        """the label frame; returns V, the number of voxels with label > 0: the rows, in raster order"""
+        lab = _frame_array(labels, self.shape, "label frame", "overlay", np.int32)
+        self.n_rows = self.painted = None
+        n = _i64(0)
+        self._call("nl_overlay_load", _ptr(lab), C.byref(n))
+        self.n_rows = int(n.value)
+        return self.n_rows
+
+    def _rows(self):
+        if self.n_rows is None:
+            raise NellieHipError(NL_ESTATE, "the overlay holds no frame")
+        return self.n_rows
+
+    def groups(self, group):
+        """one group index per row, -1 for none"""
+        g = np.asarray(group)
+        if g.shape != (self._rows(),):
+            raise ValueError(f"{g.shape} groups for {self.n_rows} rows")
+        if g.dtype != np.int32:
+            _refuse_lossy_cast(g, np.dtype(np.int32), "groups")
+        self._call("nl_overlay_groups", _ptr(np.ascontiguousarray(g, dtype=np.int32)), None, None, 0)
+
+    def groups_csr(self, offsets, idx):
+        """row r has the groups idx[offsets[r] : offsets[r + 1]], in any order, repeats allowed"""
+        off, val = np.asarray(offsets), np.asarray(idx)
+        if off.shape != (self._rows() + 1,) or val.ndim != 1:
+            raise ValueError(f"{off.shape} offsets for {self.n_rows} rows")
+        for a, dtype, what in ((off, np.int64, "offsets"), (val, np.int32, "group indices")):
+            if a.dtype != dtype:
+                _refuse_lossy_cast(a, np.dtype(dtype), what)
+        self._call("nl_overlay_groups", None, _ptr(np.ascontiguousarray(off, dtype=np.int64)), _ptr(np.ascontiguousarray(val, dtype=np.int32)), val.size)
+
+    def values(self, attr, pairwise=False):
+        """the column by group index (float64, more entries than the largest group index): every row gets the mean over its groups;
+        `pairwise`: the sum follows np.sum over a contiguous column instead of one add per entry"""
+        a = np.ascontiguousarray(attr, dtype=np.float64)
+        if a.ndim != 1:
+            raise ValueError("the column must be 1-D")
+        self._call("nl_overlay_values", _ptr(a), a.size, 0, 1 if pairwise else 0)
+
+    def values_direct(self, values):
+        """the rows' values themselves (float64, one per row)"""
+        a = np.ascontiguousarray(values, dtype=np.float64)
+        if a.shape != (self._rows(),):
+            raise ValueError(f"{a.shape} values for {self.n_rows} rows")
+        self._call("nl_overlay_values", _ptr(a), a.size, 1, 0)
+
+    def paint(self, dtype=np.float64):
+        """the dense frame on the device: float64 or float32 (NaN off the labelled voxels) or uint64 labels (0 there)"""
+        dtype = np.dtype(dtype)
+        if dtype not in self.KINDS:
+            raise TypeError(f"an overlay is painted as float64, float32 or uint64, not {dtype}")
+        self.painted = None
+        self._call("nl_overlay_paint", self.KINDS[dtype])
+        self.painted = dtype
+
+    def fetch_values(self) -> np.ndarray:
+        out = np.empty(self._rows(), np.float64)
+        self._call("nl_overlay_fetch_values", _ptr(out))
+        return out
+
+    def fetch_frame(self, out=None) -> np.ndarray:
+        """the painted frame; `out`: a C-contiguous writeable array of the frame's shape and the painted dtype that receives it"""
+        if self.painted is None:
+            raise NellieHipError(NL_ESTATE, "the overlay holds no painted frame")
+        if out is None:
+            out = np.empty(self.shape, self.painted)
+        if not (isinstance(out, np.ndarray) and out.shape == self.shape and out.dtype == self.painted and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError(f"out must be a C-contiguous writeable {self.painted} array of shape {self.shape}")
+        self._call("nl_overlay_fetch_frame", _ptr(out))
+        return out
 
 
 class VoxelFeatures(_TimedParts, _Handle):
