@@ -670,7 +670,7 @@ int nl_tracks_fetch(nl_tracks *tracks, double *rows, char *err, size_t errlen);
 int nl_tracks_kernel_ms(nl_tracks *tracks, float *ms, char *err, size_t errlen);
 
 /* ------------------------------------------------------------------ the analysis overlay -------- */
-/* The overlay of nellie_napari/nellie_analysis.py on the device (DESIGN.md section 24): a column of a feature table painted onto
+/* The overlay of nellie_napari/nellie_analysis.py on the device (DESIGN.md section 25): a column of a feature table painted onto
    the labelled voxels of a frame.  An overlay object is made for one frame shape and has its own stream and buffers; the state of
    the loaded frame (mask, rows, groups) stays until the next load, so another column costs one small upload and the paint.
    nl_overlay_create : ndim 2 or 3 (nz = 1 for 2) and the frame's shape.
@@ -809,7 +809,23 @@ int nl_nodefeat_kernel_ms(nl_nodefeat *nodefeat, float *ms, char *err, size_t er
                          region, the smallest among equals, -1 when none were given.
    nl_branchfeat_kernel_ms : ms[5], device time: skeleton list and labels, degree and edge counts, border mask and radii, per-label
                          lists with medians and tips (since the last nl_branchfeat_frame), regions (since the last
-                         nl_branchfeat_regions).  Transfers excluded. */
+                         nl_branchfeat_regions).  Transfers excluded.
+   nl_branchfeat_convex  : the convex counts of the loaded regions: per region the number of lattice points in the closed convex hull
+                         of its voxels' diamonds (every voxel centre moved by +-1/2 along every axis), which is skimage's
+                         area_convex / pixel volume; 0 for a 3-D region whose voxel centres lie in one plane (skimage's all-zero
+                         convex image).  Works on the label frame that the last nl_branchfeat_regions / _regions_rows call left
+                         on the device, so it follows that call directly (NL_ESTATE after nl_branchfeat_frame).  Exact integers:
+                         coordinates are below 2^15, doubled box-relative differences below 2^17, facet normals below 2^35 per
+                         component and N . p below 2^54, so int64 holds everything.  The hulls are built on the host.
+   nl_branchfeat_fetch_convex : count (R) int64; facets (R) int64 = facets of every region's hull; rows (R) int64 = rows (z, y) of its
+                         bounding box.  NULL pointers are skipped.
+   nl_branchfeat_convex_ms : ms[4] of the last nl_branchfeat_convex: device time of the row extremes, the per-plane hulls and the
+                         count (transfers excluded), then the host time of the hulls.
+   nl_branchfeat_convex_limits : limits[3]: box rows per workgroup of the count kernel, facets per staging chunk, workgroups per
+                         launch.
+   nl_host_convex_facets : host only: the hull's facets (k, 4) int64 = (N_z, N_y, N_x, d), N . p <= d inside in doubled coordinates
+                         (voxel c -> 2 c), of n voxels coords (n, ndim) int64 in [0, 2^15); k = 0 for a 3-D set of affine rank
+                         < 3.  Writes at most cap facets; *n_facets = k. */
 typedef struct nl_branchfeat nl_branchfeat;
 int nl_branchfeat_create(nl_branchfeat **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, const double *spacing, char *err,
                          size_t errlen);
@@ -824,6 +840,11 @@ int nl_branchfeat_regions_rows(nl_branchfeat *branchfeat, const void *labels, in
                                int64_t *n_regions, char *err, size_t errlen);
 int nl_branchfeat_fetch_regions(nl_branchfeat *branchfeat, int64_t *labels, int64_t *sums, int64_t *mode, char *err, size_t errlen);
 int nl_branchfeat_kernel_ms(nl_branchfeat *branchfeat, float *ms, char *err, size_t errlen);
+int nl_branchfeat_convex(nl_branchfeat *branchfeat, char *err, size_t errlen);
+int nl_branchfeat_fetch_convex(nl_branchfeat *branchfeat, int64_t *count, int64_t *facets, int64_t *rows, char *err, size_t errlen);
+int nl_branchfeat_convex_ms(nl_branchfeat *branchfeat, float *ms, char *err, size_t errlen);
+int nl_branchfeat_convex_limits(int64_t *limits, char *err, size_t errlen);
+int nl_host_convex_facets(const int64_t *coords, int64_t n, int ndim, int64_t *facets, int64_t cap, int64_t *n_facets, char *err, size_t errlen);
 
 /* ------------------------------------------------------------------ adjacency maps -------- */
 /* The edge lists of Hierarchy._save_adjacency_maps (nellie/feature_extraction/hierarchical.py): every list is (m, 2) int64 rows

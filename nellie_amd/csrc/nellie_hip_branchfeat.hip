@@ -1,17 +1,22 @@
 // Translation unit of libnellie_hip.so (gfx950): branch-level features (Branches of nellie/feature_extraction/hierarchical.py).
 // C-ABI in include/nellie_amd.h; kernels in branchfeat.inc.  The object owns its buffers and stream.  It keeps one frame's
 // skeleton list with everything per skeleton voxel and per skeleton label, and one frame's regions (the labels of the full
-// branch-label volume) with their sums.
+// branch-label volume) with their sums and, on request, their convex counts (convex.inc, convex_hull.h).
 #include <math.h>
 #include <string.h>
+#include <chrono>
 #include <vector>
 #include "nl_stage.h"
 #include "branchfeat.inc"
+#include "convex.inc"
+#include "convex_hull.h"
 
 #define BF_MAX_ROWS ((i64)1 << 30)          // skeleton voxels, distinct labels, region voxels of one frame: ranks and offsets are ints
 #define BF_MAX_LABEL (((i64)1 << 31) - 2)   // label values: the presence table has one bit per value
 #define BF_MAX_DIM ((i64)1 << 15)           // extent of a frame whose region sums are taken (branchfeat.inc, bf_region_kernel)
 enum { BF_MS_LIST, BF_MS_DEGREE, BF_MS_RADII, BF_MS_LISTS, BF_MS_REGIONS, BF_MS_PARTS };
+enum { CV_MS_EXTREMES, CV_MS_PLANES, CV_MS_COUNT, CV_MS_HULL, CV_MS_PARTS };
+#define CV_MAX_ROWS ((i64)1 << 28)          // box rows of all regions of one frame (two ints each come back to the host)
 
 struct nl_branchfeat : StageBase {
     int ndim = 3, noff = BF_NOFF3;
@@ -38,13 +43,21 @@ struct nl_branchfeat : StageBase {
     i64 R = 0, reg_rows = 0, acc_fields = 0; bool has_regions = false, has_mode = false;
     i64 *runiq = nullptr; u64 *acc = nullptr, *best = nullptr; u64 *keys = nullptr; i64 keys_cap = 0;
     float ms[BF_MS_PARTS] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    // convex counts of the regions (convex.inc): d_lab still holds the regions' frame while lab_regions
+    bool lab_regions = false, has_convex = false; int reg_dtype = 0;
+    CvBox *cbox = nullptr; i64 *crowoff = nullptr, *cplaneoff = nullptr, *cfacetoff = nullptr; u64 *ccount = nullptr; i64 cv_cap = 0;     // per region (+ 1)
+    int *cxmin = nullptr, *cxmax = nullptr, *ckeep_lo = nullptr, *ckeep_hi = nullptr; i64 crow_cap = 0;                                      // per box row
+    i64 *cfacets = nullptr; i64 cfacet_cap = 0; CvTask *ctasks = nullptr; i64 ctask_cap = 0;
+    std::vector<i64> cv_nfacets, cv_nrows;
+    float cms[CV_MS_PARTS] = {0.f, 0.f, 0.f, 0.f};
 };
 
 extern "C" int nl_branchfeat_destroy(nl_branchfeat *h) {
     if (!h) return NL_OK;
     stage_close(*h, {h->d_lab, h->d_in, h->sbits, h->bbits, h->tbits, h->spre, h->tpre, h->d_wcount, h->d_any, h->d_word, h->scan.d_bsum, h->scan.d_total,
                      h->pres, h->lpre, h->lwcount, h->vox, h->coords, h->label, h->tips, h->lone, h->rank, h->deg, h->radius, h->keys2, h->uniq,
-                     h->first_vox, h->first, h->count, h->off, h->edges, h->comp_l, h->median, h->runiq, h->acc, h->best, h->keys},
+                     h->first_vox, h->first, h->count, h->off, h->edges, h->comp_l, h->median, h->runiq, h->acc, h->best, h->keys,
+                     h->cbox, h->crowoff, h->cplaneoff, h->cfacetoff, h->ccount, h->cxmin, h->cxmax, h->ckeep_lo, h->ckeep_hi, h->cfacets, h->ctasks},
                 {h->scan.h_total});
     delete h;
     return NL_OK;
@@ -176,6 +189,7 @@ extern "C" int nl_branchfeat_frame(nl_branchfeat *h, const void *skel, int skel_
     hipStream_t st = h->stream;
     const i64 n = h->g.n;
     h->has_frame = false;
+    h->lab_regions = false;                                            // the skeleton takes the regions' place on the device
     h->m = h->B = h->n_tips = h->n_lone = 0;
     *n_voxels = *n_labels = *n_tips = *n_lone = 0;
     for (int j = BF_MS_LIST; j <= BF_MS_LISTS; ++j) h->ms[j] = 0.f;
@@ -306,7 +320,7 @@ static int bf_regions(nl_branchfeat *h, bool rows, const void *labels, int dtype
         return nl_fail(err, errlen, NL_EINVAL, "region sums need every extent of the frame to be at most %lld", (long long)BF_MAX_DIM);
     hipStream_t st = h->stream;
     const i64 n = h->g.n;
-    h->has_regions = h->has_mode = false;
+    h->has_regions = h->has_mode = h->has_convex = h->lab_regions = false;
     h->R = 0;
     *n_regions = 0;
     h->ms[BF_MS_REGIONS] = 0.f;
@@ -360,7 +374,8 @@ static int bf_regions(nl_branchfeat *h, bool rows, const void *labels, int dtype
     }
     NL_HIP(hipStreamSynchronize(st));
     h->R = R;
-    h->has_regions = true;
+    h->has_regions = h->lab_regions = true;
+    h->reg_dtype = dtype;
     *n_regions = R;
     return NL_OK;
 }
@@ -400,5 +415,158 @@ extern "C" int nl_branchfeat_fetch_regions(nl_branchfeat *h, int64_t *labels, in
 extern "C" int nl_branchfeat_kernel_ms(nl_branchfeat *h, float *ms, char *err, size_t errlen) {
     if (!h || !ms) return nl_fail(err, errlen, NL_EINVAL, "branch-feature object or ms is NULL");
     for (int j = 0; j < BF_MS_PARTS; ++j) ms[j] = h->ms[j];
+    return NL_OK;
+}
+
+// ---- convex counts ---------------------------------------------------------------------------------------------------------------
+// The convex counts of the loaded regions: works on the label frame the last nl_branchfeat_regions /
+// _regions_rows call left on the device and on its region table, so it follows that call directly (nl_branchfeat_frame in
+// between replaces the frame: NL_ESTATE).  Device: the candidates (row extremes, per-plane hulls) and the count; host: the hull of
+// every region from its candidates (convex_hull.h).
+extern "C" int nl_branchfeat_convex(nl_branchfeat *h, char *err, size_t errlen) {
+    STAGE_ENTER(h, "branch-feature object");
+    if (!h->has_regions || !h->lab_regions) return nl_fail(err, errlen, NL_ESTATE, "no regions loaded, or a frame was loaded after them");
+    hipStream_t st = h->stream;
+    const i64 R = h->R, n = h->g.n;
+    const int D = h->ndim;
+    h->has_convex = false;
+    for (int j = 0; j < CV_MS_PARTS; ++j) h->cms[j] = 0.f;
+    h->cv_nfacets.assign((size_t)R, 0);
+    h->cv_nrows.assign((size_t)R, 0);
+    if (R == 0) { h->has_convex = true; return NL_OK; }
+    // ---- boxes, row and plane offsets
+    std::vector<u64> lohi((size_t)(2 * D * R));
+    NL_HIP(hipMemcpyAsync(lohi.data(), h->acc + R, lohi.size() * 8, hipMemcpyDeviceToHost, st));
+    NL_HIP(hipStreamSynchronize(st));
+    std::vector<CvBox> box((size_t)R);
+    std::vector<i64> rowoff((size_t)R + 1, 0), planeoff((size_t)R + 1, 0);
+    for (i64 r = 0; r < R; ++r) {
+        CvBox &b = box[(size_t)r];
+        for (int a = 0; a < 3; ++a) {
+            const int k = a - (3 - D);                                 // the axis among the frame's own
+            b.lo[a] = k < 0 ? 0 : (int)lohi[(size_t)(k * R + r)];
+            b.ext[a] = k < 0 ? 1 : (int)(lohi[(size_t)((D + k) * R + r)] - lohi[(size_t)(k * R + r)]) + 1;
+        }
+        h->cv_nrows[(size_t)r] = (i64)b.ext[0] * b.ext[1];
+        rowoff[(size_t)r + 1] = rowoff[(size_t)r] + h->cv_nrows[(size_t)r];
+        planeoff[(size_t)r + 1] = planeoff[(size_t)r] + b.ext[0];
+        if (rowoff[(size_t)r + 1] > CV_MAX_ROWS)
+            return nl_fail(err, errlen, NL_EINVAL, "the regions' bounding boxes hold more than %lld rows", (long long)CV_MAX_ROWS);
+    }
+    const i64 rows = rowoff[(size_t)R], planes = planeoff[(size_t)R];
+    if (int rc = stage_grow(&h->cv_cap, R + 1, R + 1, {{&h->cbox, sizeof(CvBox)}, {&h->crowoff, 8}, {&h->cplaneoff, 8}, {&h->cfacetoff, 8}, {&h->ccount, 8}},
+                            err, errlen)) return rc;
+    if (int rc = stage_grow(&h->crow_cap, rows, rows, {{&h->cxmin, 4}, {&h->cxmax, 4}, {&h->ckeep_lo, 4}, {&h->ckeep_hi, 4}}, err, errlen)) return rc;
+    NL_HIP(hipMemcpyAsync(h->cbox, box.data(), (size_t)R * sizeof(CvBox), hipMemcpyHostToDevice, st));
+    NL_HIP(hipMemcpyAsync(h->crowoff, rowoff.data(), ((size_t)R + 1) * 8, hipMemcpyHostToDevice, st));
+    NL_HIP(hipMemcpyAsync(h->cplaneoff, planeoff.data(), ((size_t)R + 1) * 8, hipMemcpyHostToDevice, st));
+    NL_HIP(hipMemsetAsync(h->cxmin, 0x7f, (size_t)rows * 4, st));
+    NL_HIP(hipMemsetAsync(h->cxmax, 0xff, (size_t)rows * 4, st));
+    NL_HIP(hipMemsetAsync(h->ccount, 0, (size_t)R * 8, st));
+    // ---- step 1: candidates
+    const BfLabels lab{h->d_lab, h->reg_dtype, nullptr};
+    if (int rc = stage_start(*h, err, errlen)) return rc;
+    cv_extremes_kernel<<<bf_grid(n), 256, 0, st>>>(lab, n, h->g, h->pres, h->lpre, h->cbox, h->crowoff, h->cxmin, h->cxmax);
+    NL_CHECK_LAUNCH();
+    if (int rc = stage_stop(*h, &h->cms[CV_MS_EXTREMES], err, errlen)) return rc;
+    if (int rc = stage_start(*h, err, errlen)) return rc;
+    cv_plane_kernel<<<bf_grid(planes), 256, 0, st>>>(planes, R, h->cplaneoff, h->cbox, h->crowoff, h->cxmin, h->cxmax, h->ckeep_lo, h->ckeep_hi);
+    NL_CHECK_LAUNCH();
+    if (int rc = stage_stop(*h, &h->cms[CV_MS_PLANES], err, errlen)) return rc;
+    std::vector<int> xmin((size_t)rows), xmax((size_t)rows);
+    NL_HIP(hipMemcpyAsync(xmin.data(), h->cxmin, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    NL_HIP(hipMemcpyAsync(xmax.data(), h->cxmax, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    NL_HIP(hipStreamSynchronize(st));
+    // ---- step 2: the hulls
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<nl_convex::Facet> facets;
+    std::vector<i64> facetoff((size_t)R + 1, 0), cand;
+    std::vector<CvTask> tasks;
+    for (i64 r = 0; r < R; ++r) {
+        const CvBox &b = box[(size_t)r];
+        cand.clear();
+        for (i64 row = 0; row < h->cv_nrows[(size_t)r]; ++row) {
+            const int lo = xmin[(size_t)(rowoff[(size_t)r] + row)], hi = xmax[(size_t)(rowoff[(size_t)r] + row)];
+            const i64 z = row / b.ext[1], y = row % b.ext[1];
+            for (int e = 0; e < 2; ++e) {
+                const int x = e ? hi : lo;
+                if (x < 0 || x == CV_NO_MIN || (e && hi == lo)) continue;
+                if (D == 3) cand.push_back(z);
+                cand.push_back(y);
+                cand.push_back((i64)x - b.lo[2]);
+            }
+        }
+        nl_convex::ch_facets(cand.data(), (i64)cand.size() / D, D, facets);
+        facetoff[(size_t)r + 1] = (i64)facets.size();
+        h->cv_nfacets[(size_t)r] = facetoff[(size_t)r + 1] - facetoff[(size_t)r];
+        if (h->cv_nfacets[(size_t)r] > 0)
+            for (i64 row0 = 0; row0 < h->cv_nrows[(size_t)r]; row0 += CV_WG) tasks.push_back(CvTask{(int)r, (int)row0});
+    }
+    h->cms[CV_MS_HULL] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // ---- step 3: the count
+    const i64 nf = (i64)facets.size(), nt = (i64)tasks.size();
+    if (nt > 0) {
+        if (int rc = stage_grow(&h->cfacet_cap, nf, stage_doubled(h->cfacet_cap, nf), {{&h->cfacets, 4 * 8}}, err, errlen)) return rc;
+        if (int rc = stage_grow(&h->ctask_cap, nt, stage_doubled(h->ctask_cap, nt), {{&h->ctasks, sizeof(CvTask)}}, err, errlen)) return rc;
+        static_assert(sizeof(nl_convex::Facet) == 4 * 8, "a facet is four int64");
+        NL_HIP(hipMemcpyAsync(h->cfacets, facets.data(), (size_t)nf * 32, hipMemcpyHostToDevice, st));
+        NL_HIP(hipMemcpyAsync(h->ctasks, tasks.data(), (size_t)nt * sizeof(CvTask), hipMemcpyHostToDevice, st));
+        NL_HIP(hipMemcpyAsync(h->cfacetoff, facetoff.data(), ((size_t)R + 1) * 8, hipMemcpyHostToDevice, st));
+        if (int rc = stage_start(*h, err, errlen)) return rc;
+        cv_count_kernel<<<(unsigned)(nt < CV_MAX_GRID ? nt : CV_MAX_GRID), CV_WG, 0, st>>>(h->ctasks, nt, h->cbox, h->cfacetoff, h->cfacets, h->ccount);
+        NL_CHECK_LAUNCH();
+        if (int rc = stage_stop(*h, &h->cms[CV_MS_COUNT], err, errlen)) return rc;
+    }
+    NL_HIP(hipStreamSynchronize(st));                                  // the host vectors go away
+    h->has_convex = true;
+    return NL_OK;
+}
+
+// Downloads the convex counts of the loaded regions: count (R) int64, 0 for a 3-D region whose voxel centres lie in one plane;
+// facets (R) int64 = the facets of every region's hull, rows (R) int64 = the rows of its bounding box.  NULL pointers are skipped.
+extern "C" int nl_branchfeat_fetch_convex(nl_branchfeat *h, int64_t *count, int64_t *facets, int64_t *rows, char *err, size_t errlen) {
+    STAGE_ENTER(h, "branch-feature object");
+    if (!h->has_convex) return nl_fail(err, errlen, NL_ESTATE, "no convex counts taken");
+    const size_t R = (size_t)h->R;
+    if (R > 0 && count) {
+        NL_HIP(hipMemcpyAsync(count, h->ccount, R * 8, hipMemcpyDeviceToHost, h->stream));
+        NL_HIP(hipStreamSynchronize(h->stream));
+    }
+    for (size_t r = 0; r < R; ++r) {
+        if (facets) facets[r] = h->cv_nfacets[r];
+        if (rows) rows[r] = h->cv_nrows[r];
+    }
+    return NL_OK;
+}
+
+// ms[4] of the last nl_branchfeat_convex: device time of the row extremes, of the per-plane hulls and of the count (transfers
+// excluded), then the host time of the hulls.
+extern "C" int nl_branchfeat_convex_ms(nl_branchfeat *h, float *ms, char *err, size_t errlen) {
+    if (!h || !ms) return nl_fail(err, errlen, NL_EINVAL, "branch-feature object or ms is NULL");
+    for (int j = 0; j < CV_MS_PARTS; ++j) ms[j] = h->cms[j];
+    return NL_OK;
+}
+
+// limits[3]: the box rows of one workgroup of the count kernel, the facets of one staging chunk, the workgroups of one launch.
+extern "C" int nl_branchfeat_convex_limits(int64_t *limits, char *err, size_t errlen) {
+    if (!limits) return nl_fail(err, errlen, NL_EINVAL, "limits is NULL");
+    limits[0] = CV_WG; limits[1] = CV_CHUNK; limits[2] = CV_MAX_GRID;
+    return NL_OK;
+}
+
+// Host only: the facets (N_z, N_y, N_x, d), N . p <= d inside in doubled coordinates, of the hull of the diamonds of `n` voxels
+// coords (n, ndim) int64 with 0 <= c < 2^15; none for a 3-D set of affine rank < 3.  Writes at most `cap` facets, *n_facets = how
+// many there are.
+extern "C" int nl_host_convex_facets(const int64_t *coords, int64_t n, int ndim, int64_t *facets, int64_t cap, int64_t *n_facets, char *err,
+                                     size_t errlen) {
+    if (!coords || !n_facets || n < 1 || (ndim != 2 && ndim != 3) || (cap > 0 && !facets)) return nl_fail(err, errlen, NL_EINVAL, "bad arguments");
+    for (int64_t i = 0; i < n * ndim; ++i)
+        if (coords[i] < 0 || coords[i] >= BF_MAX_DIM) return nl_fail(err, errlen, NL_EINVAL, "coordinates must lie in [0, %lld)", (long long)BF_MAX_DIM);
+    std::vector<nl_convex::Facet> f;
+    nl_convex::ch_facets((const nl_convex::ci64 *)coords, n, ndim, f);
+    *n_facets = (int64_t)f.size();
+    for (int64_t k = 0; k < cap && k < (int64_t)f.size(); ++k) {
+        facets[4 * k] = f[(size_t)k].nz; facets[4 * k + 1] = f[(size_t)k].ny; facets[4 * k + 2] = f[(size_t)k].nx; facets[4 * k + 3] = f[(size_t)k].d;
+    }
     return NL_OK;
 }

@@ -14,7 +14,8 @@ columns from the integer sums.
 `features_voxels`, `features_nodes` and `features_branches` as the reference's Hierarchy does.
 
 `hierarchy.voxels` and `hierarchy.nodes` may be this package's objects, the reference's or any object with the same lists.
-Differences: `branch_solidity` is NaN; the region columns follow skimage's documented formulas and a negative
+Differences: `branch_solidity` is NaN unless `hierarchy.solidity` is true, when it is the exact restatement of
+skimage's area / area_convex; the region columns follow skimage's documented formulas and a negative
 square-root argument gives 0 where the reference's `except ValueError` gives NaN; the region columns and `reassigned_label` are
 float64 arrays where the reference keeps lists; a frame without branches writes no rows to the table; `hierarchy.low_memory` is
 accepted and ignored.  There is no CPU engine behind these classes (`device="cpu"` raises).
@@ -118,10 +119,12 @@ def region_stats(prefix):
     return tuple(prefix + k[len("branch"):] if k.startswith("branch_") else k for k in REGION_STATS)
 
 
-def region_columns(sums, mode, spacing, D, prefix="branch"):
+def region_columns(sums, mode, spacing, D, prefix="branch", convex=None):
     """{name: (regions,) float64} of REGION_STATS (of region_stats(prefix)) from the exact sums of every region
     (hipnative.BranchFeatures.fetch_regions): skimage's area, extent, centroid and major / minor axis length with `spacing`,
-    restated on n, S_a = sum c_a and Q_ab = sum c_a c_b; mode < 0: no reassigned labels"""
+    restated on n, S_a = sum c_a and Q_ab = sum c_a c_b; mode < 0: no reassigned labels.  `convex`: the int64 convex count of
+    every region (hipnative.BranchFeatures.fetch_convex), from which <prefix>_solidity = area / (convex * P), inf where it is 0;
+    None: NaN"""
     R = sums.shape[1]
     s = [float(v) for v in spacing]
     P = float(np.prod(spacing))
@@ -137,6 +140,9 @@ def region_columns(sums, mode, spacing, D, prefix="branch"):
             f += 1
     area = n * P
     out[prefix + "_area"] = area
+    if convex is not None:
+        with np.errstate(divide="ignore"):
+            out[prefix + "_solidity"] = area / (np.asarray(convex, dtype=np.int64) * P)
     out[prefix + "_extent"] = area / (np.prod(hi - lo + 1, axis=0).astype(np.float64) * P)
     for a in range(D):
         out["zyx"[3 - D + a]] = (S[a] / n) * s[a]
@@ -153,6 +159,34 @@ def region_columns(sums, mode, spacing, D, prefix="branch"):
         out[prefix + "_axis_length_maj"], out[prefix + "_axis_length_min"] = 4.0 * np.sqrt(lam.max(axis=1)), 4.0 * np.sqrt(lam.min(axis=1))
     out["reassigned_label"] = np.where(mode >= 0, mode.astype(np.float64), np.nan)
     return out
+
+
+def convex_of(engine, hierarchy):
+    """(the convex counts of the engine's loaded regions, {"convex": device ms, "convex_hull_host": host ms}) when
+    `hierarchy.solidity` is true, else (None, {})"""
+    if not getattr(hierarchy, "solidity", False):
+        return None, {}
+    engine.convex()
+    ms = engine.convex_ms_parts()
+    return engine.fetch_convex(), dict(convex=ms["extremes"] + ms["planes"] + ms["count"], convex_hull_host=ms["hull"])
+
+
+def convex_counts(labels, spacing=None, device=0):
+    """(region_labels, n, convex_count, solidity) of a 2-D or 3-D label array (an integer dtype), without files: the distinct labels
+    > 0 ascending (int64), their voxel counts (int64), the lattice points in the closed convex hull of their voxels' diamonds (int64,
+    0 for a 3-D region that lies in one plane) and float64 area / area_convex with `spacing` (default 1 per axis), inf where the
+    convex count is 0"""
+    from nellie_amd import hipnative
+    from nellie_amd.stage import require_gpu
+    require_gpu()
+    lab = np.asarray(labels)
+    sp = np.ones(lab.ndim) if spacing is None else np.asarray(spacing, dtype=np.float64)
+    with hipnative.BranchFeatures(lab.shape, sp, device=device) as eng:
+        eng.regions(lab, rows=True)
+        region_labels, sums, mode = eng.fetch_regions()
+        eng.convex()
+        count = eng.fetch_convex()
+    return region_labels, sums[0].copy(), count, region_columns(sums, mode, sp, lab.ndim, convex=count)["branch_solidity"]
 
 
 class Branches(Level):
@@ -228,10 +262,11 @@ class Branches(Level):
         reassigned = getattr(h, "im_branch_reassigned", None)
         eng.regions(h.label_branches[t], None if reassigned is None or h.im_info.no_t else reassigned[t])
         labels, sums, mode = eng.fetch_regions()
-        for k, v in region_columns(sums, mode, h.spacing, D).items():
+        convex, convex_ms = convex_of(eng, h)
+        for k, v in region_columns(sums, mode, h.spacing, D, convex=convex).items():
             getattr(self, k).append(v)
         self.region_label.append(labels)
-        self.kernel_ms.append(dict(eng.kernel_ms_parts(), aggregation=ms))
+        self.kernel_ms.append(dict(eng.kernel_ms_parts(), aggregation=ms, **convex_ms))
 
     def _open(self, device):
         from nellie_amd import hipnative

@@ -18,7 +18,8 @@ a branch is an empty group, whose row is NaN with sum 0.
 Hierarchy does.
 
 `hierarchy.voxels`, `hierarchy.nodes` and `hierarchy.branches` may be this package's objects, the reference's or any object with
-the same lists.  Differences: `organelle_solidity` is NaN; the region columns follow skimage's documented
+the same lists.  Differences: `organelle_solidity` is NaN unless `hierarchy.solidity` is true, when it is the exact restatement of
+skimage's area / area_convex; the region columns follow skimage's documented
 formulas and a negative square-root argument gives 0 where the reference's `except ValueError` gives NaN; the region columns and
 `reassigned_label` are float64 arrays where the reference keeps lists; a frame without components writes no rows to the table;
 `hierarchy.low_memory` is accepted and ignored.  There is no CPU engine behind these classes (`device="cpu"` raises).
@@ -27,7 +28,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from nellie_amd.feature_extraction.branches import BranchFeatures, region_columns, region_stats
+from nellie_amd.feature_extraction.branches import BranchFeatures, convex_of, region_columns, region_stats
 from nellie_amd.feature_extraction.hierarchy import Level
 from nellie_amd.feature_extraction.nodes import aggregate_groups
 from nellie_amd.feature_extraction.voxels import _image_name
@@ -99,6 +100,7 @@ class Components(Level):
             self.kernel_ms.append(dict(regions=eng.kernel_ms_parts()["regions"], aggregation=0.0))
             return
         labels, sums, mode = eng.fetch_regions()
+        convex, convex_ms = convex_of(eng, h)
         self.component_label.append(labels.astype(np.asarray(frame).dtype))
         self.time.append(np.ones(R, dtype=int) * t)
         self.image_name.append(np.ones(R, dtype=object) * _image_name(h.im_info))
@@ -112,9 +114,9 @@ class Components(Level):
             ms += more
         agg, more = self._aggregate(h.branches, label_list, h.branches.component_label[t], t)
         self.aggregate_branch_metrics.append(agg)
-        for k, v in region_columns(sums, mode, h.spacing, eng.ndim, prefix="organelle").items():
+        for k, v in region_columns(sums, mode, h.spacing, eng.ndim, prefix="organelle", convex=convex).items():
             getattr(self, k).append(v)
-        self.kernel_ms.append(dict(regions=eng.kernel_ms_parts()["regions"], aggregation=ms + more))
+        self.kernel_ms.append(dict(regions=eng.kernel_ms_parts()["regions"], aggregation=ms + more, **convex_ms))
 
     def _open(self, device):
         from nellie_amd import hipnative

@@ -122,12 +122,15 @@ def write_table(level, path, labels=None):
 class LevelDriver:
     """Runs the levels listed in `levels` from an ImInfo's files to their tables: opens what the reference's Hierarchy opens
     (hierarchical.py:190-233), then per level builds it (it stays in the attribute the level names), runs it and writes its table,
-    so a failure in a late level leaves the earlier tables on disk."""
+    so a failure in a late level leaves the earlier tables on disk.  `solidity=True` makes `Branches` and `Components` fill their
+    solidity column; it is NaN otherwise."""
 
     levels = ()
 
-    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None):
+    def __init__(self, im_info, skip_nodes: bool = False, enable_motility: bool = True, device: str = "auto", device_index: int = 0, viewer=None,
+                 solidity: bool = False):
         self.im_info = im_info
+        self.solidity = bool(solidity)                           # Branches and Components: exact convex counts instead of NaN
         resolve_device(device)
         self.device = device or "auto"
         self.device_index = int(device_index)
@@ -247,10 +250,21 @@ def adjacency_maps(hierarchy, device_index: int = 0, kernel_ms=None):
     return maps
 
 
-class Hierarchy(LevelDriver):
+class _WithOptions(type):
+    """`Hierarchy.__init__` keeps the reference's parameters and `device_index`, nothing else, so that it stays a drop-in by position
+    and by introspection; what this package adds beyond them is a keyword taken off here: Hierarchy(im_info, ..., solidity=True)."""
+
+    def __call__(cls, *args, solidity: bool = False, **kwargs):
+        obj = super().__call__(*args, **kwargs)
+        obj.solidity = bool(solidity)
+        return obj
+
+
+class Hierarchy(LevelDriver, metaclass=_WithOptions):
     """Drop-in for nellie.feature_extraction.hierarchical.Hierarchy: same constructor arguments and defaults (and `device_index`),
     same `.run()`, same files -- the five feature tables, written level by level as `ImageFeatures` writes them, and the
-    `adjacency_maps` pickle unless `enable_adjacency` is false.  `low_memory`, `node_chunk_size` and `max_node_mask_elems` are
+    `adjacency_maps` pickle unless `enable_adjacency` is false.  The keyword `solidity=True` (default False: the two solidity columns
+    stay NaN) fills them from exact convex counts.  `low_memory`, `node_chunk_size` and `max_node_mask_elems` are
     accepted and ignored; there is no CPU engine (`device="cpu"` raises).  The level objects stay in `.voxels`, `.nodes`,
     `.branches`, `.components` and `.image`; `adjacency_kernel_ms` holds the device time of the last run's edge lists."""
 

@@ -213,6 +213,11 @@ _PROTOS = {
     "nl_branchfeat_regions_rows": [_p, _p, _int, _p, _int, C.POINTER(_i64)],
     "nl_branchfeat_fetch_regions": [_p, _p, _p, _p],
     "nl_branchfeat_kernel_ms": [_p, _p],
+    "nl_branchfeat_convex": [_p],
+    "nl_branchfeat_fetch_convex": [_p, _p, _p, _p],
+    "nl_branchfeat_convex_ms": [_p, _p],
+    "nl_branchfeat_convex_limits": [_p],
+    "nl_host_convex_facets": [_p, _i64, _int, _p, _i64, C.POINTER(_i64)],
     "nl_adjacency_create": [C.POINTER(_p), _int],
     "nl_adjacency_pairs": [_p, _p, _int, _i64, _i64, C.POINTER(_i64)],
     "nl_adjacency_expand": [_p, _p, _p, _i64, C.POINTER(_i64)],
@@ -1865,6 +1870,46 @@ class BranchFeatures(_TimedParts, _Handle):
         labels, sums, mode = np.empty(R, np.int64), np.empty((1 + 3 * D + D * (D + 1) // 2, R), np.int64), np.empty(R, np.int64)
         self._call("nl_branchfeat_fetch_regions", _ptr(labels), _ptr(sums), _ptr(mode))
         return labels, sums, mode
+
+    CONVEX_PARTS = ("extremes", "planes", "count", "hull")
+
+    def convex(self):
+        """takes the convex counts of the regions of the last regions() call, whose label frame is still on the device"""
+        self._call("nl_branchfeat_convex")
+
+    def fetch_convex(self, sizes=False):
+        """count (R) int64: the lattice points in the closed hull of every region's voxel diamonds, 0 for a flat 3-D region; with
+        `sizes` also the facets of every region's hull and the rows of its bounding box, (R) int64 each"""
+        R = self.n_regions
+        count, facets, rows = np.empty(R, np.int64), np.empty(R, np.int64), np.empty(R, np.int64)
+        self._call("nl_branchfeat_fetch_convex", _ptr(count), _ptr(facets), _ptr(rows))
+        return (count, facets, rows) if sizes else count
+
+    def convex_ms_parts(self) -> dict:
+        """of the last convex(): device ms of `extremes`, `planes` and `count`, host ms of `hull`"""
+        ms = (_f32 * len(self.CONVEX_PARTS))()
+        self._call("nl_branchfeat_convex_ms", ms)
+        return dict(zip(self.CONVEX_PARTS, (float(v) for v in ms)))
+
+
+def convex_limits() -> dict:
+    """the sizes of the convex count kernel: box rows per workgroup, facets per staging chunk, workgroups per launch"""
+    lim = np.zeros(3, np.int64)
+    load().call("nl_branchfeat_convex_limits", _ptr(lim))
+    return dict(zip(("rows_per_workgroup", "facets_per_chunk", "workgroups_per_launch"), (int(v) for v in lim)))
+
+
+def host_convex_facets(coords) -> np.ndarray:
+    """(k, 4) int64 facets (N_z, N_y, N_x, d) of the hull of the diamonds of the voxels `coords` (n, 2 or 3), on the host; k = 0 for
+    a flat 3-D set"""
+    c = np.ascontiguousarray(coords, dtype=np.int64)
+    if c.ndim != 2 or c.shape[1] not in (2, 3) or len(c) == 0:
+        raise ValueError(f"coords must be (n >= 1, 2 or 3), got {c.shape}")
+    k = _i64(0)
+    load().call("nl_host_convex_facets", _ptr(c), len(c), c.shape[1], None, 0, C.byref(k))
+    out = np.empty((int(k.value), 4), np.int64)
+    load().call("nl_host_convex_facets", _ptr(c), len(c), c.shape[1], _ptr(out), len(out), C.byref(k))
+    return out
 
 
 class Adjacency(_TimedParts, _Handle):

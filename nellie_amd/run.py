@@ -138,7 +138,7 @@ def _require_inputs(im_info, keyword, asked, written, with_keywords, stages):
 
 def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=None, timeit=False, device="auto",
         low_memory=False, markers=False, devices=None, shard=None, tracking=False, network=False, skeletonize=None, reassign=False,
-        features=False, full=False):
+        features=False, full=False, solidity=False):
     """nellie.run.run's signature (run.py:18-26): `file_info` is a FileInfo (this package's or any object with the same
     fields) from which the ImInfo is built as run.py:49 does; an ImInfo (anything with `pipeline_paths`) or a path / array
     is accepted too.  Returns the ImInfo.
@@ -153,7 +153,9 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
     reassign=True: VoxelReassigner after tracking (skipped, as tracking is, for a stack without T); features=True: Hierarchy
     (skip_nodes=False) last.  Either needs the files of the stages before it: those that no requested stage will write must exist, or
     FileNotFoundError names them before anything runs.
-    full=True: network, markers, tracking, reassign and features, the reference's whole run()."""
+    full=True: network, markers, tracking, reassign and features, the reference's whole run().
+    solidity=True (with features or full): Hierarchy fills `branch_solidity` and `organelle_solidity` from exact convex-hull voxel
+    counts; by default they stay NaN."""
     if full:
         network = markers = tracking = reassign = features = True
     if network and skeletonize is None:
@@ -215,7 +217,7 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
     if features:
         from nellie_amd.feature_extraction.hierarchy import Hierarchy
         t5 = time.perf_counter()
-        Hierarchy(im_info, skip_nodes=False, device=device, low_memory=low_memory).run()
+        Hierarchy(im_info, skip_nodes=False, device=device, low_memory=low_memory, solidity=solidity).run()
         if timeit:
             print(f"[timeit] Hierarchy: {time.perf_counter() - t5:.3f}s")
     if timeit:
