@@ -595,7 +595,11 @@ int nl_host_np_sum_f32(const float *in, int64_t n, float *out, char *err, size_t
    nl_flow_interpolate_dev : the same for n query rows and an output that are already on the field's device (device pointers),
                          in one launch: nothing crosses the host.  The caller's work on the queries must be complete.  With
                          no rows loaded nothing is written and n_found = 0.
-   nl_flow_kernel_ms   : device time of the kernels of the last nl_flow_interpolate(_dev) call, transfers excluded. */
+   nl_flow_kernel_ms   : device time of the kernels of the last nl_flow_interpolate(_dev) call, transfers excluded.
+   nl_flow_grid_info   : the plan of the loaded rows, read back from the device: dims[3] (a 2-D field has a leading axis of one
+                         cell), the number of cells, the cell edge per axis in um (edge[3]; 0 where the plan resolves nothing), the
+                         cell budget the plan was given and the number of rows in the fullest cell.  All 0 with no rows loaded.
+                         Changes nothing. */
 typedef struct nl_flow nl_flow;
 int nl_flow_create(nl_flow **out, int device, int ndim, const double *spacing, double r, char *err, size_t errlen);
 int nl_flow_destroy(nl_flow *field);
@@ -603,6 +607,7 @@ int nl_flow_load(nl_flow *field, const double *coords, const double *vectors, co
 int nl_flow_interpolate(nl_flow *field, const double *queries, int64_t n, double *out, int64_t *n_found, char *err, size_t errlen);
 int nl_flow_interpolate_dev(nl_flow *field, const double *d_queries, int64_t n, double *d_out, int64_t *n_found, char *err, size_t errlen);
 int nl_flow_kernel_ms(nl_flow *field, float *ms, char *err, size_t errlen);
+int nl_flow_grid_info(nl_flow *field, int *dims, int64_t *ncell, double *edge, int64_t *max_cells, int64_t *fullest, char *err, size_t errlen);
 
 /* ------------------------------------------------------------------ voxel reassignment -------- */
 /* nellie/tracking/voxel_reassignment.py on the device.  A reassigner has its own stream and buffers and

@@ -10,6 +10,7 @@ struct nl_flow : StageBase {
     FlowSpacing sp{{1.0, 1.0, 1.0}};
     double r = 0.5;
     i64 n_rows = 0, row_cap = 0;
+    i64 max_cells = 0;                 // the cell budget the last load's plan was given
     double *d_in = nullptr;            // uploaded rows: coords (n, D) | vectors (n, D) | costs (n)
     int *d_cell = nullptr, *d_perm = nullptr;
     FlowRow *d_rows = nullptr;
@@ -80,6 +81,34 @@ extern "C" int nl_flow_load(nl_flow *f, const double *coords, const double *vect
     NL_CHECK_LAUNCH();
     NL_HIP(hipStreamSynchronize(st));   // the host arrays may go away after the call
     f->n_rows = n;
+    f->max_cells = cells;
+    return NL_OK;
+}
+
+// The plan of the rows that are loaded, read back from the device (not on any hot path): dims[3], the number of cells, the cell
+// edge per axis in um (1 / inv; 0 where the plan resolves nothing), the cell budget the plan was given and the number of rows in
+// the fullest cell.  A 2-D field reports a leading axis of one cell.  With no rows loaded everything is 0.
+extern "C" int nl_flow_grid_info(nl_flow *f, int *dims, int64_t *ncell, double *edge, int64_t *max_cells, int64_t *fullest, char *err, size_t errlen) {
+    STAGE_ENTER(f, "flow field");
+    if (!dims || !ncell || !edge || !max_cells || !fullest) return nl_fail(err, errlen, NL_EINVAL, "NULL output");
+    for (int a = 0; a < 3; ++a) { dims[a] = 0; edge[a] = 0.0; }
+    *ncell = *max_cells = *fullest = 0;
+    if (f->n_rows == 0) return NL_OK;
+    FlowGrid g;
+    NL_HIP(hipMemcpyAsync(&g, f->d_grid, sizeof(FlowGrid), hipMemcpyDeviceToHost, f->stream));
+    NL_HIP(hipStreamSynchronize(f->stream));
+    if (g.ncell < 1 || g.ncell > FLOW_MAX_CELLS) return nl_fail(err, errlen, NL_ESTATE, "the flow grid holds %d cells", g.ncell);
+    std::vector<int> start((size_t)g.ncell + 1);
+    NL_HIP(hipMemcpyAsync(start.data(), f->d_start, start.size() * 4, hipMemcpyDeviceToHost, f->stream));
+    NL_HIP(hipStreamSynchronize(f->stream));
+    for (int a = 0; a < 3; ++a) {
+        dims[a] = g.dims[a];
+        edge[a] = g.inv[a] > 0.0 ? 1.0 / g.inv[a] : 0.0;
+    }
+    *ncell = g.ncell;
+    *max_cells = f->max_cells;
+    for (int c = 0; c < g.ncell; ++c)
+        if (start[c + 1] - start[c] > *fullest) *fullest = start[c + 1] - start[c];
     return NL_OK;
 }
 

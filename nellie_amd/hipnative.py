@@ -168,6 +168,7 @@ _PROTOS = {
     "nl_flow_interpolate": [_p, _p, _i64, _p, C.POINTER(_i64)],
     "nl_flow_interpolate_dev": [_p, _p, _i64, _p, C.POINTER(_i64)],
     "nl_flow_kernel_ms": [_p, C.POINTER(_f32)],
+    "nl_flow_grid_info": [_p, _p, C.POINTER(_i64), _p, C.POINTER(_i64), C.POINTER(_i64)],
     "nl_reassign_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _f64],
     "nl_reassign_frame": [_p, _p, _p, _int, C.POINTER(_i64)],
     "nl_reassign_pair": [_p, _p, _p, C.POINTER(_i64)],
@@ -1464,6 +1465,15 @@ class FlowField(_Handle):
 
     def kernel_ms(self) -> float:
         return _kernel_ms(self, "nl_flow_kernel_ms")
+
+    def grid(self) -> dict:
+        """the plan of the loaded rows as the device holds it: dims (3,), ncell, cell_edge (3,) in um (0 where the plan resolves
+        nothing), max_cells (the budget the plan was given) and fullest (rows in the fullest cell); all 0 with no rows loaded"""
+        dims, edge = np.zeros(3, np.int32), np.zeros(3, np.float64)
+        ncell, max_cells, fullest = _i64(0), _i64(0), _i64(0)
+        self._call("nl_flow_grid_info", _ptr(dims), C.byref(ncell), _ptr(edge), C.byref(max_cells), C.byref(fullest))
+        return dict(dims=tuple(int(d) for d in dims), ncell=int(ncell.value), cell_edge=tuple(float(e) for e in edge),
+                    max_cells=int(max_cells.value), fullest=int(fullest.value))
 
 
 class Reassigner(_Handle):

@@ -38,6 +38,21 @@ def test_header_and_binding_agree(lib):
     assert "gfx950" in lib.version()
 
 
+def test_flow_grid_info_is_bound_and_refuses_a_null_field(lib):
+    """nl_flow_grid_info: in the binding's table with the header's six arguments, and a NULL field is an argument error that
+    is reported before any device is looked at"""
+    import ctypes as C
+    from nellie_amd import hipnative
+    assert "nl_flow_grid_info" in _declared_symbols()
+    assert hipnative._PROTOS["nl_flow_grid_info"] == [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                                      C.POINTER(C.c_int64)]
+    assert callable(hipnative.FlowField.grid)
+    dims, edge = np.zeros(3, np.int32), np.zeros(3)
+    ncell, budget, fullest = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    with pytest.raises(ValueError, match="flow field is NULL"):
+        lib.call("nl_flow_grid_info", None, hipnative._ptr(dims), C.byref(ncell), hipnative._ptr(edge), C.byref(budget), C.byref(fullest))
+
+
 def test_no_cpu_fallback_without_gpu(lib):
     from nellie_amd import hipnative
     if lib.device_count() > 0:
