@@ -174,14 +174,9 @@ def _planes(frame, z0, z1):
 
 class _SlabBase:
     """What LocalSlabs and RankSlab share: a ShardedFramePipeline takes its planes out of the whole frame (with the raw
-    ghost planes the first cascade step reads, so no raw plane is exchanged) and puts its own planes into whole-frame outputs."""
-
-    @staticmethod
-    def _filter_one(pipe, frame, params, mask, remove_edges):
-        from nellie_amd.sharded import slab_range
-        o0, o1 = slab_range(pipe.shape[0], pipe.world, pipe.rank)
-        g_lo, g_hi = pipe.raw_ghost_needed()
-        return pipe.filter(_planes(frame, o0 - g_lo, o1 + g_hi), params, mask=mask, remove_edges=remove_edges)
+    ghost planes the first cascade step reads, so no raw plane is exchanged) and puts its own planes into whole-frame outputs.
+    A subclass holds its pipelines in `pipes` and runs a function on each of them with `_each(fn)` -> [fn(pipe), ...]."""
+    _blank = staticmethod(np.empty)         # a whole-frame output nobody handed over (every plane of it is written)
 
     @staticmethod
     def _own(pipe):
@@ -189,16 +184,54 @@ class _SlabBase:
         return slab_range(pipe.shape[0], pipe.world, pipe.rank)
 
     @classmethod
-    def _download(cls, pipe, which, out):
+    def _filter_one(cls, pipe, frame, params, mask, remove_edges):
         o0, o1 = cls._own(pipe)
-        view = out[o0:o1]
-        get = pipe.download_frangi if which == "frangi" else pipe.download_labels
-        if isinstance(view, np.ndarray) and view.flags.c_contiguous and view.flags.writeable:
-            got = get(out=view)
-            if got is not view:             # a context that does not fill `out` in place
-                view[...] = got
-        else:
-            view[...] = get()
+        g_lo, g_hi = pipe.raw_ghost_needed()
+        return pipe.filter(_planes(frame, o0 - g_lo, o1 + g_hi), params, mask=mask, remove_edges=remove_edges)
+
+    def _download(self, which, dtype, out):
+        out = self._blank(self.shape, dtype) if out is None else out
+
+        def one(pipe):
+            o0, o1 = self._own(pipe)
+            view = out[o0:o1]
+            get = pipe.download_frangi if which == "frangi" else pipe.download_labels
+            if isinstance(view, np.ndarray) and view.flags.c_contiguous and view.flags.writeable:
+                got = get(out=view)
+                if got is not view:             # a context that does not fill `out` in place
+                    view[...] = got
+            else:
+                view[...] = get()
+        self._each(one)
+        return out
+
+    @property
+    def trace(self):
+        return self.pipes[0].trace
+
+    def filter(self, frame, params, mask=True, remove_edges=False):
+        return self._each(lambda pipe: self._filter_one(pipe, frame, params, mask, remove_edges))[0]
+
+    def download_frangi(self, out=None):
+        return self._download("frangi", np.float32, out)
+
+    def upload_frangi(self, frangi):
+        self._each(lambda pipe: pipe.upload_frangi(_planes(frangi, *self._own(pipe))))
+
+    def intensity_mask(self, original, thresh):
+        self._each(lambda pipe: pipe.intensity_mask(_planes(original, *self._own(pipe)), thresh))
+
+    def frangi_threshold(self, max_samples=1_000_000, nbins=256):
+        return self._each(lambda pipe: pipe.frangi_threshold(max_samples, nbins))[0]
+
+    def label(self, thr, min_area, fill_holes=True):
+        return self._each(lambda pipe: pipe.label(thr, min_area, fill_holes=fill_holes))[0]
+
+    def download_labels(self, out=None):
+        return self._download("labels", np.int32, out)
+
+    def close(self):
+        self._each(lambda pipe: pipe.close() if pipe is not None else None)
 
 
 class LocalSlabs(_SlabBase):
@@ -223,9 +256,9 @@ class LocalSlabs(_SlabBase):
         def build(r):
             self.pipes[r] = ShardedFramePipeline(self.shape, r, W, comm_factory_of_rank(r), params, device=self.devices[r],
                                                  ctx_factory=ctx_factory, halo=halo, halo_mode=halo_mode)
-        self._each(build)
+        self._each_rank(build)
 
-    def _each(self, fn):
+    def _each_rank(self, fn):
         """fn(rank) on one host thread per slab (the library calls release the GIL; the slabs rendezvous inside them)."""
         out, errs = [None] * self.world, []
 
@@ -243,43 +276,11 @@ class LocalSlabs(_SlabBase):
             raise errs[0]
         return out
 
-    @property
-    def trace(self):
-        return self.pipes[0].trace
-
-    def filter(self, frame, params, mask=True, remove_edges=False):
-        return self._each(lambda r: self._filter_one(self.pipes[r], frame, params, mask, remove_edges))[0]
-
-    def download_frangi(self, out=None):
-        out = np.empty(self.shape, np.float32) if out is None else out
-        self._each(lambda r: self._download(self.pipes[r], "frangi", out))
-        return out
-
-    def upload_frangi(self, frangi):
-        self._each(lambda r: self.pipes[r].upload_frangi(_planes(frangi, *self._own(self.pipes[r]))))
-
-    def intensity_mask(self, original, thresh):
-        self._each(lambda r: self.pipes[r].intensity_mask(_planes(original, *self._own(self.pipes[r])), thresh))
-
-    def frangi_threshold(self, max_samples=1_000_000, nbins=256):
-        return self._each(lambda r: self.pipes[r].frangi_threshold(max_samples, nbins))[0]
-
-    def label(self, thr, min_area, fill_holes=True):
-        return self._each(lambda r: self.pipes[r].label(thr, min_area, fill_holes=fill_holes))[0]
-
-    def download_labels(self, out=None):
-        out = np.empty(self.shape, np.int32) if out is None else out
-        self._each(lambda r: self._download(self.pipes[r], "labels", out))
-        return out
+    def _each(self, fn):
+        return self._each_rank(lambda r: fn(self.pipes[r]))
 
     def barrier(self):
         pass
-
-    def close(self):
-        def shut(r):
-            if self.pipes[r] is not None:
-                self.pipes[r].close()
-        self._each(shut)
 
 
 def _exchange_ids(spec: ShardSpec, n_ids: int, make_id, timeout_s=300.0):
@@ -299,6 +300,7 @@ def _exchange_ids(spec: ShardSpec, n_ids: int, make_id, timeout_s=300.0):
 
 class RankSlab(_SlabBase):
     kind = "rank-slab"
+    _blank = staticmethod(np.zeros)         # this rank's planes into the whole-frame array (the other ranks fill theirs)
 
     def __init__(self, shape, params: FilterParams, spec: ShardSpec, halo_mode=None, halo=None):
         from nellie_amd.sharded import RcclComm, ShardedFramePipeline
@@ -312,46 +314,17 @@ class RankSlab(_SlabBase):
             comm_factory = lambda ctx: RcclComm(ctx, spec.world, spec.rank, uid, uid2=uid2)
         self.pipe = ShardedFramePipeline(self.shape, spec.rank, spec.world, comm_factory, params, device=spec.device,
                                          ctx_factory=spec.ctx_factory, halo=halo, halo_mode=halo_mode)
+        self.pipes = [self.pipe]
         self.barrier()
         if self._id_file and spec.rank == 0:          # every rank holds its communicators (the barrier above ran on them)
             self._id_file[0].remove(self._id_file[1])
 
-    @property
-    def trace(self):
-        return self.pipe.trace
-
-    def filter(self, frame, params, mask=True, remove_edges=False):
-        return self._filter_one(self.pipe, frame, params, mask, remove_edges)
-
-    def download_frangi(self, out=None):
-        """This rank's planes into the whole-frame array (the other ranks fill theirs)."""
-        out = np.zeros(self.shape, np.float32) if out is None else out
-        self._download(self.pipe, "frangi", out)
-        return out
-
-    def upload_frangi(self, frangi):
-        self.pipe.upload_frangi(_planes(frangi, *self._own(self.pipe)))
-
-    def intensity_mask(self, original, thresh):
-        self.pipe.intensity_mask(_planes(original, *self._own(self.pipe)), thresh)
-
-    def frangi_threshold(self, max_samples=1_000_000, nbins=256):
-        return self.pipe.frangi_threshold(max_samples, nbins)
-
-    def label(self, thr, min_area, fill_holes=True):
-        return self.pipe.label(thr, min_area, fill_holes=fill_holes)
-
-    def download_labels(self, out=None):
-        out = np.zeros(self.shape, np.int32) if out is None else out
-        self._download(self.pipe, "labels", out)
-        return out
+    def _each(self, fn):
+        return [fn(self.pipe)]              # one pipe, on the calling thread
 
     def barrier(self):
         """Every rank has reached this point (a one-element all-reduce on the communicator)."""
         self.pipe.comm.allreduce(np.array([1], np.int64), "sum")
-
-    def close(self):
-        self.pipe.close()
 
 
 def plan_engine(shape_zyx, params: FilterParams, devices=None, shard: Optional[ShardSpec] = None, halo_mode=None, label_only=False,

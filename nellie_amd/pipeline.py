@@ -14,7 +14,7 @@ stage API and on-disk layout.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import os
 
@@ -262,6 +262,48 @@ def scale_order_fits(order) -> bool:
     return run_scale_schedule(len(order), list(order), lambda k: None, lambda k: None, None)
 
 
+class FramePlan(NamedTuple):
+    """What the scale loops of one frame share, worked out once per compute_vesselness call."""
+    sigmas: tuple
+    spacing: tuple
+    strides: tuple           # of the threshold sample lattice (max_samples points at most)
+    deltas: tuple            # cascade_deltas; an image's have no Z part: sigma_vec = (s, s) (filtering.py:281-282)
+    alpha_sq: float
+    beta_sq: float
+    frob_thresh: Optional[float]
+    division: object         # frob_thresh_division as given (0 / None: mask = frob > 0)
+    max_samples: int
+
+
+class ChainTail(NamedTuple):
+    """What the scale loops left behind for filter()'s epilogue: nothing, the host samples of the tail field (gathered under the device
+    chain's wait), or an epilogue that nl_tail_enqueue started and _finish_device_tail still has to finish or cancel."""
+    samples: Optional[np.ndarray] = None
+    pending: bool = False
+
+
+class _DeferredMaskCount:
+    """The h_mask count of a scale the one-pass walk completed: its resolve kernel overlaps the next scale's Gaussian, so the count is
+    read (vesselness_count waits for the kernel) only when the next walk is about to start, or at the end of the frame."""
+
+    def __init__(self, pipe):
+        self.pipe, self.entry = pipe, None
+
+    def defer(self, entry: ScaleTrace):
+        self.entry = entry
+
+    def settle(self):
+        if self.entry is not None:
+            self.entry.mask_count = self.pipe._reduce_mask_count(self.pipe.ctx.vesselness_count())
+            self.entry = None
+
+
+# entry points a context may lack (the reduced contexts of the CPU tests, older libraries): asked once per pipeline
+_OPTIONAL_ENTRY_POINTS = ("one_pass_available", "sample_range_hist", "sample_range_hist2", "sample_gather_positive",
+                          "flat_sample_gather_positive", "chain_begin", "chain_available", "chain_begin_unordered",
+                          "sample_gather_positive_begin", "mask_volume_dev", "tail_enqueue", "gauss_commit", "mask_volume_fused")
+
+
 class FramePipeline:
     """One (Z, Y, X) frame on one GPU, resident in HBM across Filter and Label."""
 
@@ -273,18 +315,19 @@ class FramePipeline:
         if len(self.shape) != 3:
             raise ValueError("FramePipeline takes a (Z, Y, X) or a (Y, X) shape")
         self.ctx = ctx if ctx is not None else hipnative.Context(self.shape, device=device)
+        self._ctx_has = frozenset(name for name in _OPTIONAL_ENTRY_POINTS if hasattr(self.ctx, name))
         if self.two_d:
             self.ctx.set_ndim(2)
         self.trace = FrameTrace()
         # One walk over the Hessian per scale instead of two (statistics, then masks): the mask threshold is
         # predicted from the sample lattice and bracketed by a relative margin; a scale whose exact threshold
         # falls outside the bracket is redone the two-pass way, so results never depend on it.
-        self.one_pass = bool(getattr(self.ctx, "one_pass_available", lambda: False)()) and not self.two_d
+        self.one_pass = "one_pass_available" in self._ctx_has and bool(self.ctx.one_pass_available()) and not self.two_d
         self.one_pass_margin = 1e-3
         # range + histogram of a threshold in one device round trip (a Z-slab pipeline reduces the range across ranks
         # between the two passes and keeps them apart)
-        self._chain_hist = hasattr(self.ctx, "sample_range_hist") and os.environ.get("NELLIE_CHAIN_HIST", "1") != "0"
-        self._pair_hist = hasattr(self.ctx, "sample_range_hist2") and os.environ.get("NELLIE_PAIR_HIST", "1") != "0"
+        self._chain_hist = "sample_range_hist" in self._ctx_has and os.environ.get("NELLIE_CHAIN_HIST", "1") != "0"
+        self._pair_hist = "sample_range_hist2" in self._ctx_has and os.environ.get("NELLIE_PAIR_HIST", "1") != "0"
         self.check_device_edges = os.environ.get("NELLIE_CHECK_EDGES", "0") == "1"
         self._one_pass_test_scale = 1.0      # tests: shifts the prediction to force a miss
         try:
@@ -314,17 +357,15 @@ class FramePipeline:
 
     def _positive_lattice_samples(self, fld, strides):
         """arr[::sz, ::sy, ::sx][... > 0] of a device field (filtering.py:348-363), compacted on the device."""
-        f = getattr(self.ctx, "sample_gather_positive", None)
-        if f is not None:
-            return self._gather(f(fld, strides))
+        if "sample_gather_positive" in self._ctx_has:
+            return self._gather(self.ctx.sample_gather_positive(fld, strides))
         sample = self._gather(self.ctx.sample_gather(fld, strides))
         return sample[sample > 0]
 
     def _positive_flat_samples(self, fld, offset, step):
         """flat[offset::step][... > 0] (labelling.py:418-433), compacted on the device."""
-        f = getattr(self.ctx, "flat_sample_gather_positive", None)
-        if f is not None:
-            return self._gather(f(fld, offset, step))
+        if "flat_sample_gather_positive" in self._ctx_has:
+            return self._gather(self.ctx.flat_sample_gather_positive(fld, offset, step))
         sample = self._gather(self.ctx.flat_sample_gather(fld, offset, step))
         return sample[sample > 0]
 
@@ -375,209 +416,238 @@ class FramePipeline:
         """Keep the raw frame resident in HBM; `filter(None, ...)` then starts from device memory."""
         self.ctx.input_load(self._as_frame(frame))
 
-    def _normalised_range(self, spec, max_abs):
-        """(min, max) of the positive NL_FIELD_FROB samples for the exact normalisation, derived from the range the
-        bracket round measured with max_abs := 1: x -> x / max_abs is monotone in float32, so min and max commute with
-        it.  None (measure it) unless the one-pass walk is still valid (no inf) and nothing underflows to 0."""
-        rng = getattr(self, "_raw_frob_range", None)
-        if not spec or rng is None:
-            return None
-        with np.errstate(all="ignore"):
-            mn, mx = rng[0] / np.float32(max_abs), rng[1] / np.float32(max_abs)
-        return (mn, mx) if (mn > 0 and np.isfinite(mx)) else None
+    def _load(self, frame):
+        self.ctx.filter_load(self._as_frame(frame))
+
+    def _restart_frame(self, frame, p: FilterParams):
+        """A frame starts (again: the chain's fallback) from the frame handed over, or from the one load_input() keeps resident."""
+        self.trace = FrameTrace()
+        if frame is None:
+            self.ctx.filter_begin()
+        else:
+            self._load(frame)
+        self._after_load(p)
+
+    def _frame_plan(self, p: FilterParams, max_samples: int) -> FramePlan:
+        sigmas = p.resolved_sigmas()
+        deltas = cascade_deltas(sigmas, z_ratio_of(p.dim_res))
+        if self.two_d:
+            deltas = [(0.0, d[1], d[2]) for d in deltas]          # sigma_vec = (s, s): no Z axis (filtering.py:281-282)
+        return FramePlan(tuple(sigmas), spacing_of(p.dim_res), self._strides(max_samples), tuple(deltas), float(p.alpha_sq), float(p.beta_sq),
+                         p.frob_thresh, p.frob_thresh_division, max_samples)
+
+    # ---- the Gaussian cascade --------------------------------------------------------------------------------------------------------
+    def _cascade_step(self, plan: FramePlan, k: int, ahead: bool) -> bool:
+        """Cascade step k (filtering.py:814-835) -- ahead: on the side stream, where it becomes current at gauss_commit().  False: not
+        run -- the step blurs nothing (all-zero delta), or it was asked to run ahead and writes all three volumes (_step_fits_ahead:
+        it then runs in order at the top of the next scale)."""
+        delta = plan.deltas[k]
+        if not any(s > 0 for s in delta):
+            return False
+        ws = [gaussian_weights(d) for d in delta]
+        if ahead and not self._step_fits_ahead(ws):
+            return False
+        z0, z1 = self._gauss_range(0 if ws[0] is None else (len(ws[0]) - 1) // 2)
+        self.ctx.gauss_step(*ws, z0=z0, z1=z1, **({"ahead": True} if ahead else {}))
+        return True
+
+    def _next_gaussian(self, plan: FramePlan, k: int, ahead: bool, run_ahead: bool) -> bool:
+        """Sigma order: the Gaussian of scale k becomes current (ahead: its step was enqueued during the previous scale), and with
+        run_ahead step k+1 is enqueued at once -- it only reads the Gaussian of THIS scale, so on the side stream it runs beside this
+        scale's sampling and Hessian walk (filtering.py:814-835 has no such dependency either).  -> is step k+1 ahead now?"""
+        if ahead:
+            self.ctx.gauss_commit()
+        else:
+            self._cascade_step(plan, k, False)
+        self._after_cascade_step(k)      # Z slabs: the ghost planes the NEXT step needs start travelling now
+        return bool(run_ahead and k + 1 < len(plan.sigmas) and self._cascade_step(plan, k + 1, True))
+
+    # ---- thresholds from lattice samples ---------------------------------------------------------------------------------------------
+    def _range_hist(self, fld, strides, pre=None, finite_only=False):
+        """Range and 256-bin histogram of the positive lattice samples of a device field -> (mn, mx, npos, counts, edges); counts and
+        edges are None without a positive sample.  One device round trip where nothing sits between the two passes (a single GPU, a
+        fused communicator; pre: its result when it was fetched together with another field's): the device builds numpy's float32 edges
+        itself and they serve the threshold arithmetic too (the GPU tests run with NELLIE_CHECK_EDGES=1: every such chain compares them
+        with numpy's, bit for bit); a degenerate range goes through numpy on the host, which raises numpy's errors.  Otherwise two
+        calls with the cross-rank reductions between them; finite_only: the caller drops a range that is not finite, so its histogram
+        is not asked for."""
+        if self._chain_hist:
+            mn, mx, npos, counts, dev_edges, valid = pre if pre is not None else self.ctx.sample_range_hist(fld, strides, 256)
+            if npos and valid == 1 and self.check_device_edges:
+                assert np.array_equal(dev_edges, histogram_edges(mn, mx, 256)), "device-built histogram edges differ from numpy's"
+            edges = dev_edges if (npos and valid == 1) else (histogram_edges(mn, mx, 256) if npos else None)
+            return mn, mx, npos, counts, edges
+        mn, mx, npos = self._reduce_minmax(*self.ctx.sample_minmax(fld, strides))
+        if npos == 0 or (finite_only and not np.isfinite(mx)):
+            return mn, mx, npos, None, None
+        return (mn, mx, npos) + self._hist_in_range(fld, strides, mn, mx)
+
+    def _hist_in_range(self, fld, strides, mn, mx):
+        """-> (counts, edges) of the positive lattice samples over numpy's 256 bins of [mn, mx]."""
+        edges = histogram_edges(mn, mx, 256)
+        return self._reduce_counts(self.ctx.sample_hist(fld, strides, edges)), edges
 
     def _threshold_from_field(self, fld, strides, known_range=None, pre=None):
         """min(triangle, otsu) over the positive lattice samples of a device field, or None if none.
-        pre: the field's sample_range_hist result when it was fetched together with another field's."""
+        known_range: their (min, max) where the caller has it already; pre: see _range_hist."""
         if known_range is not None:
-            mn, mx, npos = known_range[0], known_range[1], 1
-        elif self._chain_hist:
-            mn, mx, counts, npos, edges = self._range_hist(fld, strides, pre)
+            counts, edges = self._hist_in_range(fld, strides, known_range[0], known_range[1])
+        else:
+            _, _, npos, counts, edges = self._range_hist(fld, strides, pre)
             if npos == 0:
                 return None
-            return float(min_triangle_otsu(counts, edges))
-        else:
-            mn, mx, npos = self._reduce_minmax(*self.ctx.sample_minmax(fld, strides))
-        if npos == 0:
-            return None
-        edges = histogram_edges(mn, mx, 256)
-        counts = self._reduce_counts(self.ctx.sample_hist(fld, strides, edges))
         return float(min_triangle_otsu(counts, edges))
 
-    def _range_hist(self, fld, strides, pre=None):
-        """Range and 256-bin histogram of the positive lattice samples in one device round trip (single GPU: no
-        cross-rank reduction sits between the two passes).  The device builds numpy's float32 edges itself and they serve
-        the threshold arithmetic too (the GPU tests run with NELLIE_CHECK_EDGES=1: every such chain compares them with
-        numpy's, bit for bit); a degenerate range goes through numpy on the host, which raises numpy's errors."""
-        mn, mx, npos, counts, dev_edges, valid = pre if pre is not None else self.ctx.sample_range_hist(fld, strides, 256)
-        if npos and valid == 1 and self.check_device_edges:
-            assert np.array_equal(dev_edges, histogram_edges(mn, mx, 256)), "device-built histogram edges differ from numpy's"
-        edges = dev_edges if (npos and valid == 1) else (histogram_edges(mn, mx, 256) if npos else None)
-        return mn, mx, counts, npos, edges
-
     def _fsq_bracket(self, strides, division, pre=None):
-        """Predicted [lo, hi] for the un-normalised frob_sq threshold of the current scale, or None.
+        """Predicted [lo, hi] for the un-normalised frob_sq threshold of the current scale and the (min, max) of the raw samples it
+        was predicted from -> (lo, hi, raw_range), or None.
         Normalising by 1 instead of the (unknown) global max |H| rescales samples and threshold alike
         (filtering.py:421-444), so the histogram threshold of sqrt(frob_sq) predicts sqrt(fsq_min) up to float32
         rounding -- unless the rounding moves the histogram argmax to another bin, which the bracket then misses."""
         if pre is None:
             self.ctx.set_frob_norm(1.0, 0.0)
-        self._raw_frob_range = None
-        if self._chain_hist:
-            mn, mx, counts, npos, edges = self._range_hist(FIELD_FROB, strides, pre)
-            if npos == 0 or not np.isfinite(mx):
-                return None
-            self._raw_frob_range = (np.float32(mn), np.float32(mx))
-        else:
-            mn, mx, npos = self._reduce_minmax(*self.ctx.sample_minmax(FIELD_FROB, strides))
-            if npos == 0 or not np.isfinite(mx):
-                return None
-            self._raw_frob_range = (np.float32(mn), np.float32(mx))
-            edges = histogram_edges(mn, mx, 256)
-            counts = self._reduce_counts(self.ctx.sample_hist(FIELD_FROB, strides, edges))
+        mn, mx, npos, counts, edges = self._range_hist(FIELD_FROB, strides, pre, finite_only=True)
+        if npos == 0 or not np.isfinite(mx):
+            return None
         t = float(min_triangle_otsu(counts, edges)) * self._one_pass_test_scale / division
         lo, hi = np.float32(t * t * (1.0 - self.one_pass_margin)), np.float32(t * t * (1.0 + self.one_pass_margin))
         if not (np.isfinite(lo) and np.isfinite(hi) and hi > 0):
             return None
-        return float(lo), float(hi)
+        return float(lo), float(hi), (np.float32(mn), np.float32(mx))
 
+    @staticmethod
+    def _normalised_range(raw_range, max_abs):
+        """(min, max) of the positive NL_FIELD_FROB samples for the exact normalisation, derived from the range the
+        bracket round measured with max_abs := 1: x -> x / max_abs is monotone in float32, so min and max commute with
+        it.  None (measure it) when something underflows to 0 or overflows."""
+        with np.errstate(all="ignore"):
+            mn, mx = raw_range[0] / np.float32(max_abs), raw_range[1] / np.float32(max_abs)
+        return (mn, mx) if (mn > 0 and np.isfinite(mx)) else None
+
+    # ---- the scales of a frame -------------------------------------------------------------------------------------------------------
     def compute_vesselness(self, frame, p: FilterParams, mask: bool = True, finish: bool = True):
         """filtering.py:806-853 + 926: leaves `vesselness * masks` on the device; returns #voxels > 0.
         finish=False stops before the product is materialised (see filter()); returns None then."""
-        ctx = self.ctx
+        plan, _ = self._run_scales(frame, p, mask)
+        return self._finish_frame(plan, mask) if finish else None
+
+    def _run_scales(self, frame, p: FilterParams, mask: bool, tail_field=None):
+        """Every scale of a frame (filtering.py:806-853), on the device-resident chain where it applies and the synchronous way where
+        it does not, or where the chain met a condition it leaves to the host.  tail_field: the field whose percentile threshold the
+        caller takes next (filter()); the chain then starts that epilogue under its own wait.  -> (plan, ChainTail)."""
         max_samples = int(p.max_threshold_samples) if p.max_threshold_samples is not None else 0
         if max_samples <= 0:
             raise ValueError("max_threshold_samples must be a positive integer")
-        self.trace = FrameTrace()
-        if frame is None:
-            ctx.filter_begin()          # restart from the frame kept resident by load_input()
-        else:
-            self._load(frame)
-        self._after_load(p)
+        self._restart_frame(frame, p)
+        plan = self._frame_plan(p, max_samples)
+        tail = None
         if self._chain_usable(p, mask):
-            if self._scales_on_the_device(p, max_samples):
-                return self._finish_frame(finish, p, mask)
-            # a condition the device-resident chain leaves to the host turned up: the frame is redone, synchronously
-            self.chain_fallbacks += 1
-            self.trace = FrameTrace()
-            if frame is None:
-                ctx.filter_begin()
-            else:
-                self._load(frame)
-            self._after_load(p)
-        zr = z_ratio_of(p.dim_res)
-        spacing = spacing_of(p.dim_res)
-        sigmas = p.resolved_sigmas()
-        strides = self._strides(max_samples)
-        alpha_sq = float(p.alpha_sq)
-        beta_sq = float(p.beta_sq)
-        pending = None       # trace entry whose h_mask count is still being produced on the side stream
+            tail = self._scales_on_the_device(plan, tail_field)
+            if tail is None:
+                # a condition the device-resident chain leaves to the host turned up: the frame is redone, synchronously
+                self.chain_fallbacks += 1
+                self._restart_frame(frame, p)
+        if tail is None:
+            self._scales_synchronously(plan, mask)
+            tail = ChainTail()
+        self._settle_mask_counts()
+        return plan, tail
 
-        def settle():
-            nonlocal pending
-            if pending is not None:
-                pending.mask_count = self._reduce_mask_count(ctx.vesselness_count())
-                pending = None
-
-        deltas = list(cascade_deltas(sigmas, zr))
-        if self.two_d:
-            deltas = [(0.0, d[1], d[2]) for d in deltas]          # sigma_vec = (s, s): no Z axis (filtering.py:281-282)
+    def _scales_synchronously(self, plan: FramePlan, mask: bool):
+        """The sigma loop with every threshold decided on the host, between the passes (one wait per decision)."""
+        counts = _DeferredMaskCount(self)
+        # Hessian statistics and vesselness candidates in ONE walk where the mask threshold can be bracketed beforehand
+        want_bracket = bool(self.one_pass and mask and plan.division and plan.frob_thresh is None)
         ahead = False        # the cascade step of the current scale was enqueued during the previous one
-
-        def cascade_step(k, run_ahead):
-            delta = deltas[k]
-            if not any(s > 0 for s in delta):
-                return False
-            ws = [gaussian_weights(d) for d in delta]
-            if run_ahead and not self._step_fits_ahead(ws):
-                return False
-            z0, z1 = self._gauss_range(0 if ws[0] is None else (len(ws[0]) - 1) // 2)
-            ctx.gauss_step(*ws, z0=z0, z1=z1, **({"ahead": True} if run_ahead else {}))
-            return True
-
-        for k, sigma in enumerate(sigmas):
-            if ahead:
-                ctx.gauss_commit()
-            else:
-                cascade_step(k, False)
-            self._after_cascade_step(k)      # Z slabs: the ghost planes the NEXT step needs start travelling now
-            # the next cascade step only reads the Gaussian of THIS scale: enqueue it now, on the side stream, so that
-            # it runs beside this scale's Hessian walk (filtering.py:814-835 has no such dependency either)
-            ahead = self._gauss_ahead and k + 1 < len(sigmas) and cascade_step(k + 1, True)
-            # gamma (filtering.py:365-380, 839-840)
-            # the gamma samples and the raw Frobenius samples of the bracket need nothing from each other: one round trip
-            want_bracket = bool(self.one_pass and mask and p.frob_thresh_division and p.frob_thresh is None)
-            pair = None
-            if want_bracket and self._chain_hist and self._pair_hist:
-                ctx.set_spacing(spacing)
-                ctx.set_frob_norm(1.0, 0.0)
-                pair = ctx.sample_range_hist2(FIELD_GAUSS, FIELD_FROB, strides, 256)
-            gamma = self._threshold_from_field(FIELD_GAUSS, strides, pre=None if pair is None else pair[0])
-            if gamma is None or gamma <= 0:
-                gamma = _EPS32
-            gamma_sq = 2.0 * (float(gamma) ** 2)
-            # Hessian statistics (filtering.py:555-562) -- taken together with the vesselness candidates when the
-            # mask threshold can be bracketed beforehand (nl_vesselness_spec), by a pass of their own otherwise
-            spec = False
-            stats = None
-            if want_bracket:
-                if pair is None:
-                    ctx.set_spacing(spacing)
-                bracket = self._fsq_bracket(strides, float(p.frob_thresh_division), None if pair is None else pair[1])
-                if bracket is not None:
-                    settle()
-                    vz0, vz1 = self._vess_range()
-                    ma, mf, inf_, ovf = ctx.vesselness_spec(spacing, bracket[0], bracket[1], z0=vz0, z1=vz1)
-                    stats = self._reduce_stats(ma, mf, inf_, ovf, fused_call=True)    # nl_vesselness_spec reduces them itself on a fused communicator
-                    spec = not stats[2] and not stats[3]
-                    if stats[2]:
-                        stats = None     # a +inf frob_sq turned up: the one-pass walk only flags it (the largest finite
-                                         # value comes from the statistics pass below), and the scale goes the two-pass way
-            if stats is None:
-                stats = self._reduce_stats(*ctx.hessian_stats(spacing))
-            max_abs32, max_fsq32, any_inf = stats[:3]
-            max_abs = float(max_abs32)
-            if max_abs <= 0:
-                max_abs = 1.0
-            with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-                max_frob = np.sqrt(np.float32(max_fsq32)) / np.float32(max_abs)   # float32, as the volume op
-            ctx.set_frob_norm(max_abs, float(max_frob) if any_inf else 0.0)
-            thr = None
-            if not mask:
-                # h_mask = ones_like(image) (filtering.py:566-567)
-                thr_cmp, nonempty = np.float32(-np.inf), True
-            elif not p.frob_thresh_division:
-                thr_cmp = None                                   # mask = frob > 0 (filtering.py:428-430)
-                nonempty = bool(max_frob > 0)
-            else:
-                if p.frob_thresh is None:
-                    t = self._threshold_from_field(FIELD_FROB, strides, self._normalised_range(spec, max_abs))
-                    thr = 0.0 if t is None else t                # filtering.py:433-439
-                else:
-                    thr = float(p.frob_thresh)
-                thr_cmp = np.float32(thr / p.frob_thresh_division)   # weak python scalar vs float32 array
-                nonempty = bool(max_frob > thr_cmp)
-            count = 0
-            hit = False
+        for k, sigma in enumerate(plan.sigmas):
+            ahead = self._next_gaussian(plan, k, ahead, self._gauss_ahead)
+            gamma, frob_pre = self._scale_gamma(plan, want_bracket)
+            max_abs, max_frob, walked = self._scale_statistics(plan, want_bracket, frob_pre, counts)
+            thr, thr_cmp, nonempty = self._scale_mask_threshold(plan, mask, max_abs, max_frob, walked)
+            count, hit = 0, False
             if nonempty:                                         # filtering.py:843-844
-                if spec:
-                    hit = ctx.vesselness_resolve(gamma_sq, alpha_sq, beta_sq, thr_cmp)
-                if not hit:
-                    settle()
-                    vz0, vz1 = self._vess_range()
-                    count = self._reduce_sum(ctx.vesselness_step(gamma_sq, alpha_sq, beta_sq, thr_cmp, z0=vz0, z1=vz1))
+                count, hit = self._scale_walk(plan, 2.0 * (float(gamma) ** 2), thr_cmp, walked is not None, counts)
             self.trace.scales.append(ScaleTrace(float(sigma), float(gamma), max_abs, thr, count, not nonempty, hit))
             if hit:
-                settle()
-                pending = self.trace.scales[-1]      # its kernel overlaps the next scale's Gaussian; count read later
-        settle()
+                counts.settle()
+                counts.defer(self.trace.scales[-1])      # its kernel overlaps the next scale's Gaussian; count read later
+        counts.settle()
         if not mask and not self.two_d:
             # filtering.py:581: with h_mask all ones EVERY Hessian goes to numpy.linalg.eigvalsh, and LAPACK gives up on a matrix with a
             # NaN entry -- the reference's run ends in LinAlgError("Eigenvalues did not converge") (pinned: tests/golden nomask_nan_*).
             # The device solves in closed form and would return 0 there; it reports such a voxel instead and the same exception is raised.
-            if self._reduce_sum(int(ctx.info("nan_hessian"))):
+            if self._reduce_sum(int(self.ctx.info("nan_hessian"))):
                 raise np.linalg.LinAlgError("Eigenvalues did not converge")
-        return self._finish_frame(finish, p, mask)
+
+    def _scale_gamma(self, plan: FramePlan, want_bracket: bool):
+        """gamma (filtering.py:365-380, 839-840) -> (gamma, the raw Frobenius round of the bracket when it came along, else None):
+        the gamma samples and the raw Frobenius samples of the bracket need nothing from each other: one round trip."""
+        ctx = self.ctx
+        pair = None
+        if want_bracket and self._chain_hist and self._pair_hist:
+            ctx.set_spacing(plan.spacing)
+            ctx.set_frob_norm(1.0, 0.0)
+            pair = ctx.sample_range_hist2(FIELD_GAUSS, FIELD_FROB, plan.strides, 256)
+        gamma = self._threshold_from_field(FIELD_GAUSS, plan.strides, pre=None if pair is None else pair[0])
+        if gamma is None or gamma <= 0:
+            gamma = _EPS32
+        return gamma, (None if pair is None else pair[1])
+
+    def _scale_statistics(self, plan: FramePlan, want_bracket: bool, frob_pre, counts: _DeferredMaskCount):
+        """Hessian statistics (filtering.py:555-562) and the normalisation they set -- taken together with the vesselness candidates
+        when the mask threshold can be bracketed beforehand (nl_vesselness_spec), by a pass of their own otherwise.
+        -> (max_abs, max_frob, walked): walked is the raw sample range of the bracket round when the one-pass walk stands (neither
+        a +inf frob_sq nor a queue overflow), None when the scale goes the two-pass way."""
+        ctx = self.ctx
+        stats, walked = None, None
+        if want_bracket:
+            if frob_pre is None:
+                ctx.set_spacing(plan.spacing)
+            bracket = self._fsq_bracket(plan.strides, float(plan.division), frob_pre)
+            if bracket is not None:
+                counts.settle()
+                vz0, vz1 = self._vess_range()
+                ma, mf, inf_, ovf = ctx.vesselness_spec(plan.spacing, bracket[0], bracket[1], z0=vz0, z1=vz1)
+                stats = self._reduce_stats(ma, mf, inf_, ovf, fused_call=True)    # nl_vesselness_spec reduces them itself on a fused communicator
+                if not stats[2] and not stats[3]:
+                    walked = bracket[2]
+                if stats[2]:
+                    stats = None     # a +inf frob_sq turned up: the one-pass walk only flags it (the largest finite
+                                     # value comes from the statistics pass below), and the scale goes the two-pass way
+        if stats is None:
+            stats = self._reduce_stats(*ctx.hessian_stats(plan.spacing))
+        max_abs32, max_fsq32, any_inf = stats[:3]
+        max_abs = float(max_abs32)
+        if max_abs <= 0:
+            max_abs = 1.0
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            max_frob = np.sqrt(np.float32(max_fsq32)) / np.float32(max_abs)   # float32, as the volume op
+        ctx.set_frob_norm(max_abs, float(max_frob) if any_inf else 0.0)
+        return max_abs, max_frob, walked
+
+    def _scale_mask_threshold(self, plan: FramePlan, mask: bool, max_abs, max_frob, walked):
+        """h_mask's threshold -> (thr for the trace, thr_cmp as the walk compares it, is any voxel above it?)."""
+        if not mask:
+            return None, np.float32(-np.inf), True               # h_mask = ones_like(image) (filtering.py:566-567)
+        if not plan.division:
+            return None, None, bool(max_frob > 0)                # mask = frob > 0 (filtering.py:428-430)
+        if plan.frob_thresh is None:
+            known = None if walked is None else self._normalised_range(walked, max_abs)
+            t = self._threshold_from_field(FIELD_FROB, plan.strides, known)
+            thr = 0.0 if t is None else t                        # filtering.py:433-439
+        else:
+            thr = float(plan.frob_thresh)
+        thr_cmp = np.float32(thr / plan.division)                # weak python scalar vs float32 array
+        return thr, thr_cmp, bool(max_frob > thr_cmp)
+
+    def _scale_walk(self, plan: FramePlan, gamma_sq, thr_cmp, walked: bool, counts: _DeferredMaskCount):
+        """The vesselness of a scale -> (h_mask count, hit): the candidates of the one-pass walk resolved where the exact threshold fell
+        inside the bracket (hit: the count comes later, _DeferredMaskCount), the two-pass walk otherwise."""
+        if walked and self.ctx.vesselness_resolve(gamma_sq, plan.alpha_sq, plan.beta_sq, thr_cmp):
+            return 0, True
+        counts.settle()
+        vz0, vz1 = self._vess_range()
+        return self._reduce_sum(self.ctx.vesselness_step(gamma_sq, plan.alpha_sq, plan.beta_sq, thr_cmp, z0=vz0, z1=vz1)), False
 
     # Device-resident threshold chain (csrc/chain.inc): the scale loop without a host round trip; NELLIE_DEVICE_CHAIN=0: off
     _device_chain = os.environ.get("NELLIE_DEVICE_CHAIN", "1") == "1"
@@ -585,31 +655,23 @@ class FramePipeline:
 
     def _chain_usable(self, p: FilterParams, mask: bool) -> bool:
         return bool(self._device_chain and (self.one_pass or self.two_d) and mask and p.frob_thresh is None and p.frob_thresh_division
-                    and hasattr(self.ctx, "chain_begin") and getattr(self.ctx, "chain_available", lambda: True)()
+                    and "chain_begin" in self._ctx_has and ("chain_available" not in self._ctx_has or self.ctx.chain_available())
                     and self._chain_reductions_on_device())
 
     def _chain_reductions_on_device(self) -> bool:
         return True            # one GPU: nothing to reduce (a Z-slab pipeline needs its fused communicator)
 
-    def _scales_on_the_device(self, p: FilterParams, max_samples: int) -> bool:
-        """The sigma loop of compute_vesselness with every threshold decided on the device (nl_chain_*): kernels only, ONE
-        wait at the end.  True: the trace is filled and the frame stands; False: the caller redoes the frame synchronously."""
-        ctx = self.ctx
-        zr = z_ratio_of(p.dim_res)
-        spacing = spacing_of(p.dim_res)
-        sigmas = p.resolved_sigmas()
-        if not 1 <= len(sigmas) <= 16:
-            return False
-        strides = self._strides(max_samples)
-        deltas = list(cascade_deltas(sigmas, zr))
-        if self.two_d:
-            deltas = [(0.0, d[1], d[2]) for d in deltas]          # sigma_vec = (s, s): no Z axis (filtering.py:281-282)
-        order = self._scale_order(deltas)            # None: sigma order
+    def _scales_on_the_device(self, plan: FramePlan, tail_field):
+        """The sigma loop with every threshold decided on the device (nl_chain_*): kernels only, ONE wait at the end.
+        -> ChainTail: the trace is filled and the frame stands; None: the caller redoes the frame synchronously."""
+        if not 1 <= len(plan.sigmas) <= 16:
+            return None
+        order = self._scale_order(plan.deltas)            # None: sigma order
         if order is None:
-            self._scales_in_sigma_order(p, spacing, strides, deltas)
+            self._scales_in_sigma_order(plan)
         else:
-            self._scales_out_of_order(p, spacing, strides, deltas, order)
-        return self._chain_epilogue(strides, sigmas)
+            self._scales_out_of_order(plan, order)
+        return self._chain_epilogue(plan, tail_field)
 
     # tests: {sigma index: factor on that scale's predicted threshold} -- a bracket miss in one scale of the chain
     _chain_test_scales = {}
@@ -617,9 +679,9 @@ class FramePipeline:
     def _chain_test_scale(self, k):
         return self._chain_test_scales.get(k, self._one_pass_test_scale)
 
-    def _scales_in_sigma_order(self, p, spacing, strides, deltas):
+    def _scales_in_sigma_order(self, plan: FramePlan):
         ctx = self.ctx
-        n = len(deltas)
+        n = len(plan.sigmas)
         ctx.chain_begin(n)
         # No cascade step runs ahead here: that device (sharded.py) fills the GPU while the host waits for a scale's collectives,
         # and the chain has no such waits -- beside the walk the step only competes with it (measured on a 128 x 2048 x 2048 slab:
@@ -631,27 +693,10 @@ class FramePipeline:
         ahead = False
         # images: two passes per scale, the raw round's "bracket" decides nothing (margin 1: nl_chain_scale)
         margin = 1.0 if self.two_d else self.one_pass_margin
-
-        def cascade_step(k, on_side):
-            delta = deltas[k]
-            if not any(s > 0 for s in delta):
-                return False
-            ws = [gaussian_weights(d) for d in delta]
-            if on_side and not self._step_fits_ahead(ws):
-                return False                 # (it runs in order at the top of the next trip)
-            z0, z1 = self._gauss_range(0 if ws[0] is None else (len(ws[0]) - 1) // 2)
-            ctx.gauss_step(*ws, z0=z0, z1=z1, **({"ahead": True} if on_side else {}))
-            return True
-
         for k in range(n):
-            if ahead:
-                ctx.gauss_commit()
-            else:
-                cascade_step(k, False)
-            self._after_cascade_step(k)
-            ahead = run_ahead and k + 1 < n and cascade_step(k + 1, True)
+            ahead = self._next_gaussian(plan, k, ahead, run_ahead)
             vz0, vz1 = self._vess_range()
-            ctx.chain_scale(spacing, strides, float(p.alpha_sq), float(p.beta_sq), float(p.frob_thresh_division), margin,
+            ctx.chain_scale(plan.spacing, plan.strides, plan.alpha_sq, plan.beta_sq, float(plan.division), margin,
                             self._chain_test_scale(k), z0=vz0, z1=vz1)
 
     # ---- scales walked out of sigma order (csrc/nellie_hip.hip: nl_chain_begin_unordered) --------------------------
@@ -666,7 +711,7 @@ class FramePipeline:
         """None: sigma order.  "auto", or a schedulable 0-based permutation."""
         self.last_scale_order = None
         env = os.environ.get("NELLIE_SCALE_ORDER", "auto").strip().lower() or "auto"
-        if env == "sigma" or not self._scale_reorder_ok or self.two_d or not hasattr(self.ctx, "chain_begin_unordered"):
+        if env == "sigma" or not self._scale_reorder_ok or self.two_d or "chain_begin_unordered" not in self._ctx_has:
             return None
         if self._chain_ahead(int(np.prod(self.shape))):
             return None                  # (small frames: the next cascade step runs beside the walk, on the two free volumes)
@@ -690,23 +735,21 @@ class FramePipeline:
                              f"delayed by two cascade steps at most")
         return order
 
-    def _scales_out_of_order(self, p, spacing, strides, deltas, order):
+    def _scales_out_of_order(self, plan: FramePlan, order):
         ctx = self.ctx
-        n = len(deltas)
+        n = len(plan.sigmas)
         ctx.chain_begin_unordered(n)
-        division = float(p.frob_thresh_division)
+        division = float(plan.division)
         est = {}
         walked = []
 
-        def step(k):
-            ws = [gaussian_weights(d) for d in deltas[k]]
-            z0, z1 = self._gauss_range((len(ws[0]) - 1) // 2)
-            ctx.gauss_step(*ws, z0=z0, z1=z1)
-            ctx.chain_sample(k, spacing, strides, division, self.one_pass_margin, self._chain_test_scale(k))
+        def step(k):                     # (always fused, every delta positive: _scale_order -- so never refused, never ahead)
+            self._cascade_step(plan, k, False)
+            ctx.chain_sample(k, plan.spacing, plan.strides, division, self.one_pass_margin, self._chain_test_scale(k))
 
         def walk(k):
             vz0, vz1 = self._vess_range()
-            ctx.chain_walk(k, spacing, strides, float(p.alpha_sq), float(p.beta_sq), division, z0=vz0, z1=vz1)
+            ctx.chain_walk(k, plan.spacing, plan.strides, plan.alpha_sq, plan.beta_sq, division, z0=vz0, z1=vz1)
             walked.append(k)
 
         def choose(pending, steps_left):
@@ -723,40 +766,37 @@ class FramePipeline:
         run_scale_schedule(n, None if order == "auto" else order, step, walk, choose)
         self.last_scale_order = walked
 
-    def _chain_epilogue(self, strides, sigmas) -> bool:
+    def _chain_epilogue(self, plan: FramePlan, tail_field):
+        """The chain's one wait -> ChainTail, or None when a scale raised a flag (the frame is redone)."""
         ctx = self.ctx
         # filter()'s percentile threshold reads lattice samples of the result: their compaction is enqueued BEFORE the wait, so it
         # runs while the host waits for the chain's records and repeats its decisions (one round trip less per frame)
         # Round 4: with the percentile selected on the device (nl_tail_enqueue) the WHOLE epilogue is enqueued before the wait -- the
         # host repeats the chain's decisions while the GPU masks the frame -- and no sample ever travels.
-        dev_tail = self._tail_field is not None and self._device_tail_usable()
-        tail = not dev_tail and self._tail_ok and self._tail_field is not None and hasattr(ctx, "sample_gather_positive_begin")
-        self._tail_samples = None
-        self._tail_dev_pending = False
+        dev_tail = tail_field is not None and self._device_tail_usable()
+        tail = not dev_tail and self._tail_ok and tail_field is not None and "sample_gather_positive_begin" in self._ctx_has
         if dev_tail:
             ctx.chain_flush()
-            ctx.tail_enqueue(strides, 1.0)
+            ctx.tail_enqueue(plan.strides, 1.0)
         elif tail:
             ctx.chain_flush()
-            ctx.sample_gather_positive_begin(self._tail_field, strides)
+            ctx.sample_gather_positive_begin(tail_field, plan.strides)
         flags, gamma, max_abs, thr, counts = ctx.chain_finish()
         samples = ctx.sample_gather_positive_end() if tail else None
         self.last_chain_flags = [int(f) for f in flags]
         if not self._all_ranks_agree(not flags.any()):
             if dev_tail:
-                ctx.tail_finish(commit=False)              # the frame is redone: what the epilogue computed from it is dropped
-            return False
-        self._tail_samples = samples
-        self._tail_dev_pending = dev_tail
+                self._finish_device_tail(commit=False)     # the frame is redone: what the epilogue computed from it is dropped
+            return None
         if self.check_device_edges:
-            for k in range(len(sigmas)):
+            for k in range(len(plan.sigmas)):
                 for which in range(3):
                     _, edges, rng, _ = ctx.chain_log(k, which)
                     assert np.array_equal(edges, histogram_edges(rng[0], rng[1], 256)), "device-built histogram edges differ from numpy's"
-        for k, sigma in enumerate(sigmas):
+        for k, sigma in enumerate(plan.sigmas):
             self.trace.scales.append(ScaleTrace(float(sigma), float(gamma[k]), float(max_abs[k]), float(thr[k]),
                                                 self._reduce_mask_count(int(counts[k])), False, not self.two_d))
-        return True
+        return ChainTail(samples, dev_tail)
 
     def _all_ranks_agree(self, ok: bool) -> bool:
         return ok
@@ -771,25 +811,18 @@ class FramePipeline:
             return env == "1"
         return n_voxels < (1 << 26)
 
-    def _finish_frame(self, finish: bool, p: FilterParams, mask: bool):
+    def _finish_frame(self, plan: FramePlan, mask: bool):
         """The product `vesselness * masks` (filtering.py:926) once every scale is in."""
         ctx = self.ctx
-        sigmas = p.resolved_sigmas()
-        self._settle_mask_counts()
-        if not finish:
-            return None
         vz0, vz1 = self._vess_range()
         self.trace.n_positive = self._reduce_sum(ctx.filter_finish(vz0, vz1))
         if self.two_d:
             # filtering.py:927-930: blob response of the (by now fully blurred) frame, maximum with the vesselness
-            for i, s in enumerate(sigmas):
+            for i, s in enumerate(plan.sigmas):
                 w2, w0 = gaussian_derivative_weights(s, 2), gaussian_derivative_weights(s, 0)
                 ctx.log2d_step(w2, w0, w2, w0, np.float32(float(s) ** 2), first=(i == 0), use_mask=mask)
             self.trace.n_positive = ctx.log2d_finish()
         return self.trace.n_positive
-
-    def _load(self, frame):
-        self.ctx.filter_load(self._as_frame(frame))
 
     def mask_volume(self, p: FilterParams):
         """filtering.py:952-967 on the device-resident frame."""
@@ -812,9 +845,6 @@ class FramePipeline:
     # the device chain may gather the samples of the percentile threshold under its own wait (a single context: a slab pipeline
     # gathers them across ranks)
     _tail_ok = True
-    _tail_field = None
-    _tail_samples = None
-    _tail_dev_pending = False
     _device_tail = os.environ.get("NELLIE_DEVICE_TAIL", "1") == "1"      # 0: the percentile threshold on the host (round 3)
 
     def _device_percentile_usable(self) -> bool:
@@ -823,11 +853,11 @@ class FramePipeline:
         global _FAST_PERCENTILE
         if _FAST_PERCENTILE is None:
             percentile_of_samples(np.array([1.0, 2.0], np.float32), 1)
-        return bool(self._device_tail and _FAST_PERCENTILE and hasattr(self.ctx, "mask_volume_dev") and self._tail_reductions_on_device())
+        return bool(self._device_tail and _FAST_PERCENTILE and "mask_volume_dev" in self._ctx_has and self._tail_reductions_on_device())
 
     def _device_tail_usable(self) -> bool:
         """... and the whole fused epilogue enqueued without a wait (nl_tail_enqueue): 3-D frames."""
-        return bool(self._device_percentile_usable() and not self.two_d and hasattr(self.ctx, "tail_enqueue"))
+        return bool(self._device_percentile_usable() and not self.two_d and "tail_enqueue" in self._ctx_has)
 
     def _check_device_percentile(self, rec):
         thr, gamma = percentile_from_order_statistics(rec["n_samples"], rec["a"], rec["b"], 1)
@@ -837,16 +867,18 @@ class FramePipeline:
     def _tail_reductions_on_device(self) -> bool:
         return True            # one GPU: nothing to reduce (a Z-slab pipeline needs its fused communicator)
 
-    def _finish_device_tail(self):
-        """Waits for the epilogue nl_tail_enqueue started, checks the device's interpolation against numpy's rule, fills the trace.
-        -> positive voxels, or None when there was no positive sample (the caller takes the plain path)."""
-        rec = self.ctx.tail_finish(commit=True)
-        if rec["n_samples"] == 0:
+    def _finish_device_tail(self, commit: bool):
+        """The one place an epilogue that nl_tail_enqueue started ends.  commit: waits for it, checks the device's interpolation
+        against numpy's rule, fills the trace -> positive voxels, or None when there was no positive sample (the caller takes the
+        plain path).  Not commit (the frame is redone, or no scale was evaluated): what it computed is dropped -> None."""
+        rec = self.ctx.tail_finish(commit=commit)
+        if not commit or rec["n_samples"] == 0:
             return None
         self._check_device_percentile(rec)
         self.trace.percentile_thr = float(rec["thr"])
         self.trace.n_positive = self._reduce_fused_count(rec["n_positive"])
         return self.trace.n_positive
+
     _fused_epilogue = True      # (a Z-slab pipeline on a context without nl_mask_volume_fused keeps the two-step epilogue)
     # Enqueue the cascade step of scale s+1 on the side stream beside the Hessian walk of scale s.  Exact either way.
     # Off by default: at 1024^3 it buys ~1 % (two full-GPU kernels mostly take turns) and it blurs per-kernel timings.
@@ -863,38 +895,28 @@ class FramePipeline:
             if npos > 0:
                 self.mask_volume(p)
             return npos
-        if self._fused_epilogue and not self.two_d:
-            self._tail_field = FIELD_VESSELNESS if (self._tail_ok or self._device_tail_usable()) else None
-            self._tail_dev_pending = False
-            try:
-                self.compute_vesselness(frame, p, mask=mask, finish=False)
-            finally:
-                self._tail_field = None
-            positive, self._tail_samples = self._tail_samples, None
-            pending, self._tail_dev_pending = self._tail_dev_pending, False
-            if any(not sc.skipped for sc in self.trace.scales):
-                strides = self._strides(int(p.max_threshold_samples))
-                if pending or (positive is None and self._device_tail_usable()):
-                    if not pending:
-                        self.ctx.tail_enqueue(strides, 1.0)
-                    npos = self._finish_device_tail()
-                    if npos is not None:
-                        return npos
-                    positive = np.zeros(0, np.float32)          # no positive sample: the plain path below
-                    pending = False
+        if not self._fused_epilogue or self.two_d:
+            npos = self.compute_vesselness(frame, p, mask=mask)
+        else:
+            plan, tail = self._run_scales(frame, p, mask, FIELD_VESSELNESS if (self._tail_ok or self._device_tail_usable()) else None)
+            evaluated = any(not sc.skipped for sc in self.trace.scales)
+            positive = tail.samples
+            if tail.pending or (evaluated and positive is None and self._device_tail_usable()):
+                if not tail.pending:
+                    self.ctx.tail_enqueue(plan.strides, 1.0)
+                npos = self._finish_device_tail(commit=evaluated)       # (every scale skipped: nothing to commit)
+                if npos is not None:
+                    return npos
+                positive = np.zeros(0, np.float32)              # no positive sample: the plain path below
+            if evaluated:
                 if positive is None:
-                    positive = self._positive_lattice_samples(FIELD_VESSELNESS, strides)
+                    positive = self._positive_lattice_samples(FIELD_VESSELNESS, plan.strides)
                 if positive.size > 0:
                     thr = percentile_of_samples(positive, 1)
                     self.trace.percentile_thr = float(thr)
                     self.trace.n_positive = self._reduce_fused_count(self.ctx.mask_volume_fused(thr))
                     return self.trace.n_positive
-            if pending:                                         # every scale was skipped: nothing to commit
-                self.ctx.tail_finish(commit=False)
-            vz0, vz1 = self._vess_range()
-            npos = self.trace.n_positive = self._reduce_sum(self.ctx.filter_finish(vz0, vz1))
-        else:
-            npos = self.compute_vesselness(frame, p, mask=mask)
+            npos = self._finish_frame(plan, mask)
         if npos > 0:      # float(sum(frame)) > 0 for a non-negative frame
             self.mask_volume(p)
         return npos

@@ -49,16 +49,6 @@ def slab_range(gnz: int, world: int, rank: int):
     return o0, o0 + base + (1 if rank < rem else 0)
 
 
-def halo_depth(p: FilterParams) -> int:
-    """Ghost planes a slab needs on an interior side for the whole Filter: see the module docstring."""
-    sig = p.resolved_sigmas()
-    rz = 0
-    for delta in cascade_deltas(sig, z_ratio_of(p.dim_res)):
-        w = gaussian_weights(delta[0])
-        rz += 0 if w is None else (len(w) - 1) // 2
-    return rz + 4
-
-
 def step_radii(p: FilterParams):
     """Z radius of every cascade step (0 where the step has no Z pass)."""
     out = []
@@ -66,6 +56,11 @@ def step_radii(p: FilterParams):
         w = gaussian_weights(delta[0])
         out.append(0 if w is None else (len(w) - 1) // 2)
     return out
+
+
+def halo_depth(p: FilterParams) -> int:
+    """Ghost planes a slab needs on an interior side for the whole Filter: see the module docstring."""
+    return 4 + sum(step_radii(p))
 
 
 def halo_depth_steps(p: FilterParams) -> int:
@@ -230,7 +225,7 @@ class RcclComm:
 
 
 class ShardedFramePipeline(FramePipeline):
-    _tail_ok = False            # the percentile samples are gathered across the ranks (pipeline.py: _scales_on_the_device)
+    _tail_ok = False            # the percentile samples are gathered across the ranks (pipeline.py: _chain_epilogue)
     _scale_reorder_ok = False   # a slab's cascade steps wait for ghost planes, in sigma order (pipeline.py: _scale_order)
 
     def __init__(self, gshape, rank, world, comm_factory, params: FilterParams, device: int = 0, ctx_factory=None, halo=None,
@@ -241,7 +236,6 @@ class ShardedFramePipeline(FramePipeline):
         halo_mode: "steps" (per-step exchange, default; NELLIE_HALO overrides) or "fat" (one exchange per frame).
         halo: ghost planes per interior side (default: what the scheme needs; Label alone needs 1).
         """
-        import os
         self.rank, self.world = int(rank), int(world)
         self.halo_mode = halo_mode or os.environ.get("NELLIE_HALO", "steps")
         if self.halo_mode not in ("steps", "fat"):
@@ -256,18 +250,20 @@ class ShardedFramePipeline(FramePipeline):
         ctx = make(lshape, device, gz0, int(gshape[0]), (own_lo, own_hi))
         super().__init__(gshape, device=device, ctx=ctx)
         self.comm = comm_factory(ctx)
-        # the sample range is reduced across the ranks before the histogram pass: by the library itself between the two
-        # kernels (a "fused" communicator), or by a host-level all-reduce between two calls
+        # what the communicator does inside ONE call where others gather through the host: asked once
+        self._comm_has = frozenset(n for n in ("positive_samples_world", "allgather_list", "slab_phase_gather") if hasattr(self.comm, n))
         # the next cascade step is enqueued beside this scale's Hessian walk (pipeline.py): on slabs it fills the GPU while
         # the host waits for the collectives of the scale's thresholds (31.3 -> 30.8 ms/step on one rank; NELLIE_GAUSS_AHEAD=0: off)
-        self._gauss_ahead = hasattr(ctx, "gauss_commit") and os.environ.get("NELLIE_GAUSS_AHEAD", "1") == "1"
+        self._gauss_ahead = "gauss_commit" in self._ctx_has and os.environ.get("NELLIE_GAUSS_AHEAD", "1") == "1"
+        # the sample range is reduced across the ranks before the histogram pass: by the library itself between the two
+        # kernels (a "fused" communicator), or by a host-level all-reduce between two calls
         self._fused_reduce = bool(getattr(self.comm, "fused", False))
         self._chain_hist = self._fused_reduce
         self.params = params
         self._valid = (0, lshape[0])
         self._raw_ghosts_loaded = False
         # threshold + opening + product in one go, ghost planes included (nl_mask_volume_fused works on owned +- 2)
-        self._fused_epilogue = hasattr(ctx, "mask_volume_fused") and hasattr(ctx, "sample_gather_positive")
+        self._fused_epilogue = {"mask_volume_fused", "sample_gather_positive"} <= self._ctx_has
 
     # ---- loading: own planes in, ghost planes from the neighbours ---------------------------------------
     def raw_ghost_needed(self):
@@ -408,23 +404,21 @@ class ShardedFramePipeline(FramePipeline):
     # and ONE download happen inside one library call (nl_positive_samples_world).  The block is a bound on any rank's sample
     # points, derived from the global shape so that every rank passes the same number.
     def _positive_lattice_samples(self, fld, strides):
-        f = getattr(self.comm, "positive_samples_world", None)
-        if f is None:
+        if "positive_samples_world" not in self._comm_has:
             return super()._positive_lattice_samples(fld, strides)
         sz, sy, sx = (int(v) for v in strides)
         gnz, ny, nx = self.shape
         per_plane = -(-ny // sy) * -(-nx // sx)
         most = max(-(-o1 // sz) - -(-o0 // sz) for o0, o1 in (slab_range(gnz, self.world, r) for r in range(self.world)))
-        return f(self.ctx, fld, 0, sz, sy, sx, max(1, most * per_plane))
+        return self.comm.positive_samples_world(self.ctx, fld, 0, sz, sy, sx, max(1, most * per_plane))
 
     def _positive_flat_samples(self, fld, offset, step):
-        f = getattr(self.comm, "positive_samples_world", None)
-        if f is None:
+        if "positive_samples_world" not in self._comm_has:
             return super()._positive_flat_samples(fld, offset, step)
         gnz, ny, nx = self.shape
         plane = ny * nx
         most = max(-(-(o1 - o0) * plane // int(step)) + 1 for o0, o1 in (slab_range(gnz, self.world, r) for r in range(self.world)))
-        return f(self.ctx, fld, 1, int(offset), int(step), 0, max(1, most))
+        return self.comm.positive_samples_world(self.ctx, fld, 1, int(offset), int(step), 0, max(1, most))
 
     # ---- outputs ------------------------------------------------------------------------------------------
     def download_frangi(self, out=None):
@@ -443,9 +437,8 @@ class ShardedFramePipeline(FramePipeline):
         self.ctx.label_intensity_mask(np.asarray(original), thresh, z0=lo, z1=hi)
 
     def _gather_list(self, arr):
-        f = getattr(self.comm, "allgather_list", None)
-        if f is not None:
-            return f(arr)
+        if "allgather_list" in self._comm_has:
+            return self.comm.allgather_list(arr)
         # communicators that only concatenate: gather the sizes first
         sizes = self.comm.allgather(np.array([arr.size], np.int64))
         flat = self.comm.allgather(arr)
@@ -456,9 +449,9 @@ class ShardedFramePipeline(FramePipeline):
         """Components of this slab for one phase + the joined view of the trees that continue on other ranks.  Over RCCL the
         tables are all-gathered on the device inside the context's own call (one wait per phase); other communicators gather
         the rank's blob through the host."""
-        fused = getattr(self.comm, "slab_phase_gather", None)
-        blobs = fused(self.ctx, phase) if fused is not None else self._gather_list(self.ctx.slab_phase(phase)[0])
-        return join_slab_blobs(blobs)
+        if "slab_phase_gather" in self._comm_has:
+            return join_slab_blobs(self.comm.slab_phase_gather(self.ctx, phase))
+        return join_slab_blobs(self._gather_list(self.ctx.slab_phase(phase)[0]))
 
     def label(self, frangi_thresh, min_area, fill_holes=True):
         """labelling.py:467-509 across slabs (see the module docstring); returns the GLOBAL label count."""
