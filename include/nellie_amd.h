@@ -886,7 +886,9 @@ int nl_debug_eig_frangi(nl_ctx *ctx, const float *h6, int64_t n, int impl, float
 
 /* Introspection: "fast_div" (2 / 1 when the 2- / 3-instruction constant division was proven exact for the
    current spacings, 0: the float64 form), "hessian_tile_rows", "device_bytes", "gauss_yx_max_r" (largest in-plane
-   radius whose Y and X passes share a kernel: see nl_gauss_step_ahead). */
+   radius whose Y and X passes share a kernel: see nl_gauss_step_ahead), "last_label_path" (what nl_label_run's last frame
+   took: 0 the run-level labelling, 1 the voxel-level kernels because a row exceeds 65535 voxels, 2 the voxel-level kernels
+   after a run set exceeded the scratch capacity of n / 2 runs, 3 the voxel-level kernels forced by NELLIE_LABEL_VOXEL). */
 int nl_ctx_info(nl_ctx *ctx, const char *key, double *value);
 
 /* ------------------------------------------------------------------ timing ------------ */

@@ -1771,6 +1771,7 @@ extern "C" int nl_ctx_info(nl_ctx *c, const char *key, double *value) {
     else if (!strcmp(key, "last_fsq_min")) *value = c->last_fsq_min;
     else if (!strcmp(key, "last_spec_overflow")) *value = c->last_spec_overflow;
     else if (!strcmp(key, "last_label_sparse")) *value = c->last_label_sparse;
+    else if (!strcmp(key, "last_label_path")) *value = c->last_label_path;     // which implementation nl_label_run's last frame used (nl_common.h)
     else if (!strcmp(key, "prezero_used")) *value = c->prezero_used;        // bit 1: the last frame's labels were painted into a pre-zeroed volume (bit 0, the Frangi volume: never)
     else if (!strcmp(key, "device_bytes")) *value = (double)nl_ctx_bytes(c->nzl, c->ny, c->nx);
     else if (!strcmp(key, "gauss_yx_max_r")) *value = getenv("NELLIE_NO_FUSED_YX") ? 0 : GM_MAX_R;   // largest in-plane radius whose Y and X passes share a kernel

@@ -96,6 +96,15 @@ static int label_run_voxels(nl_ctx *c, int has_thr, float thr, int64_t min_area,
     const i64 nrows = c->nzl * c->ny;
     const i64 waves = nrows * ((c->nx + 63) / 64);
     int rc;
+    {   // run_ccl and majority_kernel launch one workgroup row per (y, z): a frame beyond the device's grid limits is refused here,
+        // before any launch (nl_ctx_create's own bound on ny and nzl is the usual limit; this reads the device's)
+        int gy = 0, gz = 0;
+        NL_HIP(hipDeviceGetAttribute(&gy, hipDeviceAttributeMaxGridDimY, c->device));
+        NL_HIP(hipDeviceGetAttribute(&gz, hipDeviceAttributeMaxGridDimZ, c->device));
+        if (c->ny > gy || c->nzl > gz)
+            return nl_fail(err, errlen, NL_EINVAL, "the voxel-level Label launches a (x, %lld, %lld) grid, beyond this device's limits (%d, %d)",
+                           (i64)c->ny, (i64)c->nzl, gy, gz);
+    }
     ProfScope ps(c, "label");
     threshold_kernel<<<grid1d(n), 256, 0, c->stream>>>(c->f[c->i_vmax], mA, has_thr, thr, n);
     NL_CHECK_LAUNCH();
@@ -397,6 +406,7 @@ extern "C" int nl_label_run(nl_ctx *c, int has_thr, float thr, int64_t min_area,
     if (c->nzl != c->gnz) return nl_fail(err, errlen, NL_EINVAL, "nl_label_run works on a whole volume (Z-slabs: nl_label_pack / nl_label_run_global)");
     static int force_voxel = -1;
     if (force_voxel < 0) { const char *e = getenv("NELLIE_LABEL_VOXEL"); force_voxel = (e && atoi(e)) ? 1 : 0; }
+    c->last_label_path = force_voxel ? 3 : (c->nx > 65535 ? 1 : 0);
     if (force_voxel || c->nx > 65535) return label_run_voxels(c, has_thr, thr, min_area, fill_holes, n_labels, err, errlen);
     LabelGeo g;
     g.nz = c->nzl; g.ny = c->ny; g.nx = c->nx;
@@ -419,7 +429,7 @@ extern "C" int nl_label_run(nl_ctx *c, int has_thr, float thr, int64_t min_area,
     bool overflow = false;
     int rc = label_core(c, g, min_area, fill_holes, n_labels, &overflow, err, errlen);
     if (rc) return rc;
-    if (overflow) return label_run_voxels(c, has_thr, thr, min_area, fill_holes, n_labels, err, errlen);
+    if (overflow) { c->last_label_path = 2; return label_run_voxels(c, has_thr, thr, min_area, fill_holes, n_labels, err, errlen); }
     if (pz) c->prezero_used |= 2;
     c->labbits_epoch = c->epoch.load();           // m[1] = the mask the labels were painted from (labels > 0, bit for bit)
     return NL_OK;

@@ -76,6 +76,8 @@ struct nl_ctx {
     unsigned long long labbits_epoch = ~0ull - 8;   // epoch at which m[1] held the bits `labels > 0` of the label volume (nl_label_run's last
                                                     // mask: what it painted from); Markers then skips re-deriving them from 4 B/voxel of labels
     int last_label_sparse = 0;
+    int last_label_path = 0;      // nl_label_run's last frame: 0 run-level result kept, 1 voxel path (nx > 65535), 2 voxel path after a
+                                  // run-capacity overflow, 3 voxel path forced by NELLIE_LABEL_VOXEL
     // Pre-zeroed label volume (NELLIE_PREZERO, nl_host.h: NL_ENTER_KEEP_PZ): the buffer -- by address, the epilogue swaps f[] entries --
     // that the frame's last fused cascade step zeroed in passing (its dead third ping-pong volume) and that nl_label_run then paints
     // sparsely.  Valid while pz_epoch == epoch at an entry point that carried it forward: every entry point that is not on that short
