@@ -288,6 +288,16 @@ int nl_vesselness_resolve(nl_ctx *ctx, float gamma_sq, float alpha_sq, float bet
    asynchronous; this returns the count later (and waits for the kernel). */
 int nl_vesselness_count(nl_ctx *ctx, int64_t *mask_count, char *err, size_t errlen);
 
+/* Host only (no context, no device): the launch plan of the Hessian walk (csrc/walk_plan.h) for a slab of nzl x ny x nx voxels with the
+   owned planes [own_lo, own_hi), walked over [z0, z1) in `mode` (0 statistics -- always the owned planes --, 1 known threshold, 2 one
+   pass), fast_div / fast_div2 as the divisors' proof came out (nl_ctx_info("fast_div") >= 1 / == 2), and the switches' values as the
+   environment would give them: switches[7] = NELLIE_HV_RS, NELLIE_HV_NP, NELLIE_HV_DPP, NELLIE_HM_TY, NELLIE_HV_ZCHUNK, NELLIE_VQ_CAP
+   (0: unset), NELLIE_SPEC_MAX_GB.  plan[13] = kernel family (0 one voxel per thread, 1 pair, 2 wave-autonomous), tile rows, rs, np,
+   division form (0 float64, 1 three instructions, 2 two), planes per workgroup, tiles in X, tiles in Y, Z chunks, grid of a launch
+   (workgroups; waves for family 2), its queue regions, queue entries per region, planes per launch. */
+int nl_host_walk_plan(int mode, int64_t nzl, int64_t ny, int64_t nx, int64_t own_lo, int64_t own_hi, int64_t z0, int64_t z1, int fast_div,
+                      int fast_div2, const int64_t switches[7], int64_t plan[13], char *err, size_t errlen);
+
 /* ---- 2-D images (im_info.no_z): a context of shape (1, ny, nx) switched to 2-D ------------------------------
    nl_set_ndim(ctx, 2) makes nl_hessian_stats, NL_FIELD_FROB, nl_vesselness_step and nl_mask_volume follow the
    reference's 2-D branches: Hessian (hxx, hxy, hyy) by np.gradient twice (filtering.py:461-490), closed-form

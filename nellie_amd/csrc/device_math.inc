@@ -309,20 +309,3 @@ __device__ __forceinline__ float frangi3(float l1, float l2, float l3, float alp
     if (!(fabsf(v) <= 3.402823466e38f)) v = 0.0f;   // nan_to_num(nan=0, posinf=0, neginf=0)
     return v;
 }
-
-#ifndef NL_HV_UNIT
-// debug / known-answer kernel: eigenvalues (sorted by |.|) and Frangi response of explicit Hessians
-static __global__ void __launch_bounds__(256)
-debug_eig_kernel(const float *__restrict__ h6, i64 n, int impl, float alpha_sq, float beta_sq, float gamma_sq,
-                 float *__restrict__ out4) {
-    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float h[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) h[k] = h6[i * 6 + k];
-    float l1, l2, l3;
-    if (impl == 0) eig3_sorted_abs(h, l1, l2, l3); else eig3_sorted_abs_libm(h, l1, l2, l3);
-    out4[i * 4 + 0] = l1; out4[i * 4 + 1] = l2; out4[i * 4 + 2] = l3;
-    out4[i * 4 + 3] = frangi3(l1, l2, l3, alpha_sq, beta_sq, gamma_sq);
-}
-#endif  // NL_HV_UNIT

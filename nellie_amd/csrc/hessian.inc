@@ -1,26 +1,7 @@
-// Part of libnellie_hip.so (gfx950): included by nellie_hip.hip, see include/nellie_amd.h for the C-ABI.
+// Part of libnellie_hip.so (gfx950): the one-voxel walk, included by nellie_walk.hip after walk_common.h; see include/nellie_amd.h for the C-ABI.
 // =================================================================================================
-// kernels: Hessian statistics and the per-scale vesselness update
+// kernel: Hessian statistics and the per-scale vesselness update, one voxel per thread
 // =================================================================================================
-struct VessP {
-    float gamma_sq, alpha_sq, beta_sq;
-    int use_thr;
-    float thr;
-    float max_abs, max_finite;
-    int have_prev;           // 1: `pmask64` holds the AND of the h_masks of every earlier scale of this frame
-    int cnt_lo, cnt_hi;      // planes whose masked voxels are counted, and whose statistics are taken (the owned ones)
-    int first;               // 1: first evaluated scale of the frame (the host zeroes the vesselness volume before it)
-    float fsq_min;           // h_mask <=> frob_sq >= fsq_min for finite frob_sq (exact: see mask_threshold_on_fsq)
-    int m_inf;               // h_mask of a voxel whose frob_sq is +inf (frob := max finite, filtering.py:421-426)
-    unsigned int *nan_flag;  // all_ones only: set when a Hessian with a NaN entry reaches the eigen-solver (the reference's LAPACK call raises there)
-    int all_ones;            // Filter.run(mask=False): h_mask = ones_like(image) (filtering.py:566-567) -- NaN Hessians included, which no
-                             // comparison with a threshold can express
-    float fsq_lo, fsq_hi;    // MODE 2: bracket of the (not yet known) fsq_min
-    int qcap;                // queue entries per wave region
-    int zchunk;              // planes a workgroup marches (0: HM_ZCHUNK); a multiple of 8
-    i64 idx_lo, idx_hi;      // resolve kernel: launch-relative voxel offsets of the counted planes
-};
-
 // -------------------------------------------------------------------------------------------------
 // Z-marching, LDS-tiled Hessian kernel.  A 512-thread workgroup owns an 8(y) x 64(x) column tile and walks a
 // chunk of HM_ZCHUNK planes, one barrier per plane; raw planes are read from HBM exactly once (+ halo), several
@@ -53,85 +34,6 @@ struct VessP {
 // bracket the resolve kernel applies the exact test to the undecided entries (results identical to MODE 0 + 1 bit
 // for bit), otherwise -- or if a region overflowed, or an inf turned up -- the scale is redone with MODE 1.
 // -------------------------------------------------------------------------------------------------
-// a response > 0 needs trace < 0 and trace^2 >= frob_sq / 3
-#define HM_TRACE_C 0.30f
-// Queue entry: (h0..h5, voxel index) = 28 bytes, stored back to back (round 5; 32 bytes with a pad word before: an eighth fewer queue
-// bytes written by the walk and read by the resolve kernel).  A region keeps its 32 x qcap bytes.  The 16 + 12 byte accesses
-// are dword-aligned only, which global memory instructions of gfx950 take as they are (global_store_dwordx4 / dwordx3).
-#define HM_ENT 28
-struct __attribute__((packed, aligned(4))) QEnt4 { float a, b, c, d; };
-struct __attribute__((packed, aligned(4))) QEnt3 { float a, b, c; };
-__device__ __forceinline__ void qent_store(float4 *region, unsigned int slot, float h0, float h1, float h2, float h3, float h4, float h5, unsigned int idx) {
-    char *e = reinterpret_cast<char *>(region) + (size_t)__umul24(slot, (unsigned int)HM_ENT);       // slot < 2^24 (qcap): a full-rate multiply
-    *reinterpret_cast<QEnt4 *>(e) = QEnt4{h0, h1, h2, h3};
-    *reinterpret_cast<QEnt3 *>(e + 16) = QEnt3{h4, h5, __uint_as_float(idx)};
-}
-__device__ __forceinline__ void qent_load(const float4 *region, unsigned int slot, float4 &a, float4 &b) {
-    const char *e = reinterpret_cast<const char *>(region) + (size_t)slot * (size_t)HM_ENT;
-    const QEnt4 x = *reinterpret_cast<const QEnt4 *>(e); const QEnt3 y = *reinterpret_cast<const QEnt3 *>(e + 16);
-    a = make_float4(x.a, x.b, x.c, x.d); b = make_float4(y.a, y.b, y.c, 0.0f);
-}
-// ... as ONE comparison: trace |trace| + 0.30 frob_sq < 0 (a ballot less per voxel than the two-sided form: the walk is short of SGPRs)
-#ifdef HM_TRACE_ALL       // (test build: every masked voxel is queued and solved; tools/soak_crc.py compares the frames of the two builds)
-#define HM_TRACE_OK(tr, fsq) (true)
-#else
-// A frob_sq that overflowed float32 (+inf, or NaN) says nothing about the trace: such a voxel is solved (its eigenvalues are taken in
-// float64 from finite components and can give a response > 0: tools/probe_overflow.py, volumes scaled by 1e16 ... 1e17).  The pair
-// walk applies the clause in MODE 1 only: a MODE 2 pass that meets an inf is discarded and redone in MODE 1 (pipeline.py, chain.inc).
-#define HM_TRACE_OK(tr, fsq) (((tr) * fabsf(tr) + HM_TRACE_C * (fsq) < 0.0f) || !((fsq) < __int_as_float(0x7f800000)))
-#endif
-#define HM_TX 64
-#define HM_SLOTS 8                    // Z-loop unroll (ring and buffer indices are compile-time inside a group)
-#ifndef HM_ZCHUNK
-#define HM_ZCHUNK 64
-#endif
-#define HM_DEPTH 4         // planes in flight in registers; divides HM_SLOTS so that the unrolled loop indexes them statically
-#define HM_REGION (HM_ZCHUNK * 64)     // queue entries a wave can produce
-#define HM_SPEC_CAP (HM_ZCHUNK * 32)    // MODE 2: entries per region (half the worst case; overflow -> MODE 1)
-#define HM_UNDECIDED 0x80000000u       // MODE 2: idx flag of a voxel whose h_mask the resolve kernel decides
-
-// A constant float32 divisor, two exact implementations of a/d:
-//  FAST : q = a*y; r = fma(-q,d,a); q' = fma(r,y,q) with y = RN(1/d) -- three float32 instructions.  This
-//         sequence is correctly rounded for most but not all d, so nl_hessian_stats PROVES it for the
-//         six divisors in use by exhaustion (divcheck_kernel: all 2^23 significands; scaling a by 2^k
-//         scales q, r, q' exactly, so one binade covers every normal a) before selecting this path.
-//  !FAST: (float)((double)a * RN64(1/d)), exact for every d (see div_c).
-//  TWO  : q' = fma(a, yh, a*yl) with yh = RN(1/d), yl = RN(1/d - yh) (Brisebarre & Muller, "Correctly rounded multiplication
-//         by arbitrary precision constants") -- two float32 instructions, again exact for most d only and PROVEN the same way
-//         before it is selected (FAST = 2; the pair kernel alone has this variant).  One binade again covers every a whose
-//         partial product a*yl stays normal (|a| > ~1e-31 / |yl|); below that the sequence can differ in the last bit, like the
-//         sub-normal quotients of FAST -- differences of float32 image values are 0 or many orders of magnitude above it.
-template <int FAST> struct Dv;
-template <> struct Dv<1> {
-    float d, y;
-    __device__ __forceinline__ float div(float a) const { const float q = a * y; const float r = fmaf(-q, d, a); return fmaf(r, y, q); }
-};
-template <> struct Dv<2> {
-    float yl, y;
-    __device__ __forceinline__ float div(float a) const { return fmaf(a, y, a * yl); }
-};
-template <> struct Dv<0> {
-    double r;
-    __device__ __forceinline__ float div(float a) const { return (float)((double)a * r); }
-};
-template <int FAST> struct HessDv { Dv<FAST> z, y, x, z2, y2, x2; };   // float32(h) and float32(2h) per axis
-
-// Global queue of voxels to solve.  Entry e = two float4: (h0,h1,h2,h3), (h4,h5,idx,-) with idx the voxel offset
-// relative to the first plane of the launch.  Wave w of workgroup b owns entries [r*HM_REGION, (r+1)*HM_REGION)
-// with r = b*waves_per_group + w and reports how many it wrote in count[r].
-struct VQueue {
-    float4 *ent;
-    unsigned int *count;
-};
-
-template <int M>
-__global__ void __launch_bounds__(256)
-divcheck_kernel(Dv<M> dv, float d, unsigned int *__restrict__ bad) {
-    const unsigned int i = blockIdx.x * 256u + threadIdx.x;               // 2^23 significands of [1,2)
-    const float a = __uint_as_float(0x3f800000u | i);
-    if (dv.div(a) != a / d || dv.div(-a) != -a / d) atomicOr(bad, 1u);
-}
-
 // -------------------------------------------------------------------------------------------------
 // The FIRST derivatives are shared through LDS.  np.gradient applied twice
 // evaluates every first derivative several times when it is fused per voxel (d/dz g at (y+-1,x), (y,x+-1) and
@@ -145,7 +47,6 @@ divcheck_kernel(Dv<M> dv, float d, unsigned int *__restrict__ bad) {
 // -------------------------------------------------------------------------------------------------
 #define HG_RP (HM_TX + 4)              // raw tile pitch
 #define HG_GP (HM_TX + 2)              // gradient tile pitch
-#define HG_RSLOT(zz) ((int)(((unsigned)((zz) - zc0 + 8)) & 3u))
 template <int TY> struct HGCfg {
     static constexpr int NT = HM_TX * TY;
     static constexpr int RPLANE = HG_RP * (TY + 4);
@@ -466,407 +367,3 @@ hessian_g_kernel(const float *__restrict__ g, unsigned long long *__restrict__ c
         }
     }
 }
-
-// Dense eigen-solve + Frangi response over the queue regions (filtering.py:583-584, 744-766), then the running
-// maximum over scales (filtering.py:846-848).  One wave per region; `base` = voxel offset of the launch's first plane.
-// RESOLVE (after a MODE 2 pass): entries flagged undecided first take the exact h_mask test; those that pass are
-// counted, AND-ed with the earlier scales' mask bit, recorded in this scale's mask word (atomicOr: the pass wrote
-// the decided bits) and, if still alive and not excluded by their trace, solved like the others.
-template <bool RESOLVE>
-__global__ void __launch_bounds__(256)
-vesselness_queue_kernel(const float4 *__restrict__ ent, const unsigned int *__restrict__ count, unsigned int nregions,
-                        float *__restrict__ vmax, i64 base, VessP vp, unsigned long long *cmask64,
-                        const unsigned long long *pmask64, int wpr, int ny, int nx, i64 zbase,
-                        unsigned long long *__restrict__ mask_count, const float *__restrict__ dev_params) {
-    // inside a device-resident threshold chain (chain.inc: the head of a ChainScale record): gamma_sq, fsq_min, m_inf were
-    // decided by a kernel
-    if (dev_params) { vp.gamma_sq = dev_params[2]; vp.fsq_min = dev_params[3]; vp.m_inf = __float_as_int(dev_params[4]); }
-    // A wave walks several regions (the launcher caps the grid): with one short-lived wave per region the kernel took
-    // the same 7.7 ms/step whether it solved the eigenproblems or not -- wave start-up and the dependent count -> entries
-    // loads dominated; 16384 workgroups x 4 waves, 8 regions each at 1024^3, bring it to 5.3 ms.  The next region's
-    // count is requested before this region's entries are worked on.
-    unsigned int passed = 0;
-    // The running-maximum store of an entry is issued at the top of the NEXT trip (round 4).  vmcnt counts loads and stores in
-    // order, and the compiler has to wait for "everything" where the prefetched entry changes registers at the end of a trip: with
-    // the store as the youngest operation that wait was the store's full round trip, once per trip, with nothing of this wave
-    // behind it.  Issued before the next trip's loads, the store completes behind the eigen-solve like they do.
-    bool st_pending = false;
-    i64 st_at = 0;
-    float st_val = 0.0f;
-    const unsigned int rstep = gridDim.x * 4u;
-    unsigned int r = blockIdx.x * 4u + (threadIdx.x >> 6);
-    unsigned int n_next = r < nregions ? count[r] : 0u;
-    for (; r < nregions; r += rstep) {
-    unsigned int n = n_next;
-    n_next = (r + rstep < nregions) ? count[r + rstep] : 0u;
-    if (RESOLVE && n > (unsigned int)vp.qcap) n = (unsigned int)vp.qcap;
-    const float4 *e = ent + (size_t)r * (size_t)vp.qcap * 2;
-    // A lane's entries are 64 apart; the NEXT entry is requested before this one is worked on, and the running maximum of
-    // this entry's voxel is requested before its eigen-solve (~500 float64 instructions) instead of after it: the kernel
-    // waits (82 % of its wave cycles in round 2), it does not compute -- both latencies now pass behind the arithmetic.
-    unsigned int i = threadIdx.x & 63u;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    if (i < n) qent_load(e, i, a, b);
-    // The region's first entry is "used" here, so that the loop is entered with no load outstanding: the compiler merges the loop
-    // header's wait over both ways in, and the first trip's pending loads put a vmcnt(0) right behind the store below on every trip.
-    asm volatile("" :: "v"(a.x), "v"(b.x));
-    for (; i < n; i += 64u) {
-        if (st_pending) { vmax[st_at] = st_val; st_pending = false; }
-        const float4 a0 = a, b0 = b;
-        if (i + 64u < n) qent_load(e, i + 64u, a, b);
-        const float h[6] = {a0.x, a0.y, a0.z, a0.w, b0.x, b0.y};
-        if (vp.all_ones) {                      // uniform; see VessP::nan_flag
-            if ((h[0] != h[0]) | (h[1] != h[1]) | (h[2] != h[2]) | (h[3] != h[3]) | (h[4] != h[4]) | (h[5] != h[5])) *vp.nan_flag = 1u;
-        }
-        unsigned int idx = __float_as_uint(b0.z);
-        const bool undecided = RESOLVE && (idx & HM_UNDECIDED);
-        idx &= ~HM_UNDECIDED;
-        const i64 c = base + idx;
-        // vesselness >= 0 everywhere and the volume is all zeros before the first scale: `val > cur` is the running maximum
-        // AND the test that keeps zero responses (37 % of the entries) from being written
-        const float cur = vp.first ? 0.0f : vmax[c];
-        if (undecided) {
-            const float fsq = frob_sq_of(h);
-            if (!((fsq >= vp.fsq_min) && (fsq < __int_as_float(0x7f800000) || vp.m_inf))) continue;
-            if ((i64)idx >= vp.idx_lo && (i64)idx < vp.idx_hi) ++passed;
-            const i64 plane = (i64)ny * nx;
-            const i64 zl = idx / plane;
-            const int rem = (int)(idx - zl * plane);
-            const int yy = rem / nx, xx = rem - yy * nx;
-            const i64 word = ((zbase + zl) * ny + yy) * wpr + (xx >> 6);
-            const unsigned long long bit = 1ull << (xx & 63);
-            if (vp.have_prev && !(pmask64[word] & bit)) continue;
-            atomicOr(&cmask64[word], bit);
-            const float tr = h[0] + h[3] + h[5];
-            if (!HM_TRACE_OK(tr, fsq)) continue;
-        }
-        float l1, l2, l3;
-        eig3_sorted_abs(h, l1, l2, l3);
-        const float val = frangi3(l1, l2, l3, vp.alpha_sq, vp.beta_sq, vp.gamma_sq);
-        if (val > cur) { st_pending = true; st_at = c; st_val = val; }
-    }
-    }
-    if (st_pending) vmax[st_at] = st_val;
-    if (RESOLVE) {
-        unsigned long long t = wave_sum_u64((unsigned long long)passed);
-        if ((threadIdx.x & 63u) == 0 && t) atomicAdd(mask_count, t);
-    }
-}
-
-#ifndef NL_HV_UNIT       // (the walk's own translation unit, nellie_hv.hip, takes the kernels above only: the ones below are not templates)
-// vesselness * masks (filtering.py:926); counts voxels > 0 on the owned planes.
-// The cumulative mask is a bit mask: one 64-bit word per 64 consecutive x of a row (row pitch `wpr` words).
-__global__ void __launch_bounds__(256)
-finish_kernel(float *__restrict__ vmax, const unsigned long long *__restrict__ cmask64, int nslots, i64 slot_words, int wpr,
-              VolGeom v, i64 z0, i64 z1, i64 cnt_lo, i64 cnt_hi, unsigned long long *__restrict__ npos) {
-    // one thread = 4 consecutive x of one row (they share a mask word); rows are padded to a multiple of 4 here
-    const i64 qpr = (v.nx + 3) / 4;                                    // quads per row
-    const i64 total = (z1 - z0) * v.ny * qpr;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    const bool vec = (v.nx & 3) == 0;
-    unsigned long long cnt = 0;
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const i64 row = t / qpr;
-        const i64 x0 = (t % qpr) * 4;
-        const i64 zloc = z0 + row / v.ny;
-        const bool counted = zloc >= cnt_lo && zloc < cnt_hi;
-        unsigned long long bits = ~0ull;
-        for (int k = 0; k < nslots; ++k) bits &= cmask64[k * slot_words + (z0 * v.ny + row) * wpr + (x0 >> 6)];
-        const unsigned int b4 = (unsigned int)(bits >> (x0 & 63)) & 0xFu;
-        float *p = vmax + (z0 * v.ny + row) * v.nx + x0;
-        if (vec) {
-            float4 val = *reinterpret_cast<float4 *>(p);
-            if (b4 != 0xFu) {
-                if (!(b4 & 1u)) val.x = 0.0f;
-                if (!(b4 & 2u)) val.y = 0.0f;
-                if (!(b4 & 4u)) val.z = 0.0f;
-                if (!(b4 & 8u)) val.w = 0.0f;
-                *reinterpret_cast<float4 *>(p) = val;
-            }
-            if (counted) cnt += (val.x > 0.0f) + (val.y > 0.0f) + (val.z > 0.0f) + (val.w > 0.0f);
-        } else {
-            for (int q = 0; q < 4 && x0 + q < v.nx; ++q) {
-                float val = p[q];
-                if (!((b4 >> q) & 1u)) { val = 0.0f; p[q] = 0.0f; }
-                if (counted && val > 0.0f) cnt++;
-            }
-        }
-    }
-    block_add_u64(wave_sum_u64(cnt), npos);
-}
-
-// filtering.py:964-966: mask = f > thr; binary_opening (6-conn cross, one iteration, border_value 0); f * mask.
-// Done on BIT masks: pack (rl_threshold_pack_kernel), erode, dilate (word-wide logic on 1 bit/voxel), apply.
-// Planes [z0, z1) are produced from planes [z0-1, z1+1) of the input bits; neighbours outside the GLOBAL volume
-// count as 0 (border_value), ghost planes of a slab are real neighbours.
-template <int DILATE>
-__global__ void __launch_bounds__(256)
-bits_morph6_kernel(const unsigned long long *__restrict__ in, unsigned long long *__restrict__ out, VolGeom v, int wpr, i64 z0, i64 z1,
-                   int two_d) {
-    const i64 nw = (z1 - z0) * v.ny * wpr;
-    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nw) return;
-    const int w = (int)(t % wpr);
-    const i64 row_in_range = t / wpr;
-    const i64 y = row_in_range % v.ny, z = z0 + row_in_range / v.ny;
-    const i64 row = z * v.ny + y;
-    const unsigned long long cur = in[row * wpr + w];
-    const unsigned long long lft = (cur << 1) | ((w > 0) ? (in[row * wpr + w - 1] >> 63) : 0ull);           // x-1
-    const unsigned long long rgt = (cur >> 1) | ((w + 1 < wpr) ? (in[row * wpr + w + 1] << 63) : 0ull);    // x+1
-    const i64 gz = v.gz0 + z;
-    // a 2-D image has no Z neighbours in its (4-connected) structuring element: neutral for AND / OR
-    const unsigned long long none = DILATE ? 0ull : ~0ull;
-    const unsigned long long up = two_d ? none : ((gz > 0) ? in[(row - v.ny) * wpr + w] : 0ull);
-    const unsigned long long dn = two_d ? none : ((gz < v.gnz - 1) ? in[(row + v.ny) * wpr + w] : 0ull);
-    const unsigned long long no = (y > 0) ? in[(row - 1) * wpr + w] : 0ull;
-    const unsigned long long so = (y < v.ny - 1) ? in[(row + 1) * wpr + w] : 0ull;
-    unsigned long long r = DILATE ? (cur | lft | rgt | up | dn | no | so) : (cur & lft & rgt & up & dn & no & so);
-    const int rem = (int)v.nx - w * 64;
-    if (rem < 64) r &= (1ull << rem) - 1ull;          // keep the tail bits of a row at 0
-    out[row * wpr + w] = r;
-}
-
-__global__ void __launch_bounds__(256)
-apply_bits_kernel(const float *__restrict__ f, const unsigned long long *__restrict__ bits, float *__restrict__ out, VolGeom v,
-                  int wpr, i64 z0, i64 z1) {
-    const i64 qpr = (v.nx + 3) / 4;
-    const i64 total = (z1 - z0) * v.ny * qpr;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    const bool vec = (v.nx & 3) == 0;
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const i64 row = z0 * v.ny + t / qpr;
-        const i64 x0 = (t % qpr) * 4;
-        const unsigned int b4 = (unsigned int)(bits[row * wpr + (x0 >> 6)] >> (x0 & 63)) & 0xFu;
-        const float *p = f + row * v.nx + x0;
-        float *o = out + row * v.nx + x0;
-        if (vec) {
-            float4 a = *reinterpret_cast<const float4 *>(p);
-            // frame * mask: a False mask gives +-0 with the sign of the value, exactly numpy's float * bool
-            if (!(b4 & 1u)) a.x *= 0.0f;
-            if (!(b4 & 2u)) a.y *= 0.0f;
-            if (!(b4 & 4u)) a.z *= 0.0f;
-            if (!(b4 & 8u)) a.w *= 0.0f;
-            *reinterpret_cast<float4 *>(o) = a;
-        } else {
-            for (int k = 0; k < 4 && x0 + k < v.nx; ++k) o[k] = ((b4 >> k) & 1u) ? p[k] : p[k] * 0.0f;
-        }
-    }
-}
-
-// Fused finish + threshold pack (filtering.py:926, 964): bit = alive && vesselness > thr.  One wave per row; the
-// vesselness is only read where the cumulative mask has bits.  Counts alive voxels > 0 on the counted rows.
-__global__ void __launch_bounds__(256)
-pack_masked_kernel(const float *__restrict__ f, const unsigned long long *__restrict__ alive, unsigned long long *__restrict__ bits,
-                   float thr_host, const float *__restrict__ thr_dev, int nx, i64 row0, i64 row1, int wpr, i64 cnt_row0, i64 cnt_row1,
-                   unsigned long long *__restrict__ npos) {
-    const float thr = thr_dev ? *thr_dev : thr_host;          // decided by a kernel (nl_tail_enqueue) or by the host
-    const i64 wstride = ((i64)gridDim.x * blockDim.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    unsigned long long cnt = 0;
-    // the row's mask words in one coalesced load (lane l holds word l) instead of a dependent load per trip; the NEXT row's words
-    // are requested before this row is worked on
-    const bool row_words = wpr <= 64;
-    const i64 first = row0 + (((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    unsigned long long mine_next = (row_words && first < row1 && lane < wpr) ? alive[first * wpr + lane] : 0ull;
-    // ... and this row's result words leave at the top of the next trip, BEFORE its loads: vmcnt counts in order, and a store that is
-    // the youngest operation when the prefetched words are taken over would be waited for (see vesselness_queue_kernel)
-    unsigned long long st_res = 0ull;
-    i64 st_row = -1;
-    for (i64 row = first; row < row1; row += wstride) {
-        const bool counted = row >= cnt_row0 && row < cnt_row1;
-        const float *fr = f + row * nx;
-        const unsigned long long mine = mine_next;
-        if (row_words) {
-            if (st_row >= 0 && lane < wpr) bits[st_row * wpr + lane] = st_res;
-            mine_next = (row + wstride < row1 && lane < wpr) ? alive[(row + wstride) * wpr + lane] : 0ull;
-            // Round 4: only the words that hold alive voxels are visited, eight of them (eight independent loads per lane) per trip,
-            // and the row's result words leave in ONE store (lane l holds word l).  The kernel is bound by its dependent round
-            // trips, not by bytes (1.1 B/voxel fetched): a 1024-wide row took 1 + 4 of them, now 1 + 1 (most rows have < 8 words alive).
-            unsigned long long nz = __ballot(mine != 0ull), res = 0ull;
-            while (nz) {                                                 // uniform
-                int wi[8];
-                float v[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    wi[k] = nz ? (int)__builtin_ctzll(nz) : -1;
-                    nz &= nz - 1ull;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const unsigned long long a = wi[k] >= 0 ? wave_read_u64(mine, wi[k]) : 0ull;
-                    const int x = wi[k] * 64 + lane;
-                    v[k] = (((a >> lane) & 1ull) && x < nx) ? fr[x] : 0.0f;   // 0 fails both tests below (thr >= 0)
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (wi[k] < 0) break;                                // uniform
-                    const unsigned long long b = __ballot(v[k] > thr && v[k] > 0.0f);
-                    const unsigned long long pb = __ballot(v[k] > 0.0f);
-                    if (counted) cnt += (unsigned long long)__builtin_popcountll(pb);      // wave-uniform
-                    if (lane == wi[k]) res = b;
-                }
-            }
-            st_res = res; st_row = row;
-            continue;
-        }
-        for (int w0 = 0; w0 < wpr; w0 += 4) {                          // four words (four independent loads) in flight
-            unsigned long long a[4];
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                a[k] = (w0 + k < wpr) ? alive[row * wpr + w0 + k] : 0ull;           // (rows of more than 64 words)
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int x = (w0 + k) * 64 + lane;
-                v[k] = (((a[k] >> lane) & 1ull) && x < nx) ? fr[x] : 0.0f;   // 0 fails both tests below (thr >= 0)
-            }
-            unsigned long long b[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                b[k] = __ballot(v[k] > thr && v[k] > 0.0f);
-                const unsigned long long pb = __ballot(v[k] > 0.0f);
-                if (counted) cnt += (unsigned long long)__builtin_popcountll(pb);      // wave-uniform
-            }
-            if (lane < 4 && w0 + lane < wpr) bits[row * wpr + w0 + lane] = lane == 0 ? b[0] : (lane == 1 ? b[1] : (lane == 2 ? b[2] : b[3]));
-        }
-    }
-    if (st_row >= 0 && lane < wpr) bits[st_row * wpr + lane] = st_res;
-    block_add_u64(cnt, npos);
-}
-
-// filtering.py:969-1000 (`_remove_edges`): per Z plane (a 2-D image is its single plane), the rows holding any non-zero
-// value span [rmin, rmax]; min(margin, rmax - rmin + 1) rows at both ends of that span are zeroed.  One workgroup per
-// plane; counts the values > 0 that remain (the reference's `sum(frame) > 0` test of a non-negative frame).
-__global__ void __launch_bounds__(256)
-remove_edges_kernel(float *__restrict__ f, VolGeom v, i64 plane0, int margin, i64 cnt_lo, i64 cnt_hi, unsigned long long *__restrict__ npos) {
-    __shared__ int s_min, s_max;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int ny = (int)v.ny, nx = (int)v.nx;
-    float *p = f + (plane0 + blockIdx.x) * v.ny * v.nx;
-    if (threadIdx.x == 0) { s_min = 0x7fffffff; s_max = -1; }
-    __syncthreads();
-    unsigned long long total = 0;
-    for (int row = w; row < ny; row += 4) {
-        const float *r = p + (i64)row * nx;
-        bool any = false;
-        for (int x = lane; x < nx; x += 64) {
-            const float val = r[x];
-            any = any || (val != 0.0f);
-            total += (val > 0.0f) ? 1ull : 0ull;
-        }
-        if (__ballot(any) != 0ull && lane == 0) { atomicMin(&s_min, row); atomicMax(&s_max, row); }
-    }
-    __syncthreads();
-    const int rmin = s_min, rmax = s_max;
-    unsigned long long removed = 0;
-    if (rmax >= 0) {
-        const int use = margin < rmax - rmin + 1 ? margin : rmax - rmin + 1;
-        // rows [rmin, rmin + use) and [rmax - use + 1, rmax], each once even where the two stretches overlap
-        const int a1 = rmin + use, b0 = (rmax - use + 1 > a1) ? rmax - use + 1 : a1;
-        const int n_rows = (a1 - rmin) + (rmax + 1 - b0);
-        for (int k = w; k < n_rows; k += 4) {
-            const int row = k < a1 - rmin ? rmin + k : b0 + (k - (a1 - rmin));
-            float *r = p + (i64)row * nx;
-            for (int x = lane; x < nx; x += 64) {
-                removed += (r[x] > 0.0f) ? 1ull : 0ull;
-                r[x] = 0.0f;
-            }
-        }
-    }
-    total = wave_sum_u64(total);
-    removed = wave_sum_u64(removed);
-    const i64 zl = plane0 + blockIdx.x;            // ghost planes are trimmed like the owned ones (the opening reads them) but not counted
-    const bool counted = zl >= cnt_lo && zl < cnt_hi;
-    block_add_u64(counted ? total - removed : 0ull, npos);   // a wave's difference may wrap; the sums over waves and planes do not
-}
-
-// out = opened bit ? vesselness : 0 (filtering.py:966 for a non-negative frame): reads only where bits are set.
-// One wave per row, 256 floats (1 KiB) per store instruction; launched with one wave per row (a pure 4 B/voxel write
-// wants many small workgroups: 5.9 TB/s against 5.2 with a capped grid-stride grid on this part).
-#ifndef APPLY_ROWS
-#define APPLY_ROWS 2
-#endif
-__global__ void __launch_bounds__(256)
-apply_bits_pos_kernel(const float *__restrict__ f, const unsigned long long *__restrict__ bits, float *__restrict__ out, VolGeom v,
-                      int wpr, i64 z0, i64 z1) {
-    const i64 nrows = (z1 - z0) * v.ny;
-    const i64 wstride = ((i64)gridDim.x * blockDim.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const int nx = (int)v.nx;
-    const bool vec = (nx & 3) == 0;
-    if (vec && wpr <= 64) {
-        // APPLY_ROWS rows per wave: a row is a chain of dependent round trips (mask words -> the values under them -> the stores), and
-        // a wave that owns one row has one such chain in flight.
-        constexpr int RR = APPLY_ROWS;
-        for (i64 r0 = (((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * RR; r0 < nrows; r0 += wstride * RR) {
-            unsigned long long mine[RR];
-            bool empty[RR];
-#pragma unroll
-            for (int j = 0; j < RR; ++j) {
-                // the row's mask words in one load (lane l holds word l)
-                mine[j] = (r0 + j < nrows && lane < wpr) ? bits[(z0 * v.ny + r0 + j) * wpr + lane] : 0ull;
-            }
-#pragma unroll
-            for (int j = 0; j < RR; ++j) empty[j] = __ballot(mine[j] != 0ull) == 0ull;      // uniform
-            for (int xb = 0; xb < nx; xb += 1024) {                                       // four 1-KiB pieces (their reads, if any, first) per trip
-                float4 a[RR][4];
-                unsigned int b4[RR][4];
-#pragma unroll
-                for (int j = 0; j < RR; ++j) {
-                    const float *p = f + (z0 * v.ny + r0 + j) * nx;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int x0 = xb + k * 256 + lane * 4;
-                        a[j][k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                        b4[j][k] = 0u;
-                        if (!empty[j] && x0 < nx) {
-                            const unsigned long long w = __shfl(mine[j], (x0 >> 6) & 63);
-                            b4[j][k] = (unsigned int)(w >> (x0 & 63)) & 0xFu;
-                            if (b4[j][k]) a[j][k] = *reinterpret_cast<const float4 *>(p + x0);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < RR; ++j) {
-                    if (r0 + j >= nrows) break;                                            // uniform
-                    float *o = out + (z0 * v.ny + r0 + j) * nx;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int x0 = xb + k * 256 + lane * 4;
-                        if (x0 < nx) {
-                            if (!(b4[j][k] & 1u)) a[j][k].x = 0.0f;
-                            if (!(b4[j][k] & 2u)) a[j][k].y = 0.0f;
-                            if (!(b4[j][k] & 4u)) a[j][k].z = 0.0f;
-                            if (!(b4[j][k] & 8u)) a[j][k].w = 0.0f;
-                            *reinterpret_cast<float4 *>(o + x0) = a[j][k];
-                        }
-                    }
-                }
-            }
-        }
-        return;
-    }
-    for (i64 r = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < nrows; r += wstride) {
-        const i64 row = z0 * v.ny + r;
-        const float *p = f + row * nx;
-        float *o = out + row * nx;
-        for (int x0 = lane * 4; x0 < nx; x0 += 256) {
-            const unsigned int b4 = (unsigned int)(bits[row * wpr + (x0 >> 6)] >> (x0 & 63)) & 0xFu;
-            if (vec) {
-                float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (b4) {
-                    a = *reinterpret_cast<const float4 *>(p + x0);
-                    if (!(b4 & 1u)) a.x = 0.0f;
-                    if (!(b4 & 2u)) a.y = 0.0f;
-                    if (!(b4 & 4u)) a.z = 0.0f;
-                    if (!(b4 & 8u)) a.w = 0.0f;
-                }
-                *reinterpret_cast<float4 *>(o + x0) = a;
-            } else {
-                for (int k = 0; k < 4 && x0 + k < nx; ++k) o[x0 + k] = ((b4 >> k) & 1u) ? p[x0 + k] : 0.0f;
-            }
-        }
-    }
-}
-#endif  // NL_HV_UNIT

@@ -1,4 +1,4 @@
-// Part of libnellie_hip.so (gfx950): included by nellie_hip.hip after hessian.inc (VessP, VQueue, Dv, HessDv, HM_*).
+// Part of libnellie_hip.so (gfx950): included by nellie_hv.hip after walk_common.h (VessP, VQueue, Dv, HessDv, HM_*).
 // =================================================================================================
 // Hessian walk, two voxels per thread (rows y and y + RS of the tile), packed float32 arithmetic
 // =================================================================================================

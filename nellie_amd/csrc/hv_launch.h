@@ -3,7 +3,9 @@
 // waves per SIMD, and the ILP-first scheduler orders its 280-instruction steps 5 % better (14.5 -> 13.7 ms per 1024^3 frame) -- while the
 // same switch costs the fused Gaussian pass 15 % (9.6 -> 11.0 ms), so it cannot be a flag of the whole library.  Scheduling moves no
 // rounding point: the kernels' results are bit for bit the same either way (the whole GPU suite runs on this build).
-// nellie_hip.hip fills an HvLaunch and calls nl_hv_launch; everything else about the walk (queue, records, streams) stays there.
+// nellie_walk.hip plans the launch (walk_plan.h), fills an HvLaunch and calls nl_hv_launch -- or launches the one-voxel kernel of hessian.inc
+// itself, which keeps the library's default flags; everything else about the walk (queue, records, streams) is there too.
+// After walk_common.h (VessP, VQueue, Dv, HessDv).
 #pragma once
 #ifndef NL_HV_VARIANTS
 #define NL_HV_VARIANTS 0       // 1: the rejected forms of the walk are built too (nellie_hv.hip)
@@ -33,7 +35,7 @@ struct HvLaunch {
 
 hipError_t nl_hv_launch(const HvLaunch &a);
 
-// divisors of np.gradient as the kernels take them (FAST: see hessian.inc)
+// divisors of np.gradient as the kernels take them (FAST: see walk_common.h)
 static inline Dv<1> dv_fast(float d) { return Dv<1>{d, (float)(1.0 / (double)d)}; }
 static inline Dv<2> dv_two(float d) {       // yh = RN32(1/d), yl = RN32(1/d - yh), both from the float64 quotient
     const double inv = 1.0 / (double)d;

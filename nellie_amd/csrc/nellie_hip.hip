@@ -1,12 +1,12 @@
 // libnellie_hip.so -- hand-written HIP for gfx950 (MI355X): Nellie's Filter -> Label hot path.  This unit: context lifetime, the
-// Gaussian cascade, the Hessian walk's launchers, the device chain and the epilogue (sampling: nellie_sample.hip, collectives:
-// nellie_comm.hip).  C-ABI in include/nellie_amd.h.  Compile with -ffp-contract=off: every float operation
+// Gaussian cascade, the device chain, the 2-D path and the epilogue (the Hessian walk: nellie_walk.hip, sampling: nellie_sample.hip,
+// collectives: nellie_comm.hip).  C-ABI in include/nellie_amd.h.  Compile with -ffp-contract=off: every float operation
 // below is meant to round exactly where numpy/scipy round.
 #include "nl_host.h"
 
-#include "hessian.inc"
-#include "hessian_pair.inc"
-#include "hv_launch.h"
+#include "walk_common.h"
+#include "walk_plan.h"
+#include "mask_volume.inc"
 #include "filter2d.inc"
 #include "thresholds.inc"
 #include "chain.inc"
@@ -22,92 +22,6 @@ bool gyx_tiled() {
     if (on < 0) { const char *e = getenv("NELLIE_GYX_TILE"); on = (e && !atoi(e)) ? 0 : 1; }
     return on != 0;
 }
-// grid of the queue kernels: NELLIE_RESOLVE_GRID caps it (waves then walk several regions each).  Measured at 512 x 1024 x 1024
-// (ms/step of the resolve group): 1792 workgroups 2.77, 2048 2.69, 4096 2.67, 8192 2.79, 16384 (rounds 1-2) and more 3.16 --
-// a wave that walks 8-16 regions amortises its start-up and evens out the regions' very different entry counts
-static unsigned resolve_grid(unsigned blocks) {
-    static long cap = -1;
-    if (cap < 0) { const char *e = getenv("NELLIE_RESOLVE_GRID"); cap = e ? atol(e) : 8192; }
-    return (cap > 0 && (unsigned)cap < blocks) ? (unsigned)cap : blocks;
-}
-// tile height of the Hessian kernels (experiment knob; 8 -> 512-thread workgroups, 16 -> 1024)
-static int hm_ty() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("NELLIE_HM_TY"); v = (e && atoi(e) == 16) ? 16 : 8; }
-    return v;
-}
-// Hessian walk: two voxels per thread (hessian_pair.inc), tile 2*RS rows; NELLIE_HV_RS = 8 (default) / 4, 0 = the
-// one-voxel kernel of hessian.inc
-static int hv_rs_env() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("NELLIE_HV_RS"); v = e ? atoi(e) : 8; if (v != 0 && v != 8 && !(NL_HV_VARIANTS && v == 16)) v = 8; }
-    return v;
-}
-// the pair kernel addresses the planes of a Z chunk through one buffer resource (32-bit byte offsets)
-static int hv_rs(const nl_ctx *c) { return ((i64)(HM_ZCHUNK + 4) * c->ny * c->nx * 4 < ((i64)1 << 32)) ? hv_rs_env() : 0; }
-static HessDv<1> hessdv_fast(const nl_ctx *c) { return hessdv_fast(hessp(c)); }      // (dv_* and the HessP forms: hv_launch.h)
-static HessDv<0> hessdv_exact(const nl_ctx *c) { return hessdv_exact(hessp(c)); }
-// the pair walk (its own translation unit, hv_launch.h): division variant as proven for this context's divisors
-static int hv_fastv(const nl_ctx *c) { return c->fast_div2 ? 2 : (c->fast_div ? 1 : 0); }
-// pair-rows per lane of the pair walk (NELLIE_HV_NP=2: four voxels per lane at 2 waves / SIMD -- the round-5 experiment, hessian_pair.inc;
-// only instantiated for the 16-row tile with the two-instruction division)
-static int hv_np(const nl_ctx *c) {
-#if NL_HV_VARIANTS
-    const char *e = getenv("NELLIE_HV_NP");            // read per call: tests switch it inside one process
-    return (e && atoi(e) == 2 && hv_rs(c) == 8 && hv_fastv(c) == 2) ? 2 : 1;
-#else
-    (void)c;
-    return 1;
-#endif
-}
-// The wave-autonomous walk (round 6, hessian_dpp.inc): strips of 4 rows x 60 columns per wave, no LDS.  Statistics and one-pass modes; the
-// statistics and known-threshold modes (MODE 0 / 1: the two-pass fallback of a scale) stay with the pair kernel.  NELLIE_HV_DPP=1 selects it
-// for the one-pass walk (default: the pair kernel -- measured equal at 1024^3, profiles/r06_walk_dpp_production.txt).
-#define HD_SR 4
-#define HD_COLS 60
-static bool hv_dpp(const nl_ctx *c) {
-    const char *e = getenv("NELLIE_HV_DPP");            // read per call: tests switch it inside one process
-    return hv_rs(c) != 0 && e && atoi(e) == 1;
-}
-// Planes per wave: 128 where that leaves several rounds of waves (a chunk's prologue -- four planes loaded, the first derivatives of one --
-// is paid half as often), 32 on small frames (a 128 x 512 x 512 frame has 1152 strips: 64-plane chunks would fill three quarters of the
-// 3072 wave slots once), else 64.
-static int hd_zchunk(const nl_ctx *c, i64 nz, i64 strips) {
-    static int forced = -1;
-    if (forced < 0) { const char *e = getenv("NELLIE_HV_ZCHUNK"); forced = e ? atoi(e) : 0; }
-    auto fits = [&](int z) { return (i64)(z + 4) * c->ny * c->nx * 4 < ((i64)1 << 32); };
-    if (forced > 0 && (forced & 3) == 0 && fits(forced)) return forced;
-    if (fits(128) && strips * ((nz + 127) / 128) >= 8192) return 128;
-    if (fits(64) && strips * ((nz + 63) / 64) >= 4096) return 64;
-    return 32;
-}
-
-// Exhaustive proof that the 3-instruction division is exact for the six divisors in use.
-static int check_fast_div(nl_ctx *c, char *err, size_t errlen) {
-    const float ds[6] = {c->hz, c->hy, c->hx, c->hz2, c->hy2, c->hx2};
-    unsigned int *bad = (unsigned int *)c->d_small + 64;
-    NL_HIP(zero_small(bad, 12 * 4, c->stream));
-    for (int k = 0; k < 6; ++k) {
-        divcheck_kernel<1><<<(1u << 23) / 256, 256, 0, c->stream>>>(dv_fast(ds[k]), ds[k], bad + k);
-        divcheck_kernel<2><<<(1u << 23) / 256, 256, 0, c->stream>>>(dv_two(ds[k]), ds[k], bad + 6 + k);
-    }
-    NL_CHECK_LAUNCH();
-    unsigned int *h = (unsigned int *)c->h_small + 64;
-    NL_HIP(hipMemcpyAsync(h, bad, 12 * 4, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    c->fast_div = 1; c->fast_div2 = 1;
-    for (int k = 0; k < 6; ++k) {
-        const bool normal = ds[k] > 1e-30f && ds[k] < 1e30f;
-        if (h[k] || !normal) c->fast_div = 0;
-        if (h[6 + k] || !normal) c->fast_div2 = 0;
-    }
-    // NELLIE_EXACT_DIV=1: the float64 path everywhere; =3: at most the three-instruction sequence (A/B of the two-instruction one)
-    const char *e = getenv("NELLIE_EXACT_DIV");
-    if (e && atoi(e) == 1) { c->fast_div = 0; c->fast_div2 = 0; }
-    if (e && atoi(e) == 3) c->fast_div2 = 0;
-    return NL_OK;
-}
-
 
 extern "C" const char *nl_version(void) { return NL_VERSION; }
 
@@ -139,44 +53,10 @@ extern "C" int nl_device_name(int device, char *name, size_t namelen, char *err,
     return NL_OK;
 }
 
-// Global eigen queue: every wave of the vesselness kernel owns HM_REGION entries (32 bytes each), so one launch
-// needs (padded plane) x (Z chunks x HM_ZCHUNK) entries.  A launch covers as many Z chunks as fit 2^28 entries
-// (8 GiB); smaller volumes go in one launch.  NELLIE_VQ_CAP (entries) is a test knob to force several launches.
-static int64_t vq_padded_plane(int64_t ny, int64_t nx) { return ((nx + HM_TX - 1) / HM_TX) * HM_TX * (((ny + 31) / 32) * 32); }
-static int64_t vq_chunks(int64_t nzl, int64_t ny, int64_t nx) {
-    static int64_t lim = 0;
-    if (!lim) { const char *e = getenv("NELLIE_VQ_CAP"); lim = (e && atoll(e) > 0) ? atoll(e) : ((int64_t)1 << 28); }
-    const int64_t per_chunk = vq_padded_plane(ny, nx) * HM_ZCHUNK;
-    int64_t chunks = lim / per_chunk;
-    const int64_t need = (nzl + HM_ZCHUNK - 1) / HM_ZCHUNK;
-    if (chunks > need) chunks = need;
-    return chunks < 1 ? 1 : chunks;
-}
-static int64_t vq_entries(int64_t nzl, int64_t ny, int64_t nx) { return vq_chunks(nzl, ny, nx) * vq_padded_plane(ny, nx) * HM_ZCHUNK; }
-// One-pass (MODE 2) vesselness needs every region of the whole slab at once, HM_SPEC_CAP entries each; it is
-// offered when that fits NELLIE_SPEC_MAX_GB (default 64) GiB.  Returns 0 when it does not.
-static int64_t vq_spec_regions(int64_t nzl, int64_t ny, int64_t nx) {
-    return vq_padded_plane(ny, nx) / 64 * ((nzl + HM_ZCHUNK - 1) / HM_ZCHUNK);
-}
-static int64_t vq_spec_entries(int64_t nzl, int64_t ny, int64_t nx) {
-    static int64_t lim = -1;
-    if (lim < 0) { const char *e = getenv("NELLIE_SPEC_MAX_GB"); lim = (e ? atoll(e) : 64) << 30; }
-    const int64_t ent = vq_spec_regions(nzl, ny, nx) * HM_SPEC_CAP;
-    return ent * 32 <= lim ? ent : 0;
-}
-int64_t vq_alloc_entries(int64_t nzl, int64_t ny, int64_t nx) {
-    const int64_t a = vq_entries(nzl, ny, nx), b = vq_spec_entries(nzl, ny, nx);
-    return a > b ? a : b;
-}
-static int64_t vq_alloc_regions(int64_t nzl, int64_t ny, int64_t nx) {
-    const int64_t a = vq_entries(nzl, ny, nx) / HM_REGION, b = vq_spec_entries(nzl, ny, nx) ? vq_spec_regions(nzl, ny, nx) : 0;
-    return a > b ? a : b;
-}
-
 extern "C" int64_t nl_ctx_bytes(int64_t nz_local, int64_t ny, int64_t nx) {
     const int64_t n = nz_local * ny * nx;
-    const int64_t qe = vq_alloc_entries(nz_local, ny, nx);
-    return n * (4 * 4 + 3) + qe * 32 + vq_alloc_regions(nz_local, ny, nx) * 4 + (1 << 16) + ((n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1) * 4;
+    const VqAlloc vq = vq_alloc(nz_local, ny, nx);
+    return n * (4 * 4 + 3) + vq.entries * 32 + vq.regions * 4 + (1 << 16) + ((n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1) * 4;
 }
 
 extern "C" int nl_ctx_destroy(nl_ctx *c) {
@@ -281,12 +161,11 @@ extern "C" int nl_ctx_create(nl_ctx **out, int device, int64_t nzl, int64_t ny, 
     }
     if (ok) ok = alloc((void **)&c->d_rows, ((size_t)nzl * ny + 2) * 2 * 4);
     if (ok) ok = alloc(&c->d_small, 1 << 16);
-    c->vq_chunks = (int)vq_chunks(nzl, ny, nx);
     {
-        const size_t qe = (size_t)vq_alloc_entries(nzl, ny, nx);
-        if (ok) ok = alloc((void **)&c->d_vq, qe * 32);
-        if (ok) ok = alloc((void **)&c->d_vq_count, (size_t)vq_alloc_regions(nzl, ny, nx) * 4);
-        c->spec_ok = vq_spec_entries(nzl, ny, nx) > 0;
+        const VqAlloc vq = vq_alloc(nzl, ny, nx);
+        if (ok) ok = alloc((void **)&c->d_vq, (size_t)vq.entries * 32);
+        if (ok) ok = alloc((void **)&c->d_vq_count, (size_t)vq.regions * 4);
+        c->spec_ok = vq.spec_ok;
     }
     c->blk_cap = (n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1;
     if (ok) ok = alloc(&c->d_blk, (size_t)c->blk_cap * 4);
@@ -626,351 +505,6 @@ extern "C" int nl_gauss_commit(nl_ctx *c, char *err, size_t errlen) {
     return NL_OK;
 }
 
-static int set_spacing(nl_ctx *c, const double spacing[3], char *err, size_t errlen) {
-    if (!spacing) return nl_fail(err, errlen, NL_EINVAL, "spacing is NULL");
-    if ((!c->two_d && c->gnz < 2) || c->ny < 2 || c->nx < 2)
-        return nl_fail(err, errlen, NL_EINVAL, "Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.");
-    if (c->chk_spacing[0] != spacing[0] || c->chk_spacing[1] != spacing[1] || c->chk_spacing[2] != spacing[2]) c->fsq_cache_valid = 0;
-    c->hz = (float)spacing[0]; c->hy = (float)spacing[1]; c->hx = (float)spacing[2];
-    c->hz2 = (float)(2.0 * spacing[0]); c->hy2 = (float)(2.0 * spacing[1]); c->hx2 = (float)(2.0 * spacing[2]);
-    if (!c->have_spacing || c->chk_spacing[0] != spacing[0] || c->chk_spacing[1] != spacing[1] || c->chk_spacing[2] != spacing[2]) {
-        int rcx = check_fast_div(c, err, errlen);
-        if (rcx) return rcx;
-        c->chk_spacing[0] = spacing[0]; c->chk_spacing[1] = spacing[1]; c->chk_spacing[2] = spacing[2];
-    }
-    c->have_spacing = 1;
-    return NL_OK;
-}
-
-extern "C" int nl_set_spacing(nl_ctx *c, const double spacing[3], char *err, size_t errlen) {
-    NL_ENTER(c);
-    return set_spacing(c, spacing, err, errlen);
-}
-
-extern "C" int nl_hessian_stats(nl_ctx *c, const double spacing[3], float *max_abs, float *max_frob_sq, int *any_inf,
-                                char *err, size_t errlen) {
-    NL_ENTER(c);
-    { int rcs = set_spacing(c, spacing, err, errlen); if (rcs) return rcs; }
-    c->spec_valid = 0;
-    if (c->two_d) {
-        unsigned int *res2 = (unsigned int *)c->d_small;
-        NL_HIP(zero_small(res2, 16, c->stream));
-        {
-            ProfScope ps(c, "hessian_stats");
-            hessian2d_stats_kernel<<<grid2d_rows(c->nx, c->ny), 256, 0, c->stream>>>(gauss_cur(c), geom(c), hessp(c), res2);
-            NL_CHECK_LAUNCH();
-        }
-        unsigned int *h2 = (unsigned int *)c->h_small;
-        NL_HIP(hipMemcpyAsync(h2, res2, 16, hipMemcpyDeviceToHost, c->stream));
-        NL_HIP(hipStreamSynchronize(c->stream));
-        if (max_abs) memcpy(max_abs, &h2[0], 4);
-        if (max_frob_sq) memcpy(max_frob_sq, &h2[1], 4);
-        if (any_inf) *any_inf = (int)h2[2];
-        return NL_OK;
-    }
-    unsigned int *res = (unsigned int *)c->d_small;
-    NL_HIP(zero_small(res, 16, c->stream));
-    {
-        ProfScope ps(c, "hessian_stats");
-        const int ntx = (int)((c->nx + HM_TX - 1) / HM_TX), nty = (int)((c->ny + 15) / 16);
-        const int nzc = (int)((c->own_hi - c->own_lo + HM_ZCHUNK - 1) / HM_ZCHUNK);
-        VessP vp{};
-#define NL_LAUNCH_STATS(TYV, FASTV, HR)                                                                                   \
-        hessian_g_kernel<0, TYV, FASTV><<<(unsigned)(ntx * (int)((c->ny + TYV - 1) / TYV) * nzc), HGCfg<TYV>::NT,         \
-                                          HGCfg<TYV>::lds_bytes(), c->stream>>>(                                          \
-            gauss_cur(c), nullptr, nullptr, 0, geom(c), HR, vp, VQueue{}, (int)c->own_lo, (int)c->own_hi, ntx,        \
-            (int)((c->ny + TYV - 1) / TYV), res, nullptr)
-        if (false) {}
-        else if (hv_rs(c)) {
-            const int rsv = hv_rs(c), ntyv = (int)((c->ny + 2 * rsv - 1) / (2 * rsv));
-            NL_HIP(nl_hv_launch(HvLaunch{0, rsv, hv_np(c), hv_fastv(c), (unsigned)(ntx * ntyv * nzc), c->stream, gauss_cur(c), nullptr, nullptr, 0, geom(c),
-                                         hessp(c), vp, VQueue{}, (int)c->own_lo, (int)c->own_hi, ntx, ntyv, res, nullptr, nullptr}));
-        }
-        else if (hm_ty() == 8) { if (c->fast_div) NL_LAUNCH_STATS(8, true, hessdv_fast(c)); else NL_LAUNCH_STATS(8, false, hessdv_exact(c)); }
-        else { if (c->fast_div) NL_LAUNCH_STATS(16, true, hessdv_fast(c)); else NL_LAUNCH_STATS(16, false, hessdv_exact(c)); }
-#undef NL_LAUNCH_STATS
-        NL_CHECK_LAUNCH();
-    }
-    unsigned int *h = (unsigned int *)c->h_small;
-    NL_HIP(hipMemcpyAsync(h, res, 16, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
-    if (max_abs) memcpy(max_abs, &h[0], 4);
-    if (max_frob_sq) memcpy(max_frob_sq, &h[1], 4);
-    if (any_inf) *any_inf = (int)h[2];
-    return NL_OK;
-}
-
-extern "C" int nl_set_frob_norm(nl_ctx *c, float max_abs, float max_finite, char *err, size_t errlen) {
-    if (!c) return nl_fail(err, errlen, NL_EINVAL, "ctx is NULL");
-    c->frob_max_abs = max_abs; c->frob_max_finite = max_finite;
-    return NL_OK;
-}
-
-// h_mask = sqrt(frob_sq)/max_abs > thr (or > 0).  sqrt and the division by a positive constant are monotone, so the
-// mask is exactly {frob_sq >= x_min} for the smallest float32 x_min whose image passes the test; it is found by
-// bisection over the (ordered) bit patterns of the non-negative floats, with the same two IEEE operations the
-// volume op would do.  The kernel then needs one compare per voxel instead of a square root and a division.
-static float mask_threshold_on_fsq(float max_abs, int use_thr, float thr) {
-    auto pred = [&](float x) -> bool {
-        volatile float fr = sqrtf(x);
-        fr = fr / max_abs;
-        return use_thr ? (fr > thr) : (fr > 0.0f);
-    };
-    unsigned int lo = 0u, hi = 0x7f800000u;          // hi = +inf bits: "nothing finite passes"
-    float fmaxv; { unsigned int b = 0x7f7fffffu; memcpy(&fmaxv, &b, 4); }
-    if (!pred(fmaxv)) { float inf; memcpy(&inf, &hi, 4); return inf; }
-    hi = 0x7f7fffffu;
-    while (lo < hi) {                                 // smallest pattern with pred true
-        const unsigned int mid = lo + (hi - lo) / 2;
-        float x; memcpy(&x, &mid, 4);
-        if (pred(x)) hi = mid; else lo = mid + 1;
-    }
-    float r; memcpy(&r, &lo, 4);
-    return r;
-}
-
-#define NL_NAN_FLAG_OFF (52 << 10)      // byte offset in d_small of the "NaN Hessian solved" word (VessP::nan_flag), zeroed per frame
-// the planes [z0, z1) of the vesselness volume are all zero already: the frame's first cascade step did it in passing (gauss_zyx.inc)
-static inline bool vmax_is_zero(const nl_ctx *c, i64 z0, i64 z1) { return c->vmax_zero_hi > 0 && c->vmax_zero_lo <= z0 && z1 <= c->vmax_zero_hi; }
-static VessP make_vessp(nl_ctx *c, float gamma_sq, float alpha_sq, float beta_sq, int use_thr, float thr) {
-    VessP vp{};
-    vp.gamma_sq = gamma_sq; vp.alpha_sq = alpha_sq; vp.beta_sq = beta_sq; vp.use_thr = use_thr; vp.thr = thr;
-    vp.max_abs = c->frob_max_abs; vp.max_finite = c->frob_max_finite;
-    vp.cnt_lo = (int)c->own_lo; vp.cnt_hi = (int)c->own_hi;
-    vp.first = c->mask_slots_used == 0 ? 1 : 0;
-    vp.fsq_min = mask_threshold_on_fsq(c->frob_max_abs, use_thr, thr);
-    vp.m_inf = use_thr ? (c->frob_max_finite > thr) : (c->frob_max_finite > 0.0f);
-    vp.all_ones = (use_thr && thr == -INFINITY) ? 1 : 0;       // the host's way of saying mask=False (pipeline.py: thr_cmp = -inf)
-    vp.nan_flag = (unsigned int *)((char *)c->d_small + NL_NAN_FLAG_OFF);
-    c->last_fsq_min = vp.fsq_min;
-    return vp;
-}
-
-// The walk of a scale in MODE 2, enqueued: statistics into res[0..3] (all "max": bit patterns of non-negative floats, flags),
-// h_mask count of the decided voxels into *d_cnt (both zeroed by the caller).  dev_lohi != NULL: the bracket is read from device
-// memory by the kernel (chain.inc) and fsq_lo / fsq_hi are ignored.
-static int spec_enqueue(nl_ctx *c, const double spacing[3], float fsq_lo, float fsq_hi, int64_t z0, int64_t z1, unsigned int *res,
-                        unsigned long long *d_cnt, const float *dev_lohi, char *err, size_t errlen) {
-    if (z0 < 0 && z1 < 0) { z0 = c->own_lo; z1 = c->own_hi; }
-    if (z0 < 0 || z1 > c->nzl || z0 >= z1) return nl_fail(err, errlen, NL_EINVAL, "bad plane range [%lld,%lld)", (i64)z0, (i64)z1);
-    if (z0 > c->own_lo || z1 < c->own_hi) return nl_fail(err, errlen, NL_EINVAL, "the plane range must cover the owned planes");
-    NL_JOIN_SIDE(c);
-    if (!c->spec_ok) return nl_fail(err, errlen, NL_ESTATE, "one-pass vesselness is not available for this context (queue too large)");
-    if (!dev_lohi && !(fsq_lo <= fsq_hi)) return nl_fail(err, errlen, NL_EINVAL, "empty bracket [%g,%g]", (double)fsq_lo, (double)fsq_hi);
-    { int rcs = set_spacing(c, spacing, err, errlen); if (rcs) return rcs; }
-    VessP vp{};
-    vp.cnt_lo = (int)c->own_lo; vp.cnt_hi = (int)c->own_hi;
-    vp.have_prev = c->mask_slots_used > 0;
-    vp.fsq_lo = fsq_lo; vp.fsq_hi = fsq_hi; vp.qcap = HM_SPEC_CAP;
-    {
-        ProfScope ps(c, "vesselness");
-        const int ntx = (int)((c->nx + HM_TX - 1) / HM_TX);
-        const int wpr = (int)((c->nx + 63) / 64);
-        const i64 slot_words = c->nzl * c->ny * wpr;
-        const int k_scale = c->mask_slots_used;          // committed by nl_vesselness_resolve
-        unsigned long long *cm = (unsigned long long *)c->m[0] + (i64)(k_scale & 1) * slot_words;
-        const unsigned long long *pm = (unsigned long long *)c->m[0] + (i64)((k_scale + 1) & 1) * slot_words;
-        const VQueue vq{(float4 *)c->d_vq, c->d_vq_count};
-        const int rs = hv_rs(c);
-        if (dev_lohi && !rs) return nl_fail(err, errlen, NL_ESTATE, "the device-resident chain needs the two-voxel walk");
-        const int ty = rs ? 2 * rs : hm_ty();
-        const int nty = (int)((c->ny + ty - 1) / ty);
-        // Planes per workgroup: 64, or 128 where that still leaves thousands of workgroups (a chunk's prologue -- four planes
-        // staged, the first gradient tile -- is paid half as often: walk -3 % at 1024^3; a 128-plane frame would run on 256
-        // workgroups and lose 30 %).  The queue was sized for 64-plane chunks: twice the planes, twice the entries per region,
-        // half the regions -- the same memory when the chunk count halves exactly or rounds the same way.
-        int zch = HM_ZCHUNK;
-        {
-            static int forced = -1;
-            if (forced < 0) { const char *e = getenv("NELLIE_HV_ZCHUNK"); forced = e ? atoi(e) : 0; }
-            const i64 nz = z1 - z0;
-            const i64 c64 = (nz + HM_ZCHUNK - 1) / HM_ZCHUNK, c128 = (nz + 2 * HM_ZCHUNK - 1) / (2 * HM_ZCHUNK);
-            const bool fits = 2 * c128 <= c64 && (i64)(2 * HM_ZCHUNK + 4) * c->ny * c->nx * 4 < ((i64)1 << 32);
-            if (rs && fits && (forced == 2 * HM_ZCHUNK || (forced == 0 && (i64)ntx * nty * c128 >= 4096))) zch = 2 * HM_ZCHUNK;
-        }
-        vp.zchunk = zch;
-        const int nzc = (int)((z1 - z0 + zch - 1) / zch);
-        const unsigned nblocks = (unsigned)(ntx * nty * nzc);
-        vp.qcap = HM_SPEC_CAP * (zch / HM_ZCHUNK);
-        if (rs) vp.qcap *= 2 * hv_np(c);                 // a wave owns two (four) row segments
-        hipStream_t hs = c->stream;
-        if (rs && hv_dpp(c)) {
-            // wave-autonomous walk: one region per strip and chunk; the queue's bytes are shared out evenly (0.47 entries per voxel of a strip
-            // where the pair kernel has 0.5: its strips overhang the volume by up to 59 columns)
-            const int ntxd = (int)((c->nx + HD_COLS - 1) / HD_COLS), ntyd = (int)((c->ny + HD_SR - 1) / HD_SR);
-            const int zd = hd_zchunk(c, z1 - z0, (i64)ntxd * ntyd);
-            const i64 nzd = (z1 - z0 + zd - 1) / zd;
-            const i64 nreg = (i64)ntxd * ntyd * nzd;
-            i64 cap = vq_alloc_entries(c->nzl, c->ny, c->nx) / nreg;
-            if (cap > (i64)HD_SR * 64 * zd) cap = (i64)HD_SR * 64 * zd;
-            if (cap > (1 << 24) - 1) cap = (1 << 24) - 1;
-            if (cap >= 64 && 2 * nreg <= vq_alloc_regions(c->nzl, c->ny, c->nx)) {     // (region counts + the strips' h_mask counts)
-                vp.zchunk = zd; vp.qcap = (int)cap;
-                // the strips OR their bits into the words (two strips share a word): the slot's planes start from zero
-                NL_HIP(hipMemsetAsync(cm + z0 * c->ny * wpr, 0, (size_t)(z1 - z0) * c->ny * wpr * 8, hs));
-                NL_HIP(nl_hv_launch(HvLaunch{2, HD_SR, 0, hv_fastv(c), (unsigned)nreg, hs, gauss_cur(c), cm, pm, wpr, geom(c), hessp(c), vp, vq, (int)z0, (int)z1,
-                                             ntxd, ntyd, res, d_cnt, dev_lohi}));
-                NL_CHECK_LAUNCH();
-                c->spec_nregions = (unsigned)nreg;
-                c->spec_qcap = vp.qcap;
-                goto launched;
-            }
-        }
-#define NL_DEV_LOHI dev_lohi
-#define NL_LAUNCH_SPEC(TYV, FASTV, HR)                                                                                    \
-        hessian_g_kernel<2, TYV, FASTV><<<nblocks, HGCfg<TYV>::NT, HGCfg<TYV>::lds_bytes(), c->stream>>>(                 \
-            gauss_cur(c), cm, pm, wpr, geom(c), HR, vp, vq, (int)z0, (int)z1, ntx, nty, res, d_cnt)
-        if (rs) NL_HIP(nl_hv_launch(HvLaunch{2, rs, hv_np(c), hv_fastv(c), nblocks, hs, gauss_cur(c), cm, pm, wpr, geom(c), hessp(c), vp, vq, (int)z0, (int)z1,
-                                             ntx, nty, res, d_cnt, NL_DEV_LOHI}));
-        else if (ty == 8) { if (c->fast_div) NL_LAUNCH_SPEC(8, true, hessdv_fast(c)); else NL_LAUNCH_SPEC(8, false, hessdv_exact(c)); }
-        else { if (c->fast_div) NL_LAUNCH_SPEC(16, true, hessdv_fast(c)); else NL_LAUNCH_SPEC(16, false, hessdv_exact(c)); }
-#undef NL_LAUNCH_SPEC
-#undef NL_DEV_LOHI
-        NL_CHECK_LAUNCH();
-        c->spec_nregions = nblocks * (unsigned)(rs ? rs / hv_np(c) : ty);
-        c->spec_qcap = vp.qcap;
-launched: ;
-    }
-    // fused: max |H|, max frob_sq (bit patterns of non-negative floats), the inf and overflow flags -- all "max"; the count stays local
-    if (fused(c)) { int rcr = reduce_u32_max(c, res, 4, err, errlen); if (rcr) return rcr; }
-    c->spec_z0 = z0; c->spec_z1 = z1;
-    return NL_OK;
-}
-
-// ---- one-pass vesselness (MODE 2 of the Hessian kernel + the resolve kernel), see hessian.inc ---------------
-extern "C" int nl_vesselness_spec(nl_ctx *c, const double spacing[3], float fsq_lo, float fsq_hi, int64_t z0, int64_t z1,
-                                  float *max_abs, float *max_frob_sq, int *any_inf, int *overflow, char *err, size_t errlen) {
-    NL_ENTER(c);
-    unsigned long long *d_cnt = (unsigned long long *)c->d_small;
-    unsigned int *res = (unsigned int *)c->d_small + 16;
-    NL_HIP(zero_small(c->d_small, 128, c->stream));
-    { int rc = spec_enqueue(c, spacing, fsq_lo, fsq_hi, z0, z1, res, d_cnt, nullptr, err, errlen); if (rc) return rc; }
-    unsigned int *h = (unsigned int *)c->h_small;
-    NL_HIP(hipMemcpyAsync(h, c->d_small, 128, hipMemcpyDeviceToHost, c->stream));      // [0] count, [16..19] statistics
-    NL_HIP(hipStreamSynchronize(c->stream));
-    c->spec_count = *(unsigned long long *)c->h_small;       // d_small is scratch for the sampling calls in between
-    h += 16;
-    if (max_abs) memcpy(max_abs, &h[0], 4);
-    if (max_frob_sq) memcpy(max_frob_sq, &h[1], 4);
-    if (any_inf) *any_inf = (int)h[2];
-    if (overflow) *overflow = (int)h[3];
-    c->spec_lo = fsq_lo; c->spec_hi = fsq_hi;
-    c->spec_valid = (h[2] == 0 && h[3] == 0) ? 1 : 0;
-    c->last_spec_overflow = (int)h[3];
-    return NL_OK;
-}
-
-static bool resolve_on_side();
-// *hit = 1: the exact threshold lies in the bracket of the pass, the scale is complete (mask_count as
-// nl_vesselness_step reports it); *hit = 0: nothing was changed, run nl_vesselness_step.
-// h_mask count of the scale completed by the last nl_vesselness_resolve hit (waits for its kernel).
-extern "C" int nl_vesselness_count(nl_ctx *c, int64_t *mask_count, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!mask_count) return nl_fail(err, errlen, NL_EINVAL, "mask_count is NULL");
-    unsigned long long *d_cnt = (unsigned long long *)((char *)c->d_small + (48 << 10));
-    unsigned long long *h_cnt = (unsigned long long *)((char *)c->h_small + (48 << 10));
-    hipStream_t st = resolve_on_side() ? c->side : c->stream;        // the stream the resolve kernel ran on
-    NL_HIP(hipMemcpyAsync(h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, st));
-    NL_HIP(hipStreamSynchronize(st));
-    *mask_count = (int64_t)(*h_cnt + c->spec_count);
-    return NL_OK;
-}
-
-// The resolve kernel of a scale, enqueued on the side stream (ordered after everything submitted to the main stream so far);
-// commits the scale's mask slot.  dev_params != NULL: gamma_sq, fsq_min and m_inf are read from device memory (chain.inc).
-// The resolve kernel runs on the MAIN stream by default (round 4): since the two-voxel walk and the cheaper resolve kernel,
-// running it beside the next scale's Gaussian buys nothing (48.8 vs 49.0 ms/step at 1024^3: the Z pass slows from 1.77 to 2.55 ms
-// per launch while it shares the GPU) -- and sending it to the side stream only to make the main stream wait for it cost two
-// cross-queue dependencies of ~13 us per scale (0.13 ms of a 3.3 ms config-5 frame).  NELLIE_RESOLVE_OVERLAP=1: the side stream,
-// beside the next cascade step (every entry point that needs its result joins it: NL_JOIN_SIDE).
-static bool resolve_on_side() {
-    static int overlap = -1;
-    if (overlap < 0) { const char *e = getenv("NELLIE_RESOLVE_OVERLAP"); overlap = (e && atoi(e)) ? 1 : 0; }
-    return overlap != 0;
-}
-static int resolve_enqueue(nl_ctx *c, VessP vp, unsigned long long *d_cnt, const float *dev_params, char *err, size_t errlen, bool force_side = false) {
-    const i64 plane = c->ny * c->nx, z0 = c->spec_z0, z1 = c->spec_z1;
-    const bool side = force_side || resolve_on_side();
-    hipStream_t st = side ? c->side : c->stream;
-    if (side) {
-        NL_HIP(hipEventRecord(c->ev_main, c->stream));
-        NL_HIP(hipStreamWaitEvent(c->side, c->ev_main, 0));
-    }
-    vp.qcap = c->spec_qcap;
-    vp.idx_lo = (c->own_lo - z0) * plane; vp.idx_hi = (c->own_hi - z0) * plane;
-    {
-        ProfScope ps(c, "vesselness_resolve", st);
-        const int wpr = (int)((c->nx + 63) / 64);
-        const i64 slot_words = c->nzl * c->ny * wpr;
-        const int k_scale = c->mask_slots_used++;
-        vp.have_prev = k_scale > 0;
-        unsigned long long *cm = (unsigned long long *)c->m[0] + (i64)(k_scale & 1) * slot_words;
-        const unsigned long long *pm = (unsigned long long *)c->m[0] + (i64)((k_scale + 1) & 1) * slot_words;
-        if (vp.first && !vmax_is_zero(c, z0, z1))
-            NL_HIP(hipMemsetAsync(c->f[c->i_vmax] + z0 * plane, 0, (size_t)(z1 - z0) * plane * 4, st));
-        c->vmax_zero_hi = 0;
-        vesselness_queue_kernel<true><<<resolve_grid((c->spec_nregions + 3) / 4), 256, 0, st>>>(
-            (const float4 *)c->d_vq, c->d_vq_count, c->spec_nregions, c->f[c->i_vmax], z0 * plane, vp, cm, pm, wpr, (int)c->ny, (int)c->nx, z0, d_cnt,
-            dev_params);
-        NL_CHECK_LAUNCH();
-    }
-    if (side) {
-        NL_HIP(hipEventRecord(c->ev_side, c->side));
-        c->side_pending = 1;
-    }
-    c->spec_valid = 0;
-    return NL_OK;
-}
-
-// Device chain (round 5, second session): the resolve kernel of scale s needs nothing the cascade step of scale s+1 touches, and the ten
-// threshold kernels of scale s+1 (one wave or a 10^6-point lattice each: ~0.15 ms of a nearly idle GPU) need nothing the resolve kernel
-// writes.  So nl_chain_scale(s) only NOTES the resolve launch; nl_chain_scale(s+1) -- called after the host has enqueued cascade step
-// s+1 -- starts it on the side stream behind that step, and the threshold kernels run beside it on the main stream; the walk of scale
-// s+1 joins (spec_enqueue: NL_JOIN_SIDE).  Beside the cascade step itself the resolve kernel only costs (both are bound by the float64
-// pipe: NELLIE_RESOLVE_OVERLAP, profiles/r05_walk_variants_1024cube.txt).  Single context, volumes of 2^26 voxels and more (below, the
-// side stream carries the cascade step that runs ahead); NELLIE_RESOLVE_DEFER=0: off.
-static bool resolve_defer_ok(const nl_ctx *c) {
-    const char *e = getenv("NELLIE_RESOLVE_DEFER");               // read per call: tests switch it (2: whatever the size, for the small volumes of the suite)
-    const int on = e ? atoi(e) : 1;
-    if (on == 2) return !c->comm && !resolve_on_side();
-    return on && !c->comm && !c->ahead_pending && !resolve_on_side() && c->n >= ((i64)1 << 26);
-}
-static int resolve_deferred_launch(nl_ctx *c, bool on_side, char *err, size_t errlen) {
-    if (!c->def_resolve) return NL_OK;
-    c->def_resolve = 0;
-    NL_JOIN_SIDE(c);          // the exact round of that scale ran on the side stream: whatever the main stream does next comes after it
-    VessP vp;
-    static_assert(sizeof(VessP) <= sizeof(((nl_ctx *)nullptr)->def_vp), "nl_ctx::def_vp holds a VessP");
-    memcpy(&vp, c->def_vp, sizeof(VessP));
-    return resolve_enqueue(c, vp, c->def_cnt, c->def_params, err, errlen, on_side);
-}
-
-extern "C" int nl_vesselness_resolve(nl_ctx *c, float gamma_sq, float alpha_sq, float beta_sq, int use_thr, float thr,
-                                     int *hit, int64_t *mask_count, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!hit) return nl_fail(err, errlen, NL_EINVAL, "hit is NULL");
-    *hit = 0;
-    if (!c->spec_valid) return NL_OK;
-    VessP vp = make_vessp(c, gamma_sq, alpha_sq, beta_sq, use_thr, thr);
-    if (!(vp.fsq_min >= c->spec_lo && vp.fsq_min <= c->spec_hi)) { c->spec_valid = 0; return NL_OK; }
-    // The kernel's counter lives outside the sampling scratch.
-    unsigned long long *d_cnt = (unsigned long long *)((char *)c->d_small + (48 << 10));
-    if (resolve_on_side()) {
-        NL_HIP(hipEventRecord(c->ev_main, c->stream));
-        NL_HIP(hipStreamWaitEvent(c->side, c->ev_main, 0));
-        NL_HIP(zero_small(d_cnt, 8, c->side));
-    } else {
-        NL_HIP(zero_small(d_cnt, 8, c->stream));
-    }
-    { int rc = resolve_enqueue(c, vp, d_cnt, nullptr, err, errlen); if (rc) return rc; }
-    *hit = 1;
-    if (mask_count) {        // asking for the count here waits for the kernel; nl_vesselness_count can be called later instead
-        int rcc = nl_vesselness_count(c, mask_count, err, errlen);
-        if (rcc) return rcc;
-    }
-    return NL_OK;
-}
-
 
 // ---- device-resident threshold chain (chain.inc) -----------------------------------------------------------------------------
 static inline unsigned int f2u(float x) { unsigned int u; memcpy(&u, &x, 4); return u; }
@@ -1025,7 +559,7 @@ static int chain_verify(const ChainScale &s, double division, double margin, dou
 extern "C" int nl_chain_begin(nl_ctx *c, int n_scales, char *err, size_t errlen) {
     NL_ENTER(c);
     if (n_scales < 1 || n_scales > NL_CHAIN_MAX_SCALES) return nl_fail(err, errlen, NL_EINVAL, "a chain holds 1..%d scales", NL_CHAIN_MAX_SCALES);
-    if (!c->two_d && (!c->spec_ok || !hv_rs(c))) return nl_fail(err, errlen, NL_ESTATE, "the device-resident chain needs the 3-D one-pass walk");
+    if (!c->two_d && (!c->spec_ok || walk_plan(c, 2, c->own_lo, c->own_hi).family == WALK_ONE_VOXEL)) return nl_fail(err, errlen, NL_ESTATE, "the device-resident chain needs the 3-D one-pass walk");
     if (!c->d_chain) {
         NL_HIP(hipMalloc(&c->d_chain, sizeof(ChainScale) * NL_CHAIN_MAX_SCALES));
         NL_HIP(hipHostMalloc(&c->h_chain, sizeof(ChainScale) * NL_CHAIN_MAX_SCALES, hipHostMallocDefault));
@@ -1070,10 +604,7 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
         // from the record as the resolve kernel does.  ~20 host round trips of a 2048^2 frame gone.
         if ((rc = sample_first_round(c, NL_FIELD_GAUSS, NL_FIELD_FROB, sz, sy, sx, NL_CHAIN_BINS, (char *)&cs->h_gauss, (char *)&cs->h_raw, nullptr, nullptr, true, err, errlen))) return rc;
         chain_thr1_kernel<<<2, 64, 0, c->stream>>>(cs, division, margin, test_scale, 0.0);
-        {
-            ProfScope ps(c, "hessian_stats");
-            hessian2d_stats_kernel<<<grid2d_rows(c->nx, c->ny), 256, 0, c->stream>>>(gauss_cur(c), geom(c), hessp(c), cs->stats);
-        }
+        if ((rc = hessian2d_stats_enqueue(c, cs->stats, err, errlen))) return rc;
         chain_post_kernel<<<1, 64, 0, c->stream>>>(cs);
         NL_CHECK_LAUNCH();
         // the exact round (an image lives on one context: no reduction)
@@ -1085,20 +616,8 @@ extern "C" int nl_chain_scale(nl_ctx *c, const double spacing[3], int64_t sz, in
         vp.cnt_lo = (int)c->own_lo; vp.cnt_hi = (int)c->own_hi;
         vp.first = c->mask_slots_used == 0 ? 1 : 0;
         vp.nan_flag = (unsigned int *)((char *)c->d_small + NL_NAN_FLAG_OFF);
-        ProfScope ps(c, "vesselness");
-        const int wpr = (int)((c->nx + 63) / 64);
-        const i64 slot_words = c->nzl * c->ny * wpr;
-        const int k_scale = c->mask_slots_used++;
-        vp.have_prev = k_scale > 0;
-        unsigned long long *cm = (unsigned long long *)c->m[0] + (i64)(k_scale & 1) * slot_words;
-        const unsigned long long *pm = (unsigned long long *)c->m[0] + (i64)((k_scale + 1) & 1) * slot_words;
-        if (vp.first && !vmax_is_zero(c, 0, c->nzl)) NL_HIP(hipMemsetAsync(c->f[c->i_vmax], 0, (size_t)c->n * 4, c->stream));
-        c->vmax_zero_hi = 0;
         c->spec_valid = 0;
-        vesselness2d_kernel<<<grid2d_rows((i64)wpr * 64, c->ny), 256, 0, c->stream>>>(gauss_cur(c), c->f[c->i_vmax], cm, pm, wpr, geom(c), hessp(c), vp,
-                                                                                        &cs->cnt_resolve, (const float *)cs);
-        NL_CHECK_LAUNCH();
-        return NL_OK;
+        return vesselness2d_enqueue(c, vp, &cs->cnt_resolve, (const float *)cs, err, errlen);
     }
     if ((rc = chain_first_round(c, cs, sz, sy, sx, division, margin, test_scale, err, errlen))) return rc;
     return chain_walk_resolve(c, cs, spacing, sz, sy, sx, alpha_sq, beta_sq, division, z0, z1, err, errlen);
@@ -1285,80 +804,27 @@ extern "C" int nl_chain_log(nl_ctx *c, int k, int which, int64_t *counts, float 
     return NL_OK;
 }
 
-extern "C" int nl_vesselness_step(nl_ctx *c, float gamma_sq, float alpha_sq, float beta_sq, int use_thr, float thr,
-                                  int64_t z0, int64_t z1, int64_t *mask_count, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (z0 < 0 && z1 < 0) { z0 = c->own_lo; z1 = c->own_hi; }
-    if (z0 < 0 || z1 > c->nzl || z0 >= z1) return nl_fail(err, errlen, NL_EINVAL, "bad plane range [%lld,%lld)", (i64)z0, (i64)z1);
-    if (!c->have_spacing) return nl_fail(err, errlen, NL_ESTATE, "nl_vesselness_step before nl_hessian_stats");
-    NL_JOIN_SIDE(c);
-    unsigned long long *d_cnt = (unsigned long long *)c->d_small;
-    NL_HIP(zero_small(d_cnt, 8, c->stream));
-    VessP vp = make_vessp(c, gamma_sq, alpha_sq, beta_sq, use_thr, thr);
-    vp.qcap = HM_REGION;
-    c->spec_valid = 0;
-    if (c->two_d) {
-        ProfScope ps(c, "vesselness");
-        const int wpr = (int)((c->nx + 63) / 64);
-        const i64 slot_words = c->nzl * c->ny * wpr;
-        const int k_scale = c->mask_slots_used++;
-        vp.have_prev = k_scale > 0;
-        unsigned long long *cm = (unsigned long long *)c->m[0] + (i64)(k_scale & 1) * slot_words;
-        const unsigned long long *pm = (unsigned long long *)c->m[0] + (i64)((k_scale + 1) & 1) * slot_words;
-        if (vp.first && !vmax_is_zero(c, 0, c->nzl)) NL_HIP(hipMemsetAsync(c->f[c->i_vmax], 0, (size_t)c->n * 4, c->stream));
-        c->vmax_zero_hi = 0;
-        vesselness2d_kernel<<<grid2d_rows((i64)wpr * 64, c->ny), 256, 0, c->stream>>>(gauss_cur(c), c->f[c->i_vmax], cm, pm, wpr, geom(c), hessp(c), vp, d_cnt);
-        NL_CHECK_LAUNCH();
-    } else {
-        ProfScope ps(c, "vesselness");
-        const int ntx = (int)((c->nx + HM_TX - 1) / HM_TX);
-        const int wpr = (int)((c->nx + 63) / 64);
-        const i64 slot_words = c->nzl * c->ny * wpr;
-        // cumulative h_mask (AND over the scales so far): scale k reads slot (k-1)&1 and writes slot k&1
-        const int k_scale = c->mask_slots_used++;
-        vp.have_prev = k_scale > 0;
-        unsigned long long *cm = (unsigned long long *)c->m[0] + (i64)(k_scale & 1) * slot_words;
-        const unsigned long long *pm = (unsigned long long *)c->m[0] + (i64)((k_scale + 1) & 1) * slot_words;
-        // one launch covers as many Z chunks as the queue has regions for
-        const i64 plane = c->ny * c->nx;
-        const i64 planes_per_launch = (i64)c->vq_chunks * HM_ZCHUNK;
-        const VQueue vq{(float4 *)c->d_vq, c->d_vq_count};
-        if (vp.first && !vmax_is_zero(c, z0, z1))      // vesselness = zeros (filtering.py:807); only voxels alive in every mask are ever read again
-            NL_HIP(hipMemsetAsync(c->f[c->i_vmax] + z0 * plane, 0, (size_t)(z1 - z0) * plane * 4, c->stream));
-        c->vmax_zero_hi = 0;
-        const int rs = hv_rs(c);
-        const int ty = rs ? 2 * rs : hm_ty();
-        const int nty = (int)((c->ny + ty - 1) / ty);
-        if (rs) vp.qcap = 2 * hv_np(c) * HM_REGION;
-#define NL_LAUNCH_VESS(TYV, FASTV, HR)                                                                                    \
-        hessian_g_kernel<1, TYV, FASTV><<<nblocks, HGCfg<TYV>::NT, HGCfg<TYV>::lds_bytes(), c->stream>>>(                 \
-            gauss_cur(c), cm, pm, wpr, geom(c), HR, vp, vq, (int)za, (int)zb, ntx, nty, nullptr, d_cnt)
-        for (i64 za = z0; za < z1; za += planes_per_launch) {
-            const i64 zb = za + planes_per_launch < z1 ? za + planes_per_launch : z1;
-            const int nzc = (int)((zb - za + HM_ZCHUNK - 1) / HM_ZCHUNK);
-            const unsigned nblocks = (unsigned)(ntx * nty * nzc);
-            if (rs) NL_HIP(nl_hv_launch(HvLaunch{1, rs, hv_np(c), hv_fastv(c), nblocks, c->stream, gauss_cur(c), cm, pm, wpr, geom(c), hessp(c), vp, vq, (int)za, (int)zb,
-                                                 ntx, nty, nullptr, d_cnt, nullptr}));
-            else if (ty == 8) { if (c->fast_div) NL_LAUNCH_VESS(8, true, hessdv_fast(c)); else NL_LAUNCH_VESS(8, false, hessdv_exact(c)); }
-            else { if (c->fast_div) NL_LAUNCH_VESS(16, true, hessdv_fast(c)); else NL_LAUNCH_VESS(16, false, hessdv_exact(c)); }
-            NL_CHECK_LAUNCH();
-            const unsigned nregions = nblocks * (unsigned)(rs ? rs / hv_np(c) : ty);
-            vesselness_queue_kernel<false><<<resolve_grid((nregions + 3) / 4), 256, 0, c->stream>>>(vq.ent, vq.count, nregions, c->f[c->i_vmax], za * plane, vp,
-                                                                                      nullptr, nullptr, wpr, (int)c->ny, (int)c->nx, za, nullptr, nullptr);
-            NL_CHECK_LAUNCH();
-        }
-#undef NL_LAUNCH_VESS
-        NL_CHECK_LAUNCH();
-    }
-    if (mask_count) {
-        NL_HIP(hipMemcpyAsync(c->h_small, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
-        NL_HIP(hipStreamSynchronize(c->stream));
-        *mask_count = (int64_t)(*(unsigned long long *)c->h_small);
-    }
+// ---- 2-D images (im_info.no_z) -----------------------------------------------------------------------------
+int hessian2d_stats_enqueue(nl_ctx *c, unsigned int *res, char *err, size_t errlen) {
+    ProfScope ps(c, "hessian_stats");
+    hessian2d_stats_kernel<<<grid2d_rows(c->nx, c->ny), 256, 0, c->stream>>>(gauss_cur(c), geom(c), hessp(c), res);
+    NL_CHECK_LAUNCH();
+    return NL_OK;
+}
+int vesselness2d_enqueue(nl_ctx *c, const VessP &vp0, unsigned long long *d_cnt, const float *dev_params, char *err, size_t errlen) {
+    VessP vp = vp0;
+    ProfScope ps(c, "vesselness");
+    const int k_scale = c->mask_slots_used++;
+    vp.have_prev = k_scale > 0;
+    const MaskSlots ms = mask_slots(c, k_scale);
+    if (vp.first && !vmax_is_zero(c, 0, c->nzl)) NL_HIP(hipMemsetAsync(c->f[c->i_vmax], 0, (size_t)c->n * 4, c->stream));
+    c->vmax_zero_hi = 0;
+    vesselness2d_kernel<<<grid2d_rows((i64)ms.wpr * 64, c->ny), 256, 0, c->stream>>>(gauss_cur(c), c->f[c->i_vmax], ms.cm, ms.pm, ms.wpr, geom(c), hessp(c), vp, d_cnt,
+                                                                                      dev_params);
+    NL_CHECK_LAUNCH();
     return NL_OK;
 }
 
-// ---- 2-D images (im_info.no_z) -----------------------------------------------------------------------------
 extern "C" int nl_set_ndim(nl_ctx *c, int ndim, char *err, size_t errlen) {
     NL_ENTER(c);
     if (ndim != 2 && ndim != 3) return nl_fail(err, errlen, NL_EINVAL, "ndim must be 2 or 3");
@@ -1764,10 +1230,10 @@ extern "C" int nl_planes_put(nl_ctx *c, int field, int64_t z0, int64_t z1, const
 extern "C" int nl_ctx_info(nl_ctx *c, const char *key, double *value) {
     if (!c || !key || !value) return NL_EINVAL;
     if (!strcmp(key, "fast_div")) *value = c->fast_div2 ? 2 : c->fast_div;      // 2: two-instruction division proven, 1: three, 0: float64
-    else if (!strcmp(key, "hessian_tile_rows")) *value = hv_rs(c) ? 2 * hv_rs(c) : hm_ty();
+    else if (!strcmp(key, "hessian_tile_rows")) *value = walk_plan(c, 0, c->own_lo, c->own_hi).ty;
     else if (!strcmp(key, "hv_variants")) *value = NL_HV_VARIANTS;               // 1: a build with the rejected forms of the walk (nellie_hv.hip)
     else if (!strcmp(key, "vesselness_one_pass")) *value = c->spec_ok;
-    else if (!strcmp(key, "chain_available")) *value = (c->two_d || (c->spec_ok && hv_rs(c))) ? 1 : 0;   // nl_chain_begin's own precondition
+    else if (!strcmp(key, "chain_available")) *value = (c->two_d || (c->spec_ok && walk_plan(c, 2, c->own_lo, c->own_hi).family != WALK_ONE_VOXEL)) ? 1 : 0;   // nl_chain_begin's own precondition
     else if (!strcmp(key, "last_fsq_min")) *value = c->last_fsq_min;
     else if (!strcmp(key, "last_spec_overflow")) *value = c->last_spec_overflow;
     else if (!strcmp(key, "last_label_sparse")) *value = c->last_label_sparse;
@@ -1798,19 +1264,6 @@ extern "C" int nl_ctx_info(nl_ctx *c, const char *key, double *value) {
         *value = flag ? 1.0 : 0.0;
     }
     else return NL_EINVAL;
-    return NL_OK;
-}
-
-extern "C" int nl_debug_eig_frangi(nl_ctx *c, const float *h6, int64_t n, int impl, float alpha_sq, float beta_sq,
-                                   float gamma_sq, float *out4, char *err, size_t errlen) {
-    NL_ENTER(c);
-    if (!h6 || !out4 || n < 1 || n * 6 > c->n) return nl_fail(err, errlen, NL_EINVAL, "bad debug batch (n=%lld)", (i64)n);
-    float *d_in = c->f[(c->i_gauss + 1) % 3], *d_out = c->f[(c->i_gauss + 2) % 3];
-    NL_HIP(hipMemcpyAsync(d_in, h6, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    debug_eig_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d_in, n, impl, alpha_sq, beta_sq, gamma_sq, d_out);
-    NL_CHECK_LAUNCH();
-    NL_HIP(hipMemcpyAsync(out4, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    NL_HIP(hipStreamSynchronize(c->stream));
     return NL_OK;
 }
 

@@ -1,12 +1,11 @@
-// Second translation unit of libnellie_hip.so (gfx950): the pair walk, compiled with the ILP-first scheduler (see hv_launch.h and
-// nellie_amd/build.py).  Only the kernel and its launch live here.
+// Part of libnellie_hip.so (gfx950): the pair walk and the wave-autonomous walk, compiled with the ILP-first scheduler (see hv_launch.h and
+// nellie_amd/build.py).  Only the kernels and their launch live here; nellie_walk.hip plans the launch (walk_plan.h).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <type_traits>
-#define NL_HV_UNIT 1
 #include "nl_common.h"
 #include "device_math.inc"
-#include "hessian.inc"
+#include "walk_common.h"
 #include "hessian_pair.inc"
 #include "hessian_dpp.inc"
 #include "hv_launch.h"

@@ -98,7 +98,6 @@ struct nl_ctx {
     int fsq_cache_valid = 0;
     float *gauss_ext = nullptr;   // current Gaussian volume when it is NOT one of f[0..2]: the resident float32 input itself,
                                   // until the first cascade step has written a volume of its own (saves the 8 B/voxel copy)
-    int vq_chunks = 1;         // Z chunks (HM_ZCHUNK planes) one vesselness launch may cover
     int spec_ok = 0;           // the queue can hold a one-pass (MODE 2) vesselness of the whole slab
     int spec_valid = 0;        // a MODE 2 pass is waiting for nl_vesselness_resolve
     float spec_lo = 0, spec_hi = 0;
@@ -114,7 +113,7 @@ struct nl_ctx {
     // device chain, round 5: the resolve kernel of scale s is held back until the cascade step of scale s+1 has been enqueued and then runs
     // on `side` beside that scale's threshold kernels (nl_chain_scale); def_* = what resolve_enqueue needs then
     int def_resolve = 0;
-    alignas(8) unsigned char def_vp[160] = {};       // a VessP (hessian.inc), copied in and out
+    alignas(8) unsigned char def_vp[160] = {};       // a VessP (walk_common.h), copied in and out
     unsigned long long *def_cnt = nullptr;
     const float *def_params = nullptr;
     int last_spec_overflow = 0;          // the last one-pass walk overflowed a queue region (diagnostics)
@@ -139,7 +138,7 @@ struct nl_ctx {
     float hz2 = 2, hy2 = 2, hx2 = 2;         // float32(2.0*h)
     int have_spacing = 0;
     int fast_div = 0;                        // 3-instruction division proven exact for the spacings in use
-    int fast_div2 = 0;                       // 2-instruction division (hessian.inc: Dv<2>) proven exact for them (pair kernel)
+    int fast_div2 = 0;                       // 2-instruction division (walk_common.h: Dv<2>) proven exact for them (pair kernel)
     double chk_spacing[3] = {0, 0, 0};
     float frob_max_abs = 1.0f, frob_max_finite = 0.0f;
     int frangi_ready = 0;

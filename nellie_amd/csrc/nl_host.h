@@ -1,13 +1,15 @@
 // Internal: what the translation units of libnellie_hip.so share on the host side -- the communicator dispatch, the entry-point macros,
 // a few launch helpers and the declarations of what one unit defines for the others (at the end of this file):
-//   nellie_hip.hip      Filter: context lifetime, cascade, Hessian walk, device chain, epilogue   -> upload_convert, store_planes, ...
+//   nellie_hip.hip      Filter: context lifetime, cascade, device chain, 2-D path, epilogue      -> upload_convert, store_planes, ...
+//   nellie_walk.hip     the Hessian walk: divisors, launch plan and launcher, resolve launch     -> set_spacing, spec_enqueue, resolve_*, walk_plan
 //   nellie_sample.hip   lattice / flat sampling, histogram records and thresholds               -> the sample_* rounds, fetch_counted, host_edges
 //   nellie_comm.hip     RCCL loader, loopback transport, communicator pool, collectives         -> rccl(), comm_release, reduce_*, ag_reserve, allgather_sizes
 //   nellie_label.hip    Label / Network / streaming                                             -> nl_launch_threshold_pack
 //   nellie_markers.hip  Markers                                                                 -> nl_launch_pack_labels
 //   nellie_hip_network.hip  Network behind the thinning (clean, seed, per-object relabel)        -> nw_release
 //   nellie_hip_thin.hip     the 3-D thinning (Lee94 as skimage runs it)                           -> thin_device
-//   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h; the eight stage handles share nl_stage.h.
+//   nellie_gauss.hip, nellie_gzyx.hip, nellie_hv.hip: kernels behind gauss_launch.h / hv_launch.h (nellie_hv.hip: the pair and the wave-autonomous
+//   walk, launched by nellie_walk.hip); the eight stage handles share nl_stage.h.
 // gfx950 only.
 #pragma once
 #include <stdarg.h>
@@ -79,6 +81,17 @@ static inline float *field_ptr(nl_ctx *c, int field) {      // the fields that a
     if (field == NL_FIELD_FRANGI) return c->f[c->i_vmax];
     return nullptr;
 }
+// The cumulative h_mask bit planes of Filter ping-pong in m[0]: scale k writes slot k & 1 (cm) and reads the other (pm); wpr words per row.
+// (k = c->mask_slots_used; the caller that commits the slot increments it.)
+struct MaskSlots { unsigned long long *cm; const unsigned long long *pm; int wpr; };
+static inline MaskSlots mask_slots(const nl_ctx *c, int k) {
+    const int wpr = (int)((c->nx + 63) / 64);
+    const i64 slot_words = c->nzl * c->ny * wpr;
+    return MaskSlots{(unsigned long long *)c->m[0] + (i64)(k & 1) * slot_words, (unsigned long long *)c->m[0] + (i64)((k + 1) & 1) * slot_words, wpr};
+}
+#define NL_NAN_FLAG_OFF (52 << 10)      // byte offset in d_small of the "NaN Hessian solved" word (VessP::nan_flag), zeroed per frame
+// the planes [z0, z1) of the vesselness volume are all zero already: the frame's first cascade step did it in passing (gauss_zyx.inc)
+static inline bool vmax_is_zero(const nl_ctx *c, i64 z0, i64 z1) { return c->vmax_zero_hi > 0 && c->vmax_zero_lo <= z0 && z1 <= c->vmax_zero_hi; }
 static inline HessP hessp(const nl_ctx *c) { return HessP{c->hz, c->hy, c->hx, c->hz2, c->hy2, c->hx2}; }
 static VolGeom geom(const nl_ctx *c) {
     VolGeom v{c->nzl, c->ny, c->nx, c->gz0, c->gnz};
@@ -157,8 +170,26 @@ static inline bool fused(const nl_ctx *c) { return c->comm && c->fuse_reduce; }
 // ---- defined in nellie_hip.hip ------------------------------------------------------------------------------------------
 int upload_convert(nl_ctx *c, const void *host, int dtype, float *dst, i64 count, char *err, size_t errlen);
 int store_planes(nl_ctx *c, const void *dev_base, void *host, size_t elem, int64_t z0, int64_t z1, char *err, size_t errlen);
-int64_t vq_alloc_entries(int64_t nzl, int64_t ny, int64_t nx);
 bool gyx_tiled();
+struct VessP;
+// The two Hessian kernels of an image (filter2d.inc), enqueued in their profiling groups: the statistics into res[0..2]; the vesselness
+// update, which commits the scale's mask slot (dev_params: as resolve_enqueue's)
+int hessian2d_stats_enqueue(nl_ctx *c, unsigned int *res, char *err, size_t errlen);
+int vesselness2d_enqueue(nl_ctx *c, const VessP &vp0, unsigned long long *d_cnt, const float *dev_params, char *err, size_t errlen);
+
+// ---- defined in nellie_walk.hip -----------------------------------------------------------------------------------------
+struct VqAlloc;
+struct WalkPlan;
+VqAlloc vq_alloc(int64_t nzl, int64_t ny, int64_t nx);                       // the eigen queue of a context (walk_plan.h), under the environment's switches
+int64_t vq_alloc_entries(int64_t nzl, int64_t ny, int64_t nx);               // its 32-byte entries (the other stages borrow the queue as scratch)
+WalkPlan walk_plan(const nl_ctx *c, int mode, int64_t z0, int64_t z1);       // the walk's launch plan for this context (walk_plan.h)
+int set_spacing(nl_ctx *c, const double spacing[3], char *err, size_t errlen);
+float mask_threshold_on_fsq(float max_abs, int use_thr, float thr);
+int spec_enqueue(nl_ctx *c, const double spacing[3], float fsq_lo, float fsq_hi, int64_t z0, int64_t z1, unsigned int *res, unsigned long long *d_cnt,
+                 const float *dev_lohi, char *err, size_t errlen);
+int resolve_enqueue(nl_ctx *c, VessP vp, unsigned long long *d_cnt, const float *dev_params, char *err, size_t errlen, bool force_side = false);
+bool resolve_defer_ok(const nl_ctx *c);
+int resolve_deferred_launch(nl_ctx *c, bool on_side, char *err, size_t errlen);
 
 // ---- defined in nellie_sample.hip ---------------------------------------------------------------------------------------
 // A histogram record, contiguous so that one transfer brings it back: counts (u64 x nbins) | edges (f32 x nbins + 1, padded to

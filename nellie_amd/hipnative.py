@@ -61,6 +61,7 @@ _PROTOS = {
     "nl_debug_percentile": [_p, _p, _i64, _f64, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)],
     "nl_positive_samples_world": [_p, _int, _int, _i64, _i64, _i64, _i64, _p, _i64, _p],
     "nl_host_slab_join": [_int, _p, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), _p, _p, _p, _p],
+    "nl_host_walk_plan": [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _p, _p],
     "nl_outputs_pack": [_p, _int, _p],
     "nl_outputs_pack_with_label": [_p, _int],
     "nl_outputs_fetch_packed_async": [_p, _p, _i64],
@@ -399,6 +400,24 @@ def host_slab_join(blobs):
     if k > cap:          # (the library reports this as an error: the arrays above are sized from the entry counts, which bound the nodes)
         raise NellieHipError(NL_EINVAL, f"nl_host_slab_join: {k} nodes for arrays of {cap}")
     return rank[:k], root[:k], val[:k], comp[:k], int(nc.value)
+
+
+WALK_PLAN_FIELDS = ("family", "tile_rows", "rs", "np", "division", "zchunk", "ntx", "nty", "nzc", "grid", "regions", "qcap", "launch_planes")
+WALK_SWITCH_DEFAULTS = {"NELLIE_HV_RS": 8, "NELLIE_HV_NP": 1, "NELLIE_HV_DPP": 0, "NELLIE_HM_TY": 8, "NELLIE_HV_ZCHUNK": 0, "NELLIE_VQ_CAP": 0,
+                        "NELLIE_SPEC_MAX_GB": 64}
+
+
+def host_walk_plan(mode, shape, own=None, planes=None, fast_div=1, fast_div2=1, **switches):
+    """The launch plan of the Hessian walk (nl_host_walk_plan; host code, no device) for a slab of `shape` with the owned planes `own` walked
+    over `planes` (both default to the whole slab) -> dict of WALK_PLAN_FIELDS.  switches: NELLIE_* = the value the variable would hold."""
+    nzl, ny, nx = (int(v) for v in shape)
+    own_lo, own_hi = own or (0, nzl)
+    z0, z1 = planes or (own_lo, own_hi)
+    assert set(switches) <= set(WALK_SWITCH_DEFAULTS), sorted(set(switches) - set(WALK_SWITCH_DEFAULTS))
+    sw = np.array([switches.get(k, d) for k, d in WALK_SWITCH_DEFAULTS.items()], np.int64)
+    plan = np.zeros(len(WALK_PLAN_FIELDS), np.int64)
+    load().call("nl_host_walk_plan", int(mode), nzl, ny, nx, int(own_lo), int(own_hi), int(z0), int(z1), int(fast_div), int(fast_div2), _ptr(sw), _ptr(plan))
+    return dict(zip(WALK_PLAN_FIELDS, (int(v) for v in plan)))
 
 
 def outputs_unpack(blob, nbytes, frangi, labels=None, zero_fill=True, threads=8):

@@ -1347,7 +1347,7 @@ print(json.dumps(out))
 
 
 def test_three_forms_of_the_constant_division_agree(hip):
-    """The walk divides by float32(h) / float32(2h) in one of three ways (csrc/hessian.inc: Dv<2> two instructions, Dv<1> three,
+    """The walk divides by float32(h) / float32(2h) in one of three ways (csrc/walk_common.h: Dv<2> two instructions, Dv<1> three,
     Dv<0> through float64), the short ones only after a proof by exhaustion for the divisors in use: same Frangi frame, same
     trace, on an isotropic and an anisotropic spacing (NELLIE_EXACT_DIV is read per context, a child process per setting)."""
     import json, subprocess, sys
@@ -1402,6 +1402,56 @@ pipe.close()
         got[rs] = json.loads(r.stdout.strip().splitlines()[-1])
     assert got["8"][:2] == [True, True] and got["0"][:2] == [False, False]
     assert got["8"][2:] == got["0"][2:] and got["8"][4] > 0
+
+
+def test_every_launch_branch_of_the_walk_gives_the_same_frame(hip):
+    """The walk's launch plan (csrc/walk_plan.h) has branches only switches reach on frames of test size: the forced 128-plane chunk, the
+    one-voxel kernel at both tile heights (what a plane too large for one buffer resource selects by itself), its known-threshold mode in
+    several launches, the wave-autonomous walk at a forced chunk.  70 x 37 x 130: two 64-plane chunks or three 32-plane ones, rows that are
+    no multiple of 4, 8 or 16, columns that overhang the 64-column tile and the 60-column strip.  Per setting (cached switches: a child
+    process each) the chain, the synchronous one-pass path and the two-pass path -- MODE 2, and MODE 0 + 1 -- must give the default's
+    per-scale trace, Frangi frame and labels bit for bit."""
+    import json, subprocess, sys
+    code = r'''
+import json, zlib
+from nellie_amd import pipeline as pl
+from nellie_amd.synthetic import ISO_01, make_volume
+vol = make_volume((70, 37, 130), 91)
+out = []
+for chain, one_pass in ((True, True), (False, True), (False, False)):
+    pipe = pl.FramePipeline(vol.shape)
+    pipe._device_chain = chain
+    pipe.one_pass = one_pass
+    pipe.filter(vol, pl.FilterParams(dim_res=ISO_01))
+    tr = [(s.gamma, s.max_abs, s.frob_thr, s.mask_count) for s in pipe.trace.scales]
+    fr = pipe.download_frangi()
+    pipe.label(pipe.frangi_threshold(), pl.min_area_pixels_of(ISO_01))
+    lab = pipe.download_labels()
+    out.append([tr, zlib.crc32(fr.tobytes()), int((fr > 0).sum()), zlib.crc32(lab.tobytes()), int(lab.max()), int(pipe.ctx.info("hessian_tile_rows"))])
+    pipe.close()
+print(json.dumps(out))
+'''
+    one_chunk = 192 * 64 * 64          # queue entries of one 64-plane chunk of this frame: its padded plane is 64 rows x 192 columns
+    settings = {"default": {},
+                "zchunk128": {"NELLIE_HV_ZCHUNK": "128"},
+                "one_voxel": {"NELLIE_HV_RS": "0"},
+                "one_voxel_ty16": {"NELLIE_HV_RS": "0", "NELLIE_HM_TY": "16"},
+                "one_voxel_launches": {"NELLIE_HV_RS": "0", "NELLIE_VQ_CAP": str(one_chunk)},
+                "dpp_zchunk64": {"NELLIE_HV_DPP": "1", "NELLIE_HV_ZCHUNK": "64"}}
+    switches = ("NELLIE_HV_RS", "NELLIE_HV_NP", "NELLIE_HV_DPP", "NELLIE_HM_TY", "NELLIE_HV_ZCHUNK", "NELLIE_VQ_CAP", "NELLIE_SPEC_MAX_GB")
+    got = {}
+    for name, sw in settings.items():
+        env = {k: v for k, v in os.environ.items() if k not in switches}
+        env.update(sw, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, f"{name}: {r.stderr[-2000:]}"
+        got[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    ref = got["default"]
+    assert all(way[2] > 0 and way[4] > 0 for way in ref), "the default run gave an empty frame"
+    assert [way[5] for way in ref] == [16] * 3 and [way[5] for way in got["one_voxel"]] == [8] * 3 and [way[5] for way in got["one_voxel_ty16"]] == [16] * 3
+    for name, ways in got.items():
+        for way, ref_way, how in zip(ways, ref, ("chain", "one pass", "two passes")):
+            assert way[:5] == ref_way[:5], f"{name}, {how}: differs from the default run"
 
 
 def test_device_percentile_equals_numpy(hip):
