@@ -887,6 +887,41 @@ int nl_adjacency_lookup(nl_adjacency *adjacency, const int64_t *child, int64_t n
 int nl_adjacency_fetch(nl_adjacency *adjacency, int64_t *out, char *err, size_t errlen);
 int nl_adjacency_kernel_ms(nl_adjacency *adjacency, float *ms, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ label transitions -------- */
+/* Label transition counts from voxel matches: for a frame pair, every match row (a voxel of frame t, a voxel
+   of frame t + 1) is turned into the pair of labels found there, and the distinct pairs are counted.  A transitions object is made
+   for one frame shape and has its own stream and buffers; two label frames stay on the device.
+   nl_trans_create  : ndim 2 or 3 (nz = 1 for 2) and the frame's shape.
+   nl_trans_frame   : the next label frame (NL_I32 or NL_I64, frame shape): the resident "next" frame becomes "prev", this one "next".
+   nl_trans_begin   : begins a pair with a cleared table of `slots` slots (a power of two).  Needs two frames.
+   nl_trans_count   : rows row0 .. row0 + n of the pair: prev, next (n, ndim) coordinates of NL_U16, NL_U32 or NL_U64.  Any number of
+                      calls, rows ascending; all count into the same table.  A coordinate outside the frame is NL_EINVAL naming the
+                      lowest such row (found by the kernel; the object stays usable).  *overflow: the table is too small.
+   nl_trans_finish  : ends the pair.  A gathered label below 0 or above 2^31 - 1 is NL_EINVAL naming the lowest such row.  *overflow:
+                      repeat the pair with more slots.  Else *n_entries distinct pairs, *n_dropped rows with a label of 0 at either
+                      end, *n_heads runs of equal neighbouring rows that touched the table (one atomic add each).
+   nl_trans_fetch   : out (n_entries, 2) uint64: (prev label << 32 | next label, count), in no particular order.
+   nl_trans_label_max : the largest label of the "next" frame.
+   nl_trans_relabel : the "next" frame through lut (n_lut int32): label b in (0, n_lut) becomes lut[b], everything else 0.
+   nl_trans_fetch_frame : that frame, int32.
+   nl_trans_kernel_ms   : ms[4], device time of the clear, the count launches and the compaction of the last pair, and of the last
+                          relabel.  Transfers excluded, except that the compaction's figure spans the scan's one-word round trip
+                          to the host between its kernels.
+   At most 2^31 rows per nl_trans_count, 2^34 slots, 2^31 - 1 distinct pairs. */
+typedef struct nl_trans nl_trans;
+int nl_trans_create(nl_trans **out, int device, int ndim, int64_t nz, int64_t ny, int64_t nx, char *err, size_t errlen);
+int nl_trans_destroy(nl_trans *trans);
+int nl_trans_frame(nl_trans *trans, const void *labels, int dtype, char *err, size_t errlen);
+int nl_trans_begin(nl_trans *trans, int64_t slots, char *err, size_t errlen);
+int nl_trans_count(nl_trans *trans, const void *prev, const void *next, int coord_dtype, int64_t n, int64_t row0, int *overflow, char *err,
+                   size_t errlen);
+int nl_trans_finish(nl_trans *trans, int64_t *n_entries, int64_t *n_dropped, int64_t *n_heads, int *overflow, char *err, size_t errlen);
+int nl_trans_fetch(nl_trans *trans, uint64_t *out, char *err, size_t errlen);
+int nl_trans_label_max(nl_trans *trans, int64_t *top, char *err, size_t errlen);
+int nl_trans_relabel(nl_trans *trans, const int32_t *lut, int64_t n_lut, char *err, size_t errlen);
+int nl_trans_fetch_frame(nl_trans *trans, int32_t *frame, char *err, size_t errlen);
+int nl_trans_kernel_ms(nl_trans *trans, float *ms, char *err, size_t errlen);
+
 /* ------------------------------------------------------------------ test hooks -------- */
 /* Known-answer hook for the fused device routine (filtering.py:581-585 + 744-766): for n explicit
    Hessians h6[n][6] = (hxx,hxy,hxz,hyy,hyz,hzz) writes out4[n][4] = (l1,l2,l3 sorted by |.|, Frangi

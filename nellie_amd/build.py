@@ -23,11 +23,12 @@ LIB = os.path.join(HERE, "libnellie_hip.so")
 # (nellie_hip_network.hip), the thinning (nellie_hip_thin.hip), Markers (nellie_markers.hip), tracking
 # (nellie_hip_track.hip), flow interpolation (nellie_hip_flow.hip), voxel reassignment (nellie_hip_reassign.hip) and voxel-level features
 # (nellie_hip_voxfeat.hip), node-level (nellie_hip_nodefeat.hip) and branch-level features (nellie_hip_branchfeat.hip) and the adjacency
-# maps (nellie_hip_adjacency.hip) and the voxel tracks of a label stack (nellie_hip_tracks.hip) and the analysis overlay (nellie_hip_overlay.hip) are separate so that an edit rebuilds one of
-# them (nl_host.h holds what all of them share, nl_stage.h what the last nine -- the stage handles -- share beyond that).
+# maps (nellie_hip_adjacency.hip) and the voxel tracks of a label stack (nellie_hip_tracks.hip) and the analysis overlay (nellie_hip_overlay.hip) and the label transitions
+# (nellie_hip_transitions.hip) are separate so that an edit rebuilds one of
+# them (nl_host.h holds what all of them share, nl_stage.h what the last ten -- the stage handles -- share beyond that).
 SOURCES = {"nellie_hip.hip": [], "nellie_walk.hip": [], "nellie_sample.hip": [], "nellie_comm.hip": [], "nellie_gauss.hip": [], "nellie_gzyx.hip": [], "nellie_label.hip": [],
            "nellie_markers.hip": [], "nellie_hip_track.hip": [], "nellie_hip_flow.hip": [], "nellie_hip_reassign.hip": [], "nellie_hip_voxfeat.hip": [],
-           "nellie_hip_nodefeat.hip": [], "nellie_hip_branchfeat.hip": [], "nellie_hip_adjacency.hip": [], "nellie_hip_tracks.hip": [], "nellie_hip_overlay.hip": [], "nellie_hip_network.hip": [], "nellie_hip_thin.hip": [],
+           "nellie_hip_nodefeat.hip": [], "nellie_hip_branchfeat.hip": [], "nellie_hip_adjacency.hip": [], "nellie_hip_tracks.hip": [], "nellie_hip_overlay.hip": [], "nellie_hip_transitions.hip": [], "nellie_hip_network.hip": [], "nellie_hip_thin.hip": [],
            "nellie_hv.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 # every include of the translation units: a stale library after editing one of them would silently test old kernels
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".inc", ".h"))) + [os.path.join("..", "..", "include", "nellie_amd.h")]

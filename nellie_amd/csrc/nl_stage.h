@@ -1,6 +1,7 @@
 // Internal: the host side that the stage handles share (nellie_hip_track.hip, nellie_hip_flow.hip, nellie_hip_reassign.hip,
-// nellie_hip_voxfeat.hip, nellie_hip_nodefeat.hip, nellie_hip_branchfeat.hip, nellie_hip_adjacency.hip, nellie_hip_tracks.hip, nellie_hip_overlay.hip) -- argument checks of the create calls, the device / stream / event-pair base of a handle, growing
-// device buffers and kernel timing.  Included by those nine units only.
+// nellie_hip_voxfeat.hip, nellie_hip_nodefeat.hip, nellie_hip_branchfeat.hip, nellie_hip_adjacency.hip, nellie_hip_tracks.hip, nellie_hip_overlay.hip,
+// nellie_hip_transitions.hip) -- argument checks of the create calls, the device / stream / event-pair base of a handle, growing
+// device buffers and kernel timing.  Included by those ten units only.
 #pragma once
 #include <initializer_list>
 #include "nl_host.h"

@@ -1,4 +1,4 @@
-// Shared by nellie_hip_reassign.hip, nellie_hip_voxfeat.hip, nellie_hip_nodefeat.hip, nellie_hip_branchfeat.hip, nellie_hip_adjacency.hip, nellie_hip_tracks.hip and nellie_hip_overlay.hip: a frame's 1-bit-per-voxel mask with its word populations, the
+// Shared by nellie_hip_reassign.hip, nellie_hip_voxfeat.hip, nellie_hip_nodefeat.hip, nellie_hip_branchfeat.hip, nellie_hip_adjacency.hip, nellie_hip_tracks.hip, nellie_hip_overlay.hip and nellie_hip_transitions.hip: a frame's 1-bit-per-voxel mask with its word populations, the
 // exclusive scan of int counts (workgroup sums, one workgroup over the sums, write) with its host driver, the rank of a set bit
 // of such a mask and the voxels' coordinates as flow queries.  The kernels are static: every translation unit that includes this
 // file has its own copy.

@@ -192,6 +192,16 @@ _PROTOS = {
     "nl_overlay_fetch_values": [_p, _p],
     "nl_overlay_fetch_frame": [_p, _p],
     "nl_overlay_kernel_ms": [_p, _p],
+    "nl_trans_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64],
+    "nl_trans_frame": [_p, _p, _int],
+    "nl_trans_begin": [_p, _i64],
+    "nl_trans_count": [_p, _p, _p, _int, _i64, _i64, C.POINTER(_int)],
+    "nl_trans_finish": [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int)],
+    "nl_trans_fetch": [_p, _p],
+    "nl_trans_label_max": [_p, C.POINTER(_i64)],
+    "nl_trans_relabel": [_p, _p, _i64],
+    "nl_trans_fetch_frame": [_p, _p],
+    "nl_trans_kernel_ms": [_p, _p],
     "nl_voxfeat_create": [C.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _f64],
     "nl_voxfeat_frame": [_p, _p, _p, _p, _int, _p, _int, C.POINTER(_i64)],
     "nl_voxfeat_fetch_voxels": [_p, _p, _p, _p, _p, _p],
@@ -246,6 +256,7 @@ _PLAIN = {
     "nl_reassign_destroy": (_int, [_p]),
     "nl_tracks_destroy": (_int, [_p]),
     "nl_overlay_destroy": (_int, [_p]),
+    "nl_trans_destroy": (_int, [_p]),
     "nl_voxfeat_destroy": (_int, [_p]),
     "nl_nodefeat_destroy": (_int, [_p]),
     "nl_branchfeat_destroy": (_int, [_p]),
@@ -1682,6 +1693,129 @@ class Overlay(_TimedParts, _Handle):
         if not (isinstance(out, np.ndarray) and out.shape == self.shape and out.dtype == self.painted and out.flags.c_contiguous and out.flags.writeable):
             raise ValueError(f"out must be a C-contiguous writeable {self.painted} array of shape {self.shape}")
         self._call("nl_overlay_fetch_frame", _ptr(out))
+        return out
+
+
+class Transitions(_TimedParts, _Handle):
+    """Device state of the label transition counts for one frame shape (include/nellie_amd.h nl_trans_*): two label frames -- frame()
+    makes the resident "next" frame "prev" and uploads a new "next" --, the counting table of a pair and the relabelled frame.
+    frame(), frame(), count(), then relabel() for the pair's later frame; count() again after each further frame()."""
+
+    _destroy, _noun = "nl_trans_destroy", "transitions object"
+    PARTS, _ms_symbol = ("clear", "count", "compact", "relabel"), "nl_trans_kernel_ms"
+    ROWS_PER_LAUNCH = 1 << 24             # rows of one upload and launch: at most 768 MB of coordinates are resident
+    SLOT_BYTES = 17                       # of device memory per slot: key, count, and the mask and scan words of the compaction
+    COORD_DTYPES = (np.dtype(np.uint16), np.dtype(np.uint32), np.dtype(np.uint64))
+
+    def __init__(self, shape, device=0):
+        self.ndim, self.shape, (nz, ny, nx), _ = _frame_geometry("label frames", (1.0,) * len(shape), shape=shape)
+        self.device = int(device)
+        self._create("nl_trans_create", self.device, self.ndim, nz, ny, nx)
+        self.frames = 0                   # frames uploaded so far
+        self.resident = 0                 # frames the device holds: 0, 1 ("next") or 2
+        self.regrown = self.table_slots = self.n_heads = self.n_rows = 0      # of the last count()
+
+    def frame(self, labels):
+        """the next label frame: int32 and int64 go up as they are, other integer types as int32 or (when a value needs it) int64"""
+        a = np.asarray(labels)
+        if a.dtype not in (np.int32, np.int64):
+            wide = a.dtype.kind in "iu" and a.size > 0 and not (-2 ** 31 <= int(a.min()) and int(a.max()) < 2 ** 31)
+            a = _frame_array(a, self.shape, "label frame", "transitions object", np.int64 if wide else np.int32)
+        a = _frame_array(a, self.shape, "label frame", "transitions object")
+        try:
+            self._call("nl_trans_frame", _ptr(a), DTYPE_CODES[a.dtype])
+        except BaseException:
+            self.resident = min(self.resident, 1)        # a failed upload costs the "prev" slot it was written into; "next" stays
+            raise
+        self.frames += 1
+        self.resident = min(self.resident + 1, 2)
+
+    def _coords(self, prev, next):
+        """both ends as (n, ndim) rows of one of COORD_DTYPES; other integer types become uint64, a negative coordinate is outside the frame"""
+        ends = [np.asarray(a) for a in (prev, next)]
+        for a in ends:
+            if a.ndim != 2 or a.shape[1] != self.ndim or a.shape != ends[0].shape:
+                raise ValueError(f"match coordinates must be two (n, {self.ndim}) arrays, got {ends[0].shape} and {ends[1].shape}")
+            if a.dtype.kind not in "iu":
+                raise TypeError(f"match coordinates of dtype {a.dtype}")
+        dtype = ends[0].dtype if ends[0].dtype == ends[1].dtype and ends[0].dtype in self.COORD_DTYPES else np.dtype(np.uint64)
+        if any(a.dtype.kind == "i" for a in ends):
+            neg = np.nonzero((ends[0] < 0).any(axis=1) | (ends[1] < 0).any(axis=1))[0]
+            if len(neg):
+                raise ValueError(f"row {int(neg[0])} holds a coordinate outside the frame {self.shape}")
+        return [a if a.dtype == dtype else a.astype(dtype) for a in ends], dtype
+
+    def default_slots(self, n_rows) -> int:
+        """a power of two of at least twice the rows (no more of them can be kept), as far as half the free device memory holds it"""
+        slots = 64
+        while slots < 2 * n_rows:
+            slots *= 2
+        free, _ = self.lib.device_mem_info(self.device)
+        while slots > 64 and slots * self.SLOT_BYTES > free // 2:
+            slots //= 2
+        return slots
+
+    def count(self, prev, next, table_slots=None, rows_per_launch=None):
+        """the matches (prev: coordinates in the "prev" frame, next: in the "next" frame) -> ((E, 3) int64 rows (src, dst, count) in
+        lexicographic order, n_dropped).  table_slots: the slots of the counting table to begin with (a power of two; None:
+        default_slots); a table that turns out too small is doubled and the pair repeated, `regrown` times.  rows_per_launch: rows
+        per upload and launch (None: ROWS_PER_LAUNCH); every chunk counts into the same table."""
+        (p, q), dtype = self._coords(prev, next)
+        n = len(p)
+        step = self.ROWS_PER_LAUNCH if rows_per_launch is None else int(rows_per_launch)
+        if step < 1:
+            raise ValueError("rows_per_launch must be at least 1")
+        self.regrown = self.n_heads = 0
+        self.n_rows = n
+        self.table_slots = 0
+        if n == 0:
+            return np.zeros((0, 3), np.int64), 0
+        if self.resident < 2:
+            raise NellieHipError(NL_ESTATE, "the transitions object holds fewer than two label frames")
+        slots = self.default_slots(n) if table_slots is None else int(table_slots)
+        over, m, dropped, heads = _int(0), _i64(0), _i64(0), _i64(0)
+        while True:
+            self._call("nl_trans_begin", slots)
+            over.value = 0
+            for r0 in range(0, n, step):
+                a, b = np.ascontiguousarray(p[r0:r0 + step]), np.ascontiguousarray(q[r0:r0 + step])
+                self._call("nl_trans_count", _ptr(a), _ptr(b), DTYPE_CODES[dtype], len(a), r0, C.byref(over))
+                if over.value:
+                    break
+            if not over.value:
+                self._call("nl_trans_finish", C.byref(m), C.byref(dropped), C.byref(heads), C.byref(over))
+            if not over.value:
+                break
+            slots *= 2
+            self.regrown += 1
+        self.table_slots, self.n_heads = slots, int(heads.value)
+        ent = np.empty((int(m.value), 2), np.uint64)
+        self._call("nl_trans_fetch", _ptr(ent))
+        ent = ent[np.argsort(ent[:, 0], kind="stable")]          # slot order depends on arrival; uint64 key order is (src, dst) order
+        table = np.stack([ent[:, 0] >> np.uint64(32), ent[:, 0] & np.uint64(0xFFFFFFFF), ent[:, 1]], axis=1).astype(np.int64)
+        return table, int(dropped.value)
+
+    def label_max(self) -> int:
+        """the largest label of the "next" frame"""
+        top = _i64(0)
+        self._call("nl_trans_label_max", C.byref(top))
+        return int(top.value)
+
+    def relabel(self, lut, out=None) -> np.ndarray:
+        """the "next" frame with every label b in (0, len(lut)) replaced by lut[b] and everything else 0, int32; `out`: a C-contiguous
+        writeable int32 array of the frame's shape (a memmap, say) that receives it"""
+        lut = np.asarray(lut)
+        if lut.ndim != 1:
+            raise ValueError("the label table must be 1-D")
+        if lut.dtype != np.int32:
+            _refuse_lossy_cast(lut, np.dtype(np.int32), "label table")
+        lut = np.ascontiguousarray(lut, dtype=np.int32)
+        if out is None:
+            out = np.empty(self.shape, np.int32)
+        if not (isinstance(out, np.ndarray) and out.shape == self.shape and out.dtype == np.int32 and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError(f"out must be a C-contiguous writeable int32 array of shape {self.shape}")
+        self._call("nl_trans_relabel", _ptr(lut), lut.size)
+        self._call("nl_trans_fetch_frame", _ptr(out))
         return out
 
 

@@ -7,7 +7,8 @@ Markers stage (reference run.py:88-89; it does not depend on Network) and writes
 im_border; `tracking=True` then runs this package's HuMomentTracking on them (run.py:91-92) and writes
 flow_vector_array; `reassign=True` runs this package's VoxelReassigner behind tracking (run.py:94-95) and writes
 im_obj_label_reassigned / im_branch_label_reassigned; `features=True` runs this package's Hierarchy last (run.py:97-98) and writes the
-five feature tables and the adjacency maps.  `full=True` turns all five on: the reference's whole run().  Without these keywords the
+five feature tables and the adjacency maps.  `full=True` turns all five on: the reference's whole run().  `transitions=True` runs
+this package's MatchTransitions behind VoxelReassigner and writes the label_transitions pickle; `full` leaves it off.  Without these keywords the
 later stages are left to the caller, who finds the two files Filter and Label wrote.
 """
 from __future__ import annotations
@@ -138,7 +139,7 @@ def _require_inputs(im_info, keyword, asked, written, with_keywords, stages):
 
 def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=None, timeit=False, device="auto",
         low_memory=False, markers=False, devices=None, shard=None, tracking=False, network=False, skeletonize=None, reassign=False,
-        features=False, full=False, solidity=False):
+        features=False, full=False, solidity=False, transitions=False):
     """nellie.run.run's signature (run.py:18-26): `file_info` is a FileInfo (this package's or any object with the same
     fields) from which the ImInfo is built as run.py:49 does; an ImInfo (anything with `pipeline_paths`) or a path / array
     is accepted too.  Returns the ImInfo.
@@ -155,7 +156,13 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
     FileNotFoundError names them before anything runs.
     full=True: network, markers, tracking, reassign and features, the reference's whole run().
     solidity=True (with features or full): Hierarchy fills `branch_solidity` and `organelle_solidity` from exact convex-hull voxel
-    counts; by default they stay NaN."""
+    counts; by default they stay NaN.
+    transitions=True (or "organelle"), or "branch": MatchTransitions of that level after VoxelReassigner (skipped for a stack
+    without T); it writes the label_transitions pickle (DESIGN.md section 26).  It needs voxel_matches, which reassign=True writes;
+    `full` does not turn it on."""
+    level = "organelle" if transitions is True else transitions
+    if transitions and level not in ("organelle", "branch"):
+        raise ValueError(f"transitions must be True, 'organelle' or 'branch', got {transitions!r}")
     if full:
         network = markers = tracking = reassign = features = True
     if network and skeletonize is None:
@@ -178,6 +185,11 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
                     "tracking=True and network=True", "HuMomentTracking and Network")
     _require_inputs(im_info, "features", features, dict(im_skel=network, im_pixel_class=network, im_skel_relabelled=network, im_distance=markers,
                                                         im_border=markers), "network=True and markers=True", "Network and Markers")
+    needed = dict(voxel_matches=reassign, im_instance_label=True)     # Label always writes the organelle labels
+    if level == "branch":
+        needed["im_skel_relabelled"] = network                         # read by the branch level only
+    _require_inputs(im_info, "transitions", bool(transitions) and not im_info.no_t, needed,
+                    "reassign=True" + (" and network=True" if level == "branch" else ""), "VoxelReassigner")
     t0 = time.perf_counter() if timeit else None
     preprocessing = Filter(im_info, remove_edges=remove_edges, device=device, low_memory=low_memory, devices=devices, shard=shard)
     preprocessing.run()
@@ -214,6 +226,12 @@ def run(file_info, remove_edges=False, otsu_thresh_intensity=False, threshold=No
         VoxelReassigner(im_info, device=device, low_memory=low_memory).run()
         if timeit:
             print(f"[timeit] VoxelReassigner: {time.perf_counter() - t4:.3f}s")
+    if transitions and not im_info.no_t:
+        from nellie_amd.tracking.match_transitions import MatchTransitions
+        t_tr = time.perf_counter()
+        MatchTransitions(im_info, level=level, device=device).run()
+        if timeit:
+            print(f"[timeit] MatchTransitions: {time.perf_counter() - t_tr:.3f}s")
     if features:
         from nellie_amd.feature_extraction.hierarchy import Hierarchy
         t5 = time.perf_counter()
